@@ -488,6 +488,20 @@ def train_mode(args, rank, world, dist):
 
 
 RESULT = sys.stdout     # where the ONE JSON line goes (main() moves everything else that writes to fd 1 over to stderr)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+DUMP_ROWS = 128              # rows of the audio --dump-outputs keeps when the whole batch would not fit (32.8 MB at 4 s, 16 kHz)
+
+
+def dump_outputs(directory, y):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the audio y [B, N] of OscillatorBank +
+    FilteredNoise -- as DIR/audio.npy (float32).  All rows when they fit in DUMP_MAX_BYTES, otherwise DUMP_ROWS rows drawn with a
+    fixed seed, in ascending order; their indices go to DIR/audio_rows.npy (float64)."""
+    B, N = y.shape
+    n = min(B, max(1, DUMP_MAX_BYTES // (4 * N + 8)))
+    rows = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, min(n, DUMP_ROWS), replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "audio.npy"), y[torch.from_numpy(rows).to(y.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(directory, "audio_rows.npy"), rows.astype(np.float64))
 
 
 def main():
@@ -525,7 +539,15 @@ def main():
                     help="rehearsal: initialise the process group (and run every collective of the N > 1 path) with ONE rank too")
     ap.add_argument("--noise", default="device", choices=["device", "resident"],
                     help="uniform draw: in-kernel Philox, or a [B,T,hop] tensor already resident in HBM")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="synth mode: after the timed steps, write the audio the last timed step computed (rank 0) as DIR/audio.npy "
+                         "(float32; a fixed, seeded sample of rows when the batch exceeds 64 MB) and the sampled row indices as "
+                         "DIR/audio_rows.npy; the inputs are the same on every run with the same arguments")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "synth":
+        ap.error("--dump-outputs: synth mode only")
     # libraries print to stdout on their own (gloo's "[Gloo] Rank 0 is connected ..." at the first collective): from here on
     # fd 1 is stderr for everybody, and only the result line goes to the real stdout
     global RESULT
@@ -570,7 +592,8 @@ def main():
     x = {k: torch.from_numpy(v).cuda() for k, v in ctl.items()}
     conf = Conf(shape)
     osc = ddsp.OscillatorBank(conf).cuda()
-    uniform = torch.rand(shape.batch, shape.frames, shape.hop, device="cuda") if args.noise == "resident" else None
+    uniform = torch.rand(shape.batch, shape.frames, shape.hop, device="cuda",
+                         generator=torch.Generator("cuda").manual_seed(5678 + rank)) if args.noise == "resident" else None
     if args.tiling:
         assert ddsp._lib.lib().ddsp_test_hooks_enabled(), "--tiling is a tuning hook: run with DDSP_TEST_HOOKS=1"
         ddsp._lib.check(ddsp._lib.lib().ddsp_osc_set_tiling(args.tiling), "ddsp_osc_set_tiling")
@@ -623,7 +646,9 @@ def main():
     extra = settle_clock(step, done, left) if left > 0 else 0
     done += extra
     settle_ms = 1e3 * (time.perf_counter() - t_settle)
-    elapsed, records, y = timed_pass(done)
+    # the same noise streams (Philox offsets) as the from-idle pass: the number of settle steps depends on the wall clock, and the
+    # audio of the last timed step must not (--dump-outputs)
+    elapsed, records, y = timed_pass(0)
     timed_first_launch = (cal_i[0] - (1 << 20)) + done + args.warmup   # index (from 0) of the first timed launch of each kernel in this process (calibration steps included)
     assert bool(torch.isfinite(y).all()), "non-finite audio"
     own_elapsed = elapsed
@@ -644,6 +669,8 @@ def main():
     # every rank's own clock and per-kernel averages, gathered so that the first multi-GPU run diagnoses itself: a slow rank
     # (clock, thermal, a noisy neighbour on its XCDs) shows up by index instead of hiding inside the MAX
     diag = gather_rows(dist, [1e3 * own_elapsed / args.steps] + [kern_ms.get(k, float("nan")) for k in KERNELS], world, rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)      # y: still the last timed step's audio (every later step allocated its own)
     del y
 
     if rank == 0:

@@ -7,6 +7,10 @@ import pytest
 # the process-global *_set_* hooks of libddsp_hip.so (kernel-form selection, fault injection) only work in processes that
 # opted in BEFORE the library was loaded (include/ddsp_hip.h: ddsp_test_hooks_enabled)
 os.environ.setdefault("DDSP_TEST_HOOKS", "1")
+# torch's CPU FFTs run on MKL, whose default code path depends on the host CPU's vendor and vector extensions and differs in the
+# last bits between hosts; the bit-exact fixture tests need the one path MKL reproduces on every x86 host (tools/make_goldens.py
+# captures the reference under the same setting).  MKL reads it at its first call, after this file is imported.
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

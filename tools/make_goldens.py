@@ -18,6 +18,7 @@ import os
 import sys
 
 os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")     # torch's CPU FFTs on MKL's host-independent code path, as tests/conftest.py sets it
 sys.dont_write_bytecode = True
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
