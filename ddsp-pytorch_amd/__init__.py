@@ -15,7 +15,9 @@ from .reverb import Reverb, causal_fft_convolve  # noqa: F401
 from .graphed import GraphedSynth, GraphedLiveDecoder, GraphedTrainStep  # noqa: F401
 from .gru import GRU, gru_forward, gru_backward, gru_status  # noqa: F401
 from .decoder import Controller, Decoder  # noqa: F401
+from .encoder import Crepe, F0Encoder, LoudnessEncoder, Encoder  # noqa: F401
+from .autoencoder import AutoEncoder  # noqa: F401
 from .training import MSSLoss, train_step, allreduce_gradients, OverlappedGradientReducer  # noqa: F401
 
-__all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency",
+__all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "Crepe", "F0Encoder", "LoudnessEncoder", "Encoder", "AutoEncoder", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency",
            "synthetic"]

@@ -165,6 +165,18 @@ def lib():
     L.ddsp_reverb_live_scratch_bytes.argtypes = [i32, i32]
     L.ddsp_reverb_live.restype = i32
     L.ddsp_reverb_live.argtypes = [vp] * 9 + [i32, i32, vp]
+    L.ddsp_resample.restype = i32
+    L.ddsp_resample.argtypes = [vp] * 4 + [ctypes.c_long, ctypes.c_long, i32, i32, i32, vp]
+    L.ddsp_crepe_frames.restype = i32
+    L.ddsp_crepe_frames.argtypes = [vp] * 3 + [ctypes.c_long, ctypes.c_long, i32, ctypes.c_long, vp]
+    L.ddsp_crepe_epilogue.restype = i32
+    L.ddsp_crepe_epilogue.argtypes = [vp] * 7 + [ctypes.c_long, i32, i32, i32, vp]
+    L.ddsp_pitch_decode.restype = i32
+    L.ddsp_pitch_decode.argtypes = [vp] * 8 + [ctypes.c_long, vp]
+    L.ddsp_loudness_supported.restype = i32
+    L.ddsp_loudness_supported.argtypes = [i32]
+    L.ddsp_loudness.restype = i32
+    L.ddsp_loudness.argtypes = [vp] * 3 + [ctypes.c_long, ctypes.c_long, i32, i32, vp]
     _lib = L
     return L
 
@@ -176,7 +188,8 @@ EXPORTS = ("ddsp_hip_abi_version", "ddsp_test_hooks_enabled", "ddsp_osc_scratch_
            "ddsp_spectral_loss_scratch_bytes", "ddsp_spectral_loss", "ddsp_scaled_sigmoid_forward", "ddsp_scaled_sigmoid_backward", "ddsp_heads_sigmoid_forward", "ddsp_heads_sigmoid_backward",
            "ddsp_ln_lrelu_scratch_bytes", "ddsp_ln_lrelu_forward", "ddsp_ln_lrelu_backward", "ddsp_ln_lrelu_forward_16", "ddsp_ln_lrelu_backward_16", "ddsp_outer_ln_lrelu_scratch_bytes", "ddsp_outer_ln_lrelu_forward", "ddsp_outer_ln_lrelu_backward",
            "ddsp_colsum_scratch_bytes", "ddsp_colsum", "ddsp_stft_frames", "ddsp_stft_frames_backward", "ddsp_mss_scale_scratch_bytes", "ddsp_mss_scale_supported", "ddsp_mss_scale", "ddsp_reverb_impulse", "ddsp_reverb_impulse_backward", "ddsp_spectral_mul", "ddsp_spectral_mul_backward",
-           "ddsp_reverb_live_scratch_bytes", "ddsp_reverb_live")
+           "ddsp_reverb_live_scratch_bytes", "ddsp_reverb_live",
+           "ddsp_resample", "ddsp_crepe_frames", "ddsp_crepe_epilogue", "ddsp_pitch_decode", "ddsp_loudness_supported", "ddsp_loudness")
 
 KERNEL_NAMES = {1: "osc_frame_totals", 2: "osc_scan", 3: "osc_frame_synth", 4: "noise_frame", 5: "noise_impulse_responses"}
 

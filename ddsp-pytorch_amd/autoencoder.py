@@ -1,0 +1,43 @@
+"""`AutoEncoder` (model/autoencoder/autoencoder.py): the encoder of `encoder.py` in front of this package's `Decoder`.
+
+  forward(x)                 audio [B, L] -> audio: pads (p // 2, p - p // 2) with p = n_fft - hop so that the loudness frames
+                             and the CREPE frames line up with the decoder's hop grid (autoencoder.py:17-22)
+  forward_live(x, hidden)    the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
+                             copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
+                             encoder, then Decoder.forward_live -> (audio as numpy, hidden)
+
+State-dict keys are the reference's (`encoder.f0_encoder.model.*`, `encoder.loudness_encoder.a_weight`, `decoder.*`).  CREPE
+weights come from `weights` or `conf.crepe_weights` (see encoder.F0Encoder).  The decoder's synthesis runs on the device only.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .decoder import Decoder
+from .encoder import Encoder
+
+
+class AutoEncoder(nn.Module):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None):
+        super().__init__()
+        self.encoder = Encoder(conf, weights)
+        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed)
+        self.padding = conf.n_fft - conf.hop_length
+        self.hop_length = conf.hop_length
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
+        return self.decoder(self.encoder(x))
+
+    def live_window(self, x: np.ndarray) -> torch.Tensor:
+        """The callback's window on the module's device, trimmed as autoencoder.py:28-30 trims it: [1, len - hop]."""
+        device = self.encoder.loudness_encoder.a_weight.device
+        audio_in = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).unsqueeze(0).to(device, non_blocking=False)
+        return audio_in[:, self.hop_length // 2:-(self.hop_length - self.hop_length // 2)]
+
+    def forward_live(self, x: np.ndarray, hidden: torch.Tensor):
+        z = self.encoder(self.live_window(x))
+        return self.decoder.forward_live(z, hidden)

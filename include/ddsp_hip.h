@@ -363,6 +363,45 @@ int ddsp_ln_lrelu_backward_16(const void *grad_y, const void *x, const void *y, 
                               const float *rstd, void *grad_x, float *grad_gamma, float *grad_beta, float *grad_xsum, void *scratch,
                               long rows, int D, float slope, int io_type, void *stream);
 
+/*
+ * Audio encoder (model/autoencoder/encoder.py, crepe/crepe.py): everything around the CREPE convolutions (MIOpen) and its
+ * classifier GEMM (rocBLAS).  All fp32, dense row-major.
+ *
+ * ddsp_resample      polyphase windowed-sinc resampler (torchaudio.transforms.Resample(orig, new) with its defaults, applied
+ *                    at encoder.py:57), rates already reduced by their gcd: x [B, L] -> y [B, ceil(nw * L / orig)],
+ *                    y[b, j] = sum_t table[r, t] * x[b, q * orig + first[r] + t]  (r = j mod nw, q = j div nw, x = 0 outside
+ *                    [0, L)).  table [nw, ntaps] and first [nw] (int32) are the kernel matrix's taps inside the sinc's support,
+ *                    built by the caller; nw * ntaps <= 16384 (DDSP_ERANGE otherwise).  Equal rates are the caller's identity.
+ * ddsp_crepe_frames  CREPE's normalisation and framing (encoder.py:60-72, crepe.py:119): y [B, Lr] -> stats [B, 2] (mean,
+ *                    unbiased std of each row) and frames [B * T, 254 + 1024 + 254] = (y[b, t * hop + p] - mean) / std inside,
+ *                    zero in the margins: conv1's padded input.  (T - 1) * hop + 1024 <= Lr.  A constant row gives NaN frames,
+ *                    as the reference does.
+ * ddsp_crepe_epilogue one CREPE layer after its bias-free convolution (crepe.py:128-133): conv [N, C, Lc] -> +bias -> ReLU ->
+ *                    BatchNorm (eval, eps 1e-3) -> max-pool (2, 1).  last = 0: out [N, C, 31 + Lc / 2 + 32], the next layer's
+ *                    padded input; last != 0: out [N, (Lc / 2) * C] at l * C + c, the classifier's rows (crepe.py:101).
+ * ddsp_pitch_decode  logits [N, 360] (classifier without bias) -> probabilities [N, 360] = sigmoid(logits + bias) (crepe.py:104),
+ *                    bin = torch.argmax (first maximum; a NaN is the maximum and the first NaN wins), f0 = f0_table[bin],
+ *                    harmonicity = probabilities[bin], cents = cents_table[bin] (encoder.py:120-128; tables [360] by the caller).
+ */
+int ddsp_resample(const float *x, const float *table, const int *first, float *y, long B, long L, int orig, int nw, int ntaps,
+                  void *stream);
+int ddsp_crepe_frames(const float *y, float *stats, float *frames, long B, long Lr, int hop, long T, void *stream);
+int ddsp_crepe_epilogue(const float *conv, const float *bias, const float *running_mean, const float *running_var, const float *gamma,
+                        const float *beta, float *out, long N, int C, int Lc, int last, void *stream);
+int ddsp_pitch_decode(const float *logits, const float *bias, const float *f0_table, const float *cents_table, float *probs, float *f0,
+                      float *harmonicity, float *cents, long N, void *stream);
+
+/*
+ * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
+ *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
+ * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
+ * float64 (the reference's parameter dtype; each bin's fp32 level plus its weight is rounded to fp32 once, as torch's `+=` does).
+ * One kernel, transforms in LDS; n_fft a power of two in [64, 2048] (ddsp_loudness_supported) and L >= n_fft, DDSP_ERANGE
+ * otherwise.
+ */
+int ddsp_loudness_supported(int n_fft);
+int ddsp_loudness(const float *x, const double *a_weight, float *out, long B, long L, int n_fft, int hop, void *stream);
+
 
 #ifdef __cplusplus
 }
