@@ -548,30 +548,12 @@ int pick_lpf_log(int F, int R, int mode)
     return -1;
 }
 
-}  // namespace
-
-namespace {
-int noise_forward_impl(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop, uint64_t seed,
-                       uint64_t offset, const uint64_t *offset_dev, int accumulate, void *workspace, size_t workspace_bytes,
-                       void *stream);
 // where the whole-batch matrix product pays for its extra launches (cosine operand + product; measured crossovers at 195 bands,
 // hop 512: forward between 2 752 and 5 504 frames, backward below 688): the real-time callback's 4 frames and the reference's
 // own training batch (16 x 172 frames) keep the cosine sums in the forward
 constexpr long kIrProductMinFramesFwd = 4096, kIrProductMinFramesBwd = 512;
-}
 
-extern "C" int ddsp_noise_forward(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop,
-                                  uint64_t seed, uint64_t offset, int accumulate, void *stream)
-{
-    return noise_forward_impl(Hmag, uniform, y, B, T, F, hop, seed, offset, nullptr, accumulate, nullptr, 0, stream);
-}
-
-extern "C" int ddsp_noise_forward_counter(const float *Hmag, float *y, int B, int T, int F, int hop, uint64_t seed,
-                                          const uint64_t *counter_dev, int accumulate, void *stream)
-{
-    if (!counter_dev) return DDSP_EINVAL;
-    return noise_forward_impl(Hmag, nullptr, y, B, T, F, hop, seed, 0, counter_dev, accumulate, nullptr, 0, stream);
-}
+}  // namespace
 
 extern "C" size_t ddsp_noise_workspace_bytes(int B, int T, int F, int hop)
 {
@@ -585,20 +567,12 @@ extern "C" int ddsp_noise_forward_ws(const float *Hmag, const float *uniform, fl
                                      size_t workspace_bytes, void *stream)
 {
     if (uniform && counter_dev) return DDSP_EINVAL;
-    return noise_forward_impl(Hmag, uniform, y, B, T, F, hop, seed, offset, counter_dev, accumulate, workspace, workspace_bytes, stream);
-}
-
-namespace {
-int noise_forward_impl(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop, uint64_t seed,
-                       uint64_t offset, const uint64_t *offset_dev, int accumulate, void *workspace, size_t workspace_bytes,
-                       void *stream)
-{
     if (B == 0) return 0;
     if (!Hmag || !y || B < 0 || T <= 0 || F < 2 || hop <= 0) return DDSP_EINVAL;
     NoiseParams p;
     p.Hm = Hmag; p.u = uniform; p.y = y;
     p.B = B; p.T = T; p.F = F; p.R = hop; p.S = 2 * (F - 1);
-    p.seed = seed; p.offset = offset; p.offset_dev = offset_dev; p.accumulate = accumulate; p.lpf_log = 0;
+    p.seed = seed; p.offset = offset; p.offset_dev = counter_dev; p.accumulate = accumulate; p.lpf_log = 0;
     p.zrows = nullptr; p.zs = 0;
     if ((long)B * T >= (1L << 31)) return DDSP_ERANGE;
     hipStream_t s = (hipStream_t)stream;
@@ -678,7 +652,6 @@ int noise_forward_impl(const float *Hmag, const float *uniform, float *y, int B,
     ddsp_prof::end(slot, s);
     return (int)hipGetLastError();
 }
-}  // namespace
 
 extern "C" int ddsp_noise_set_generic(int on)
 {
@@ -687,41 +660,17 @@ extern "C" int ddsp_noise_set_generic(int on)
     return 0;
 }
 
-static int noise_backward_impl(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop,
-                               uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *workspace, size_t workspace_bytes,
-                               void *stream);
-
-extern "C" int ddsp_noise_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop,
-                                   uint64_t seed, uint64_t offset, void *stream)
-{
-    return noise_backward_impl(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int ddsp_noise_backward_counter(const float *grad_y, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
-                                           const uint64_t *counter_dev, void *stream)
-{
-    if (!counter_dev) return DDSP_EINVAL;
-    return noise_backward_impl(grad_y, nullptr, grad_H, B, T, F, hop, seed, 0, counter_dev, nullptr, 0, stream);
-}
-
 extern "C" int ddsp_noise_backward_ws(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
                                       uint64_t offset, const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (uniform && counter_dev) return DDSP_EINVAL;
-    return noise_backward_impl(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, counter_dev, workspace, workspace_bytes, stream);
-}
-
-static int noise_backward_impl(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop,
-                               uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *workspace, size_t workspace_bytes,
-                               void *stream)
-{
     if (B == 0) return 0;
     if (!grad_y || !grad_H || B < 0 || T <= 0 || F < 2 || hop <= 0) return DDSP_EINVAL;
     if ((long)B * T >= (1L << 31)) return DDSP_ERANGE;
     NoiseBwdParams p;
     p.g = grad_y; p.u = uniform; p.gH = grad_H;
     p.B = B; p.T = T; p.F = F; p.R = hop; p.S = 2 * (F - 1);
-    p.seed = seed; p.offset = offset; p.offset_dev = offset_dev;
+    p.seed = seed; p.offset = offset; p.offset_dev = counter_dev;
     hipStream_t s = (hipStream_t)stream;
     if (!(g_force_generic.load(std::memory_order_relaxed) & 3)) {    // hop 512: correlation in the in-LDS FFT form (mode bits 0 / 1 keep the direct forms)
         hipError_t fe = hipSuccess;
@@ -729,7 +678,7 @@ static int noise_backward_impl(const float *grad_y, const float *uniform, float 
         const bool ws_ok = workspace && !(g_force_generic.load(std::memory_order_relaxed) & 16) && ir_product_shape(F, hop) &&
                            (long)B * T >= kIrProductMinFramesBwd && workspace_bytes >= ir_workspace_bytes((long)B * T, F) &&
                            ((uintptr_t)workspace % 16) == 0;
-        if (launch_noise_fft_backward(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, offset_dev, ws_ok ? workspace : nullptr, s, &fe))
+        if (launch_noise_fft_backward(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, counter_dev, ws_ok ? workspace : nullptr, s, &fe))
             return (int)fe;
     }
     const int lpf_log = pick_bwd_lpf_log(F, hop);

@@ -702,13 +702,6 @@ extern "C" size_t ddsp_osc_scratch_bytes(int B, int T, int H)
     return chunk_scratch_bytes(B, T, H);   // = the frame layout + the chunked form's small arrays behind it
 }
 
-extern "C" int ddsp_osc_forward(const float *f0, const float *c, const float *a, float *y, void *scratch,
-                                const float *live_in, float *live_out, float *dbg_phi, int B, int T, int H, int hop,
-                                int sample_rate, void *stream)
-{
-    return ddsp_osc_forward_ex(f0, c, a, y, scratch, live_in, live_out, dbg_phi, B, T, H, hop, sample_rate, 0u, stream);
-}
-
 extern "C" int ddsp_osc_forward_ex(const float *f0, const float *c, const float *a, float *y, void *scratch,
                                    const float *live_in, float *live_out, float *dbg_phi, int B, int T, int H, int hop,
                                    int sample_rate, unsigned flags, void *stream)

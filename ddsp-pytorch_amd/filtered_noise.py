@@ -14,9 +14,9 @@ from . import _lib
 
 
 def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, out=None, accumulate=False, counter=None):
-    """Raw launcher over the C ABI (include/ddsp_hip.h: ddsp_noise_forward).
-    `counter`: a 1-element int64 CUDA tensor holding the Philox offset of the in-kernel draw (read on the device at
-    launch time, so a captured launch draws from wherever the counter stands at each replay); excludes `uniform`."""
+    """Raw launcher over the C ABI (include/ddsp_hip.h: ddsp_noise_forward_ws).
+    `counter`: a 1-element int64 CUDA tensor added to `offset` to give the Philox offset of the in-kernel draw (read on the
+    device at launch time, so a captured launch draws from wherever the counter stands at each replay); excludes `uniform`."""
     if Hmag.dim() != 3:
         raise ValueError("expected H [B,T,F]")
     if not Hmag.is_cuda:
@@ -38,25 +38,18 @@ def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, 
         raise ValueError("counter must be a 1-element int64 CUDA tensor and excludes an injected draw")
     with torch.cuda.device(Hmag.device):
         stream = torch.cuda.current_stream().cuda_stream
+        # (the reference's default shape: impulse responses of the whole batch as one matrix-core product, include/ddsp_hip.h)
         ws_bytes = _lib.lib().ddsp_noise_workspace_bytes(B, T, F, hop)
-        if ws_bytes:
-            # (the reference's default shape: impulse responses of the whole batch as one matrix-core product, include/ddsp_hip.h)
-            ws = torch.empty(ws_bytes, device=Hmag.device, dtype=torch.uint8)
-            rc = _lib.lib().ddsp_noise_forward_ws(Hmag.data_ptr(), None if uniform is None else uniform.data_ptr(), out.data_ptr(),
-                                                  B, T, F, hop, seed, offset, None if counter is None else counter.data_ptr(),
-                                                  1 if accumulate else 0, ws.data_ptr(), ws_bytes, stream)
-        elif counter is not None:
-            rc = _lib.lib().ddsp_noise_forward_counter(Hmag.data_ptr(), out.data_ptr(), B, T, F, hop, seed, counter.data_ptr(),
-                                                       1 if accumulate else 0, stream)
-        else:
-            rc = _lib.lib().ddsp_noise_forward(Hmag.data_ptr(), None if uniform is None else uniform.data_ptr(),
-                                               out.data_ptr(), B, T, F, hop, seed, offset, 1 if accumulate else 0, stream)
-    _lib.check(rc, "ddsp_noise_forward")
+        ws = torch.empty(ws_bytes, device=Hmag.device, dtype=torch.uint8) if ws_bytes else None
+        rc = _lib.lib().ddsp_noise_forward_ws(Hmag.data_ptr(), None if uniform is None else uniform.data_ptr(), out.data_ptr(),
+                                              B, T, F, hop, seed, offset, None if counter is None else counter.data_ptr(),
+                                              1 if accumulate else 0, None if ws is None else ws.data_ptr(), ws_bytes, stream)
+    _lib.check(rc, "ddsp_noise_forward_ws")
     return out
 
 
 def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0, offset: int = 0, counter=None):
-    """Raw launcher of ddsp_noise_backward: grad_y [B,T*hop] -> grad_H [B,T,F] for the same draw as the forward
+    """Raw launcher of ddsp_noise_backward_ws: grad_y [B,T*hop] -> grad_H [B,T,F] for the same draw as the forward
     (`counter`: the device counter the forward read, still at the same value)."""
     grad_y = grad_y.detach().contiguous().float()
     B = grad_y.shape[0]
@@ -67,18 +60,11 @@ def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0
     with torch.cuda.device(grad_y.device):
         stream = torch.cuda.current_stream().cuda_stream
         ws_bytes = _lib.lib().ddsp_noise_workspace_bytes(B, T, n_filters, hop)
-        if ws_bytes:
-            ws = torch.empty(ws_bytes, device=grad_y.device, dtype=torch.uint8)
-            rc = _lib.lib().ddsp_noise_backward_ws(grad_y.data_ptr(), None if uniform is None else uniform.data_ptr(), grad_h.data_ptr(),
-                                                   B, T, n_filters, hop, seed, offset, None if counter is None else counter.data_ptr(),
-                                                   ws.data_ptr(), ws_bytes, stream)
-        elif counter is not None:
-            rc = _lib.lib().ddsp_noise_backward_counter(grad_y.data_ptr(), grad_h.data_ptr(), B, T, n_filters, hop, seed,
-                                                        counter.data_ptr(), stream)
-        else:
-            rc = _lib.lib().ddsp_noise_backward(grad_y.data_ptr(), None if uniform is None else uniform.data_ptr(),
-                                                grad_h.data_ptr(), B, T, n_filters, hop, seed, offset, stream)
-    _lib.check(rc, "ddsp_noise_backward")
+        ws = torch.empty(ws_bytes, device=grad_y.device, dtype=torch.uint8) if ws_bytes else None
+        rc = _lib.lib().ddsp_noise_backward_ws(grad_y.data_ptr(), None if uniform is None else uniform.data_ptr(), grad_h.data_ptr(),
+                                               B, T, n_filters, hop, seed, offset, None if counter is None else counter.data_ptr(),
+                                               None if ws is None else ws.data_ptr(), ws_bytes, stream)
+    _lib.check(rc, "ddsp_noise_backward_ws")
     return grad_h
 
 

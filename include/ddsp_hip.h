@@ -5,12 +5,12 @@
  * Python nn.Modules made of stock torch ops.  These entry points are what a binding
  * for that path binds instead of those op sequences:
  *
- *   ddsp_osc_forward      replaces OscillatorBank.forward / .live
- *                         (model/ddsp/harmonic_oscillator.py:57-62 and :64-75, i.e.
- *                          prepare_harmonics :24-37, generate_phases :39-43, generate_signal :45-50)
- *   ddsp_noise_forward    replaces FilteredNoise.forward
- *                         (model/ddsp/filtered_noise.py:40-53, i.e. amp_to_impulse_response :7-22,
- *                          fft_convolve :25-32, and the torch.rand draw :44-48)
+ *   ddsp_osc_forward_ex    replaces OscillatorBank.forward / .live
+ *                          (model/ddsp/harmonic_oscillator.py:57-62 and :64-75, i.e.
+ *                           prepare_harmonics :24-37, generate_phases :39-43, generate_signal :45-50)
+ *   ddsp_noise_forward_ws  replaces FilteredNoise.forward
+ *                          (model/ddsp/filtered_noise.py:40-53, i.e. amp_to_impulse_response :7-22,
+ *                           fft_convolve :25-32, and the torch.rand draw :44-48)
  *
  * Conventions: plain pointers and sizes only (no torch types); every pointer is DEVICE memory
  * unless said otherwise; tensors are dense row-major fp32 with the reference's shapes; nothing
@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DDSP_HIP_ABI_VERSION 4
+#define DDSP_HIP_ABI_VERSION 5
 
 #define DDSP_EINVAL (-1)   /* null pointer / non-positive size */
 #define DDSP_ERANGE (-2)   /* shape outside what the kernels are built for */
@@ -48,7 +48,7 @@ int ddsp_hip_abi_version(void);
 int ddsp_test_hooks_enabled(void);
 
 /*
- * Bytes of device scratch ddsp_osc_forward needs for a [B,T,H] problem (any hop): frame-rate increments fp32 [B,T,H] +
+ * Bytes of device scratch ddsp_osc_forward_ex needs for a [B,T,H] problem (any hop): frame-rate increments fp32 [B,T,H] +
  * normalised amplitudes fp32 [B,T,H] + an fp64 region of [B,T,H] (chunk totals, or frame-start phases + their superblock
  * totals) + a few int32 arrays of at most B*T entries (16*B*T*H bytes + ~2*B*(T+3)/4*H + 12*B*T + 4*T*(B+16) + flag words;
  * 256-byte aligned parts).
@@ -62,15 +62,11 @@ size_t ddsp_osc_scratch_bytes(int B, int T, int H);
  *   live_in  [H]   nullable: phase offsets added to the first increment row of batch row 0 (:70)
  *   live_out [H]   nullable: receives the last phase row of batch row 0 (:72); must not alias live_in
  *   dbg_phi  [B,T*hop,H] nullable (tests only): the wrapped phases, bit-exact w.r.t. torch CPU
+ *   flags          0 or DDSP_OSC_KEEP_FRAME_SCRATCH.  With it, `scratch` keeps the frame-rate layout (start phase of every
+ *                  frame) that ddsp_osc_backward re-walks: set it when the scratch goes to the backward.  Without it the
+ *                  forward is free to take the chunked form (power-of-two hops >= 64), whose scratch the backward cannot
+ *                  use (it then returns NaN gradients, not an error code).
  * Inputs are not modified.  Requires T*hop < 2^24 (exact fp32 sample indices).
- */
-int ddsp_osc_forward(const float *f0, const float *c, const float *a, float *y, void *scratch,
-                     const float *live_in, float *live_out, float *dbg_phi,
-                     int B, int T, int H, int hop, int sample_rate, void *stream);
-/*
- * The same with flags.  DDSP_OSC_KEEP_FRAME_SCRATCH: the caller will hand `scratch` to ddsp_osc_backward, which re-walks
- * the frame-rate layout (start phase of every frame); without it the forward is free to take the chunked form
- * (power-of-two hops >= 64), whose scratch the backward refuses (it then returns NaN gradients).
  */
 #define DDSP_OSC_KEEP_FRAME_SCRATCH 1u
 int ddsp_osc_forward_ex(const float *f0, const float *c, const float *a, float *y, void *scratch,
@@ -78,60 +74,50 @@ int ddsp_osc_forward_ex(const float *f0, const float *c, const float *a, float *
                         int B, int T, int H, int hop, int sample_rate, unsigned flags, void *stream);
 
 /*
- * Filtered noise (filtered_noise.py:40-53).
- *   Hmag [B,T,F] filter magnitudes -> y [B, T*hop]; per frame: zero-phase IR (irfft, length 2(F-1)),
- *   periodic-Hann window, re-wrapped to hop samples (cropped when hop < 2(F-1)), then the first hop
- *   samples of the linear convolution with uniform noise in [-1,1); frames are concatenated.
- *   uniform [B,T,hop] nullable: the U[0,1) draw (what torch.rand returned, filtered_noise.py:44-48).
- *                      NULL => drawn on the device with Philox4x32-10 from (seed, offset); that stream is
- *                      NOT the torch CPU generator's (documented in DESIGN.md).
- *   accumulate != 0: y += noise instead of y = noise (fuses decoder.py:132 `harmonics + noise`).
+ * Filtered noise (filtered_noise.py:40-53) and its backward.  Both draw the same noise from the same arguments:
+ *   uniform [B,T,hop]  nullable: the U[0,1) draw (what torch.rand returned, filtered_noise.py:44-48).
+ *                      NULL => drawn on the device with Philox4x32-10 from `seed`, starting at counter
+ *                      offset + *counter_dev; that stream is NOT the torch CPU generator's (documented in DESIGN.md).
+ *   counter_dev        nullable (NULL counts as 0): a device uint64, only read, at launch time.  The caller advances it
+ *                      between calls, e.g. by a node of the same hipGraph: a replayed graph then draws fresh noise every time.
+ *                      uniform and counter_dev exclude each other (both non-NULL: DDSP_EINVAL).
+ *   workspace          nullable: device memory of workspace_bytes, 16-byte aligned, contents undefined before and after.
+ *                      ddsp_noise_workspace_bytes is 0 for the shapes that have no use for one; for the reference's default shape
+ *                      (195 bands at hop 512, config/default.py:15,19: 2(F-1) = 388 has no radix-2 transform) at >= 512 frames
+ *                      it holds the cosine operand and the impulse responses of the whole batch, which are then ONE split-bf16
+ *                      matrix-core product (csrc/ddsp_noise_ir.hip) instead of F x S/4 cosine sums per frame pair: 2x faster
+ *                      end to end at large batches (the forward takes it from 4 096 frames on, the backward from 512: below,
+ *                      the extra launches cost more than the sums).  A NULL or too small workspace keeps the sums (same
+ *                      results within rounding).
+ *
+ * ddsp_noise_forward_ws   Hmag [B,T,F] filter magnitudes -> y [B, T*hop]; per frame: zero-phase IR (irfft, length 2(F-1)),
+ *                         periodic-Hann window, re-wrapped to hop samples (cropped when hop < 2(F-1)), then the first hop
+ *                         samples of the linear convolution with uniform noise in [-1,1); frames are concatenated.
+ *                         accumulate != 0: y += noise instead of y = noise (fuses decoder.py:132 `harmonics + noise`).
+ * ddsp_noise_backward_ws  gradient w.r.t. Hmag (autograd of filtered_noise.py:40-53; the noise draw is a constant):
+ *                         grad_y [B,T*hop] -> grad_H [B,T,F].  `uniform`, `seed`, `offset` and the value *counter_dev holds
+ *                         must be the forward call's (a caller that owns the counter advances it only after both), so that
+ *                         the backward sees the same draw as the forward.  For the default shape with a workspace the
+ *                         correlation runs in the in-LDS FFT form and dH = dz C^T is one matrix-core product, instead of
+ *                         the direct kernels' F x S/2 cosine sums per frame.  The workspace need not be the forward's.
  */
-int ddsp_noise_forward(const float *Hmag, const float *uniform, float *y,
-                       int B, int T, int F, int hop, uint64_t seed, uint64_t offset,
-                       int accumulate, void *stream);
-/* Same with the in-kernel draw starting at *counter_dev (a device uint64 the caller advances between calls, e.g. by a
- * node of the same hipGraph: a replayed graph then draws fresh noise every time).  counter_dev is only read. */
-int ddsp_noise_forward_counter(const float *Hmag, float *y, int B, int T, int F, int hop, uint64_t seed,
-                               const uint64_t *counter_dev, int accumulate, void *stream);
-/* The same launch with a caller-provided workspace (device memory, 16-byte aligned, contents undefined before and after).
- * ddsp_noise_workspace_bytes is 0 for the shapes that have no use for one; for the reference's default shape (195 bands at
- * hop 512, config/default.py:15,19: 2(F-1) = 388 has no radix-2 transform) at >= 512 frames it holds the cosine operand and the
- * impulse responses of the whole batch, which are then ONE split-bf16 matrix-core product (csrc/ddsp_noise_ir.hip) instead of
- * F x S/4 cosine sums per frame pair: 2x faster end to end at large batches (the forward takes it from 4 096 frames on, the
- * backward from 512: below, the extra launches cost more than the sums).  A NULL / too small workspace takes the ddsp_noise_forward path
- * (same results within rounding).  uniform and counter_dev exclude each other (both NULL: the draw starts at `offset`). */
 size_t ddsp_noise_workspace_bytes(int B, int T, int F, int hop);
 int ddsp_noise_forward_ws(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop, uint64_t seed,
                           uint64_t offset, const uint64_t *counter_dev, int accumulate, void *workspace, size_t workspace_bytes,
                           void *stream);
-/* Backward of the same (ddsp_noise_backward / _counter with a workspace of ddsp_noise_workspace_bytes: for the default shape the
- * correlation runs in the in-LDS FFT form and dH = dz C^T is one matrix-core product, instead of the direct kernels' F x S/2
- * cosine sums per frame).  The workspace need not be the forward's. */
 int ddsp_noise_backward_ws(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
                            uint64_t offset, const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
- * Backward of ddsp_osc_forward w.r.t. c and a (autograd of harmonic_oscillator.py:24-62; f0 carries no gradient,
- * decoder.py:105).  `fwd_scratch` is the scratch buffer the matching ddsp_osc_forward call filled (same B,T,H,hop,
- * sample_rate, same tiling); `bwd_scratch` >= ddsp_osc_backward_scratch_bytes(B,T,H).
+ * Backward of ddsp_osc_forward_ex w.r.t. c and a (autograd of harmonic_oscillator.py:24-62; f0 carries no gradient,
+ * decoder.py:105).  `fwd_scratch` is the scratch buffer the matching ddsp_osc_forward_ex call filled with
+ * DDSP_OSC_KEEP_FRAME_SCRATCH (same B,T,H,hop, sample_rate, same tiling); `bwd_scratch` >= ddsp_osc_backward_scratch_bytes(B,T,H).
  *   grad_y [B,T*hop] -> grad_c [B,T,H], grad_a [B,T,1]
  */
 size_t ddsp_osc_backward_scratch_bytes(int B, int T, int H);
 int ddsp_osc_backward(const float *grad_y, const float *f0, const float *c, const float *a, const void *fwd_scratch,
                       void *bwd_scratch, float *grad_c, float *grad_a, int B, int T, int H, int hop, int sample_rate,
                       void *stream);
-
-/*
- * Backward of ddsp_noise_forward w.r.t. Hmag (autograd of filtered_noise.py:40-53; the noise draw is a constant).
- * `uniform`/`seed`/`offset` must be the forward call's.   grad_y [B,T*hop] -> grad_H [B,T,F]
- */
-int ddsp_noise_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop,
-                        uint64_t seed, uint64_t offset, void *stream);
-/* The backward of a ddsp_noise_forward_counter call: the same draw, read from the same device counter (which the caller
- * advances only after both). */
-int ddsp_noise_backward_counter(const float *grad_y, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
-                                const uint64_t *counter_dev, void *stream);
 
 /*
  * Tuning hook (benchmarks only): force the number of harmonics each lane keeps in registers
@@ -143,11 +129,11 @@ int ddsp_osc_set_tiling(int harmonics_per_lane);
  * (chunked form where it applies and the batch fills the row blocks to >= 88 %), 2 = chunked form for every eligible shape
  * whatever the batch (tests of small batches).  Same results within rounding. */
 int ddsp_osc_set_path(int path);
-/* What ddsp_osc_forward would launch for this shape on the current device (HOST array of >= 8 ints): out[0] harmonics per
+/* What ddsp_osc_forward_ex (flags 0) would launch for this shape on the current device (HOST array of >= 8 ints): out[0] harmonics per
  * lane, [1] lanes per row group, [2] 1 = chunked form, then its [3] chunk length in samples, [4] chunks per row,
  * [5] row blocks, [6] compute units and [7] resident workgroups per unit the chunk length was sized for. */
 int ddsp_osc_plan(int B, int T, int H, int hop, int sample_rate, int *out, int cap);
-/* Diagnostic, SYNCHRONISES `stream`: the shader clock (GHz) one wavefront of the synth kernel of the LAST ddsp_osc_forward
+/* Diagnostic, SYNCHRONISES `stream`: the shader clock (GHz) one wavefront of the synth kernel of the LAST ddsp_osc_forward_ex
  * on `scratch` (same B, T, H, hop, sample_rate, same hooks) ran at: in-kernel shader-clock ticks over 100 MHz wall-clock
  * ticks between that wavefront's start and end.  ghz is a HOST pointer; 0.0 if the kernel did not run.  Not for launch paths. */
 int ddsp_osc_clock(const void *scratch, int B, int T, int H, int hop, int sample_rate, double *ghz, void *stream);
@@ -164,7 +150,7 @@ int ddsp_noise_get_residency(void);
  * (any hop) instead of the batched ones (hop % 8 == 0, tile fits LDS); bit 1 keeps the direct (time-domain) forms where the
  * in-LDS FFT form would run (hop 512 with 2(F-1) <= hop); bit 2 takes the FFT form for hop 256 too (correct, not faster);
  * bit 3 keeps the batched kernel where the wavefront-private form would run (hop 128, 65 bands); bit 4 keeps the cosine sums
- * where ddsp_noise_forward_ws would take the matrix product;
+ * where a workspace would give the matrix product;
  * (l + 1) << 8 forces 64 >> l frames per workgroup in the batched forward kernel (l = 0..3); 0 restores the defaults.
  * Same results within rounding. */
 int ddsp_noise_set_generic(int on);

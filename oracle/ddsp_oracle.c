@@ -218,7 +218,7 @@ void ddsp_oracle_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uin
 }
 
 /*
- * The uniform draw of the in-kernel stream, laid out like torch.rand(B,T,R) (include/ddsp_hip.h, ddsp_noise_forward):
+ * The uniform draw of the in-kernel stream, laid out like torch.rand(B,T,R) (include/ddsp_hip.h, ddsp_noise_forward_ws):
  * frame f (= b*T + t), sample m: word (m & 3) of Philox(counter = offset + f*ceil(R/4) + (m >> 2), key = seed),
  * counter and key as 64-bit values split low word first, upper counter words 0; u = (word >> 8) * 2^-24 in [0,1).
  * The kernels then form x = 2u - 1 exactly as the reference does with its own draw (:45).

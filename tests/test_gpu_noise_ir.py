@@ -79,8 +79,9 @@ def test_matrix_product_form_silent_and_unequal_frames():
     assert np.max(np.abs(y - ref)) <= TOL * max(1.0, float(np.max(np.abs(ref))))
 
 
-def test_workspace_contract():
-    """ddsp_noise_workspace_bytes is 0 where no form uses one; ddsp_noise_forward_ws without a workspace is ddsp_noise_forward."""
+def test_workspace_contract_abi5():
+    """ddsp_noise_workspace_bytes is 0 where no form uses one; ddsp_noise_forward_ws without a workspace (or with one too small) is
+    the cosine-sum path, bit for bit."""
     L = ddsp._lib.lib()
     for B, T, nf, hop in ((512, 375, 257, 512), (512, 500, 65, 128), (1, 500, 195, 512), (1, 4, 195, 512), (8, 64, 195, 256), (0, 5, 195, 512)):
         assert L.ddsp_noise_workspace_bytes(B, T, nf, hop) == 0
@@ -92,14 +93,19 @@ def test_workspace_contract():
     y0 = torch.empty(2, 2100 * 512, device="cuda")
     y1 = torch.empty_like(y0)
     s = torch.cuda.current_stream().cuda_stream
-    assert L.ddsp_noise_forward(Hn.data_ptr(), None, y0.data_ptr(), 2, 2100, 195, 512, 11, 0, 0, s) == 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert L.ddsp_noise_set_generic(16) == 0          # bit 4: the cosine sums despite a full workspace, the path a NULL one takes
+    try:
+        assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y0.data_ptr(), 2, 2100, 195, 512, 11, 0, None, 0, ws.data_ptr(),
+                                       ctypes.c_size_t(need), s) == 0
+    finally:
+        L.ddsp_noise_set_generic(0)
     assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y1.data_ptr(), 2, 2100, 195, 512, 11, 0, None, 0, None, 0, s) == 0
     assert torch.equal(y0, y1)
     small = torch.empty(need - 16, dtype=torch.uint8, device="cuda")      # too small: the same fallback, no overrun
     assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y1.data_ptr(), 2, 2100, 195, 512, 11, 0, None, 0, small.data_ptr(),
                                    ctypes.c_size_t(need - 16), s) == 0
     assert torch.equal(y0, y1)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y1.data_ptr(), 2, 2100, 195, 512, 11, 0, None, 0, ws.data_ptr(),
                                    ctypes.c_size_t(need), s) == 0
     assert float((y0 - y1).abs().max()) <= TOL * max(1.0, float(y0.abs().max()))

@@ -1,7 +1,7 @@
 """GPU parity tests proper: the HIP path (through the C ABI) against the golden fixtures captured
 from the reference and against the CPU oracle on the same seeded inputs.
 
-Tolerances: wrapped phases bit-exact (debug output of ddsp_osc_forward); audio <= 1e-5 absolute
+Tolerances: wrapped phases bit-exact (debug output of ddsp_osc_forward_ex); audio <= 1e-5 absolute
 (BASELINE.json north_star); the live state `last_phases` bit-exact; noise <= 2e-6 (+ the oracle's own
 5e-7 distance from the reference's fp32 FFT, so 1e-5 is the contract and we assert tighter).
 """
@@ -43,9 +43,9 @@ def run_osc(g, debug=False, prefix=""):
     return y.cpu().numpy(), (phi.cpu().numpy() if debug else None)
 
 
-def test_native_library_is_loaded():
+def test_native_library_is_loaded_abi5():
     L = ddsp._lib.lib()
-    assert L.ddsp_hip_abi_version() == ddsp._lib.ABI_VERSION == 4
+    assert L.ddsp_hip_abi_version() == ddsp._lib.ABI_VERSION == 5
     with open("/proc/self/maps") as f:
         assert "libddsp_hip.so" in f.read()
 
@@ -230,6 +230,25 @@ def test_filtered_noise_module_device_stream_advances_like_the_oracle():
         ref = oracle.noise_forward(Hn, None, 128, seed=99, offset=off)
         assert np.max(np.abs(y - ref)) <= 2e-6
         off += B * T * 32
+
+
+def test_device_draw_starts_at_offset_plus_counter():
+    """The in-kernel draw starts at offset + *counter (include/ddsp_hip.h: ddsp_noise_forward_ws), also on a shape that takes no
+    workspace (hop 128 / 65 bands: the wavefront-private form, 129 frames leave a remainder for the batched kernel); the
+    backward reads the same draw."""
+    rng = np.random.default_rng(21)
+    B, T, nf, hop = 3, 43, 65, 128
+    assert ddsp._lib.lib().ddsp_noise_workspace_bytes(B, T, nf, hop) == 0
+    Hn = syn.controller_range(rng.standard_normal((B, T, nf), dtype=np.float32))
+    seed, offset, count = 17, (1 << 32) + 7, 12345
+    counter = torch.tensor([count], dtype=torch.int64, device="cuda")
+    y = ddsp.noise_forward(dev(Hn), hop, seed=seed, offset=offset, counter=counter)
+    ref = oracle.noise_forward(Hn, None, hop, seed=seed, offset=offset + count)
+    assert np.max(np.abs(y.cpu().numpy() - ref)) <= 2e-6 * max(1.0, float(np.max(np.abs(ref))))
+    assert torch.equal(y, ddsp.noise_forward(dev(Hn), hop, seed=seed, offset=offset + count))
+    g = torch.from_numpy(rng.standard_normal((B, T * hop), dtype=np.float32)).cuda()
+    assert torch.equal(ddsp.noise_backward(g, hop, nf, seed=seed, offset=offset, counter=counter),
+                       ddsp.noise_backward(g, hop, nf, seed=seed, offset=offset + count))
 
 
 def test_decoder_wiring_g11():
@@ -490,14 +509,14 @@ def test_osc_edge_shapes_vs_oracle(B, T, H, hop, sr):
     assert np.max(np.abs(y2.cpu().numpy() - ref)) <= TOL_Y
 
 
-def test_shape_limits_are_reported_not_computed():
+def test_shape_limits_are_reported_not_computed_abi5():
     L = ddsp._lib.lib()
     x = torch.zeros(4, device="cuda")
     p = x.data_ptr()
     # 1601 harmonics: no tiling; T*hop >= 2^24: sample indices not exact in fp32
-    assert L.ddsp_osc_forward(p, p, p, p, p, None, None, None, 1, 1, 1601, 1, 16000, None) == -2
-    assert L.ddsp_osc_forward(p, p, p, p, p, None, None, None, 1, 1 << 14, 1, 1 << 10, 16000, None) == -2
-    assert L.ddsp_noise_forward(p, None, p, 1, 1, 1, 8, 0, 0, 0, None) == -1          # F < 2
+    assert L.ddsp_osc_forward_ex(p, p, p, p, p, None, None, None, 1, 1, 1601, 1, 16000, 0, None) == -2
+    assert L.ddsp_osc_forward_ex(p, p, p, p, p, None, None, None, 1, 1 << 14, 1, 1 << 10, 16000, 0, None) == -2
+    assert L.ddsp_noise_forward_ws(p, None, p, 1, 1, 1, 8, 0, 0, None, 0, None, 0, None) == -1          # F < 2
     with pytest.raises(ValueError):
         ddsp.noise_forward(torch.zeros(1, 2, 5, device="cuda"), 8, uniform=torch.zeros(1, 2, 7, device="cuda"))
     empty = ddsp.osc_forward(torch.zeros(0, 3, 1, device="cuda"), torch.zeros(0, 3, 4, device="cuda"),

@@ -25,30 +25,76 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(ddsp_[a-z0-9_]+)\s*\(", text)))
 
 
+C_TYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long": ctypes.c_long, "size_t": ctypes.c_size_t,
+           "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def declared_prototypes():
+    """-> {name: (return type, [(base type, is pointer)])} of every declaration in include/ddsp_hip.h ("const" and names dropped)."""
+    text = open(os.path.join(ROOT, "include", "ddsp_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"(\w+)\s+(ddsp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        args = []
+        for param in params.split(","):
+            words = param.replace("*", " * ").split()
+            if words == ["void"]:
+                continue
+            words = [w for w in words if w != "const"]
+            assert len([w for w in words if w != "*"]) == 2, (name, param)     # one type word and a parameter name
+            args.append((words[0], "*" in words))
+        protos[name] = (ret, args)
+    return protos
+
+
+def binds(decl, ct):
+    """A pointer binds as c_void_p or as POINTER(the pointee's type); anything else as its own ctypes type."""
+    base, pointer = decl
+    if pointer:
+        return ct is ctypes.c_void_p or (issubclass(ct, ctypes._Pointer) and ct._type_ is C_TYPES.get(base))
+    return ct is C_TYPES[base]
+
+
 def test_header_symbols_exported():
     L = ctypes.CDLL(ddsp._lib.SO_PATH)
     syms = declared_symbols()
-    assert set(syms) == set(ddsp._lib.EXPORTS)
+    table = ddsp._lib.SIGNATURES
+    assert set(syms) == set(ddsp._lib.EXPORTS) == set(table)
     for s in syms:
         assert hasattr(L, s), s
+    # the binding's types are the header's, parameter by parameter: a wrong argtypes entry would pass garbage to a kernel
+    protos = declared_prototypes()
+    assert list(protos) == list(table)                  # (every declaration parsed, the table in header order)
+    for name, (ret, args) in protos.items():
+        restype, argtypes = table[name]
+        assert restype is C_TYPES[ret], name
+        assert len(argtypes) == len(args), name
+        for i, (decl, ct) in enumerate(zip(args, argtypes)):
+            assert binds(decl, ct), (name, i, decl, ct)
 
 
-def test_abi_version_and_scratch_size():
+def test_abi_version_5_and_scratch_size():
     L = ddsp._lib.lib()
-    assert L.ddsp_hip_abi_version() == 4 == ddsp._lib.ABI_VERSION
+    assert L.ddsp_hip_abi_version() == 5 == ddsp._lib.ABI_VERSION
     assert L.ddsp_osc_scratch_bytes(0, 1, 1) == 0
     n = 64 * 500 * 100
     assert L.ddsp_osc_scratch_bytes(64, 500, 100) >= 16 * n
 
 
-def test_argument_validation_without_gpu():
+def test_argument_validation_without_gpu_abi5():
     L = ddsp._lib.lib()
-    assert L.ddsp_osc_forward(None, None, None, None, None, None, None, None, 1, 1, 1, 1, 16000, None) == -1
-    assert L.ddsp_osc_forward(None, None, None, None, None, None, None, None, 0, 1, 1, 1, 16000, None) == 0  # empty batch
-    assert L.ddsp_noise_forward(None, None, None, 1, 1, 65, 128, 0, 0, 0, None) == -1
+    assert L.ddsp_osc_forward_ex(None, None, None, None, None, None, None, None, 1, 1, 1, 1, 16000, 0, None) == -1
+    assert L.ddsp_osc_forward_ex(None, None, None, None, None, None, None, None, 0, 1, 1, 1, 16000, 0, None) == 0  # empty batch
+    assert L.ddsp_noise_forward_ws(None, None, None, 1, 1, 65, 128, 0, 0, None, 0, None, 0, None) == -1
     assert L.ddsp_osc_set_tiling(7) == -2 and L.ddsp_osc_set_tiling(0) == 0
-    # the callers' entry points validate before touching the device as well
-    assert L.ddsp_noise_forward_counter(None, None, 1, 1, 65, 128, 0, None, 0, None) == -1
+    # the callers' entry points validate before touching the device as well; an injected draw excludes a device counter
+    # (checked first: with an empty batch the call would otherwise return 0 without a launch)
+    word = ctypes.c_uint64(0)                      # (a valid address; nothing is read from it)
+    p = ctypes.addressof(word)
+    assert L.ddsp_noise_forward_ws(p, p, p, 0, 1, 65, 128, 0, 0, p, 0, None, 0, None) == -1
+    assert L.ddsp_noise_forward_ws(p, None, p, 0, 1, 65, 128, 0, 0, p, 0, None, 0, None) == 0
+    assert L.ddsp_noise_backward_ws(p, p, p, 0, 1, 65, 128, 0, 0, p, None, 0, None) == -1
+    assert L.ddsp_noise_backward_ws(p, None, p, 0, 1, 65, 128, 0, 0, p, None, 0, None) == 0
     assert L.ddsp_gru_forward(None, None, None, None, None, None, None, None, None, 1, 1, 16, None) == -1
     assert L.ddsp_gru_forward(None, None, None, None, None, None, None, None, None, 0, 1, 16, None) == 0   # empty batch
     assert L.ddsp_gru_backward(None, None, None, None, None, None, None, None, None, None, None, 1, 1, 16, None) == -1
@@ -60,7 +106,7 @@ def test_argument_validation_without_gpu():
     assert L.ddsp_ln_lrelu_scratch_bytes(512) > 0
     assert L.ddsp_ln_lrelu_backward(None, None, None, None, None, None, None, None, None, None, None, 0, 512, 0.01, None) == -1   # empty rows still need dgamma/dbeta
     assert L.ddsp_gru_set_fault_step(-1) == -2 and L.ddsp_gru_set_fault_step(0) == 0
-    # round-2 entry points: framing, one-kernel loss scale, column sums, reverb, counter-driven noise backward
+    # round-2 entry points: framing, one-kernel loss scale, column sums, reverb, noise backward
     assert L.ddsp_stft_frames(None, None, None, 1, 4096, 512, 128, None) == -1 and L.ddsp_stft_frames(None, None, None, 0, 4096, 512, 128, None) == 0
     assert L.ddsp_stft_frames_backward(None, None, None, 1, 4096, 512, 128, 0, None) == -1
     assert L.ddsp_mss_scale_supported(512) == 1 and L.ddsp_mss_scale_supported(96) == 0 and L.ddsp_mss_scale_supported(4096) == 0
@@ -68,7 +114,7 @@ def test_argument_validation_without_gpu():
     assert L.ddsp_mss_scale(None, None, None, None, None, None, 1, 4096, 512, 128, 1.0, 1e-7, None) == -1     # no output word
     assert L.ddsp_colsum(None, None, None, 8, 0, 0, None) == 0 and L.ddsp_colsum(None, None, None, 8, 4, 0, None) == -1
     assert L.ddsp_colsum_scratch_bytes(512) > 0 and L.ddsp_colsum_scratch_bytes(0) == 0
-    assert L.ddsp_noise_backward_counter(None, None, 1, 1, 65, 128, 0, None, None) == -1
+    assert L.ddsp_noise_backward_ws(None, None, None, 1, 1, 65, 128, 0, 0, None, None, 0, None) == -1
     assert L.ddsp_reverb_impulse(None, None, None, None, None, 16, 16, None) == -1
 
 
