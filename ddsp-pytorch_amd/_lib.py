@@ -98,6 +98,8 @@ SIGNATURES = {
     "ddsp_pitch_decode": (_i32, [_vp] * 8 + [_long, _vp]),
     "ddsp_loudness_supported": (_i32, [_i32]),
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
+    "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
+    "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

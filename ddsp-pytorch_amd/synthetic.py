@@ -1,8 +1,8 @@
 """Synthetic control signals for the DDSP synthesis hot path.
 
 These are the inputs SURVEY.md §8(d) / BASELINE.md §4 prescribe for the
-benchmark and for the golden fixtures: there is no dataset and no trained
-controller in this repository, so `f0`, `c`, `a`, `H` are drawn with the
+benchmark and for the golden fixtures: no recorded corpus (dataset.py builds one from a user's
+WAV files) and no trained controller ship with this repository, so `f0`, `c`, `a`, `H` are drawn with the
 value ranges the reference's controller produces
 (`model/autoencoder/decoder.py:110-116` modified_sigmoid: 2*sigmoid(z)^2.3026 + 1e-7,
  `model/autoencoder/encoder.py:39-48` CREPE pitch grid).

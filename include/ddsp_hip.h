@@ -388,6 +388,30 @@ int ddsp_pitch_decode(const float *logits, const float *bias, const float *f0_ta
 int ddsp_loudness_supported(int n_fft);
 int ddsp_loudness(const float *x, const double *a_weight, float *out, long B, long L, int n_fft, int hop, void *stream);
 
+/*
+ * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
+ *
+ * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
+ *                    torchaudio.load(normalize=True) scales it (format DDSP_PCM_S16: / 32768, DDSP_PCM_S32: / 2^31 -- a 24-bit
+ *                    file reaches the caller left-justified in int32 --, DDSP_PCM_F32: as is), then for C > 1 the mean over
+ *                    channels summed in channel order from 0 and divided by C (torch's CPU y.mean(dim=0), :30-37).  An unknown
+ *                    format is DDSP_EINVAL; C <= 65535.
+ * ddsp_make_examples the examples e0 .. e0 + E - 1 of several files' conf-rate mono audio, concatenated in y [y_len].  files
+ *                    [n_files, 4] int64 (device): start of the file in y, its length, its front hop-pad pad // 2
+ *                    (pad = length % hop, :46-47) and its first example's index; first is non-decreasing.  Example e of file f
+ *                    is the padded file's samples (e - first) * step .. + duration (unfold(0, duration, step), :50-59), zero
+ *                    outside [0, length).  Writes, either may be NULL but not both:
+ *                      enc_in [E, duration + p]  the example between (p / 2, p - p / 2) zeros, p = n_fft - hop (:86, 90)
+ *                      audio  [E, duration]      the bare example (the `audio` key, :95)
+ *                    duration <= INT_MAX.  No read leaves y, whatever the table holds.
+ */
+#define DDSP_PCM_S16 1
+#define DDSP_PCM_S32 2
+#define DDSP_PCM_F32 3
+int ddsp_pcm_to_mono(const void *pcm, float *y, long L, int C, int format, void *stream);
+int ddsp_make_examples(const float *y, long y_len, const long *files, int n_files, long e0, long E, long duration, long step, int p,
+                       float *enc_in, float *audio, void *stream);
+
 
 #ifdef __cplusplus
 }
