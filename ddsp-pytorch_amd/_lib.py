@@ -100,6 +100,9 @@ SIGNATURES = {
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
+    "ddsp_griffinlim_supported": (_i32, [_i32]),
+    "ddsp_griffinlim_workspace_bytes": (_size, [_long, _long, _i32, _i32]),
+    "ddsp_griffinlim": (_i32, [_vp] * 6 + [_size, _long, _long, _i32, _i32, _long, _i32, _f32, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -413,6 +413,28 @@ int ddsp_make_examples(const float *y, long y_len, const long *files, int n_file
                        float *enc_in, float *audio, void *stream);
 
 
+/*
+ * Griffin-Lim phase reconstruction (torchaudio 0.8.1 functional.griffinlim; style_transfer.py:149-156, helper.py:105-112).
+ *   mag    [B, F, T] fp32, F = n_fft / 2 + 1: the magnitude ALREADY raised to 1 / power
+ *   angles [B, F, T] complex64 (interleaved re, im) initial phases, or NULL: every angle 1 (rand_init=False)
+ *   window [n_fft]   the analysis / synthesis window zero-padded and centred to n_fft (torch.stft's padding of win_length)
+ *   env    [L]       the istft window envelope (sum of window^2 over the overlapping frames) at retained sample j, i.e. at
+ *                    n_fft/2 + j of the overlap-added signal; read for j < min(L, n_fft/2 + hop (T - 1)) only.  The caller checks
+ *                    it (NOLA) once.
+ *   y      [B, L]    out: the signal; also the iteration's signal in between (no other output buffer is needed)
+ * Each of the n_iter iterations is y = istft(mag * angles, center=True, length=L); R = stft(y, center=True, reflect, onesided);
+ * angles = R - c R_prev (skipped for c == 0; R_prev = 0 in the first iteration); angles /= sqrt(re^2 + im^2) + 1e-16.  Then one
+ * final istft.  c = fl32(momentum / (1 + momentum)) in [0, 1).  Constraints (DDSP_ERANGE otherwise): n_fft a power of two in
+ * [64, 2048] (ddsp_griffinlim_supported), 1 + L / hop == T, L > n_fft / 2 (reflect padding), B <= 65535.  The workspace
+ * (ddsp_griffinlim_workspace_bytes; with_angles: whether `angles` will be non-NULL) holds the frame-major magnitude, the
+ * initial angles, two rebuilt spectra and the synthesised frames; nothing is allocated inside.  All launches are enqueued
+ * on `stream` (three per iteration, no atomics: deterministic) and the call returns without synchronising.
+ */
+int ddsp_griffinlim_supported(int n_fft);
+size_t ddsp_griffinlim_workspace_bytes(long B, long T, int n_fft, int with_angles);
+int ddsp_griffinlim(const float *mag, const float *angles, const float *window, const float *env, float *y, void *workspace,
+                    size_t workspace_bytes, long B, long T, int n_fft, int hop, long L, int n_iter, float c, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
