@@ -7,6 +7,7 @@
 #include <initializer_list>
 
 #include "ddsp_hip.h"
+#include "ddsp_internal.h"
 
 namespace {
 
@@ -139,13 +140,6 @@ extern "C" int ddsp_heads_sigmoid_backward(const void *x, const float *g0, const
 // rows are D = 256 * NV wide (NV = 1..4).  HBM-bound: 8 B per element forward, 16 B backward.
 namespace {
 
-__device__ __forceinline__ float wave_sum64(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Element type of the activations (x, y and their gradients): fp32, or -- under torch.autocast, where the Linear in front
 // hands over bf16 / fp16 and the Linear behind wants it back -- the 16-bit type itself, so that no cast pass runs on either
 // side of the fused pass.  Statistics, gamma / beta and all arithmetic stay fp32.
@@ -198,14 +192,14 @@ __global__ void __launch_bounds__(256) ln_lrelu_fwd_kernel(const typename IO::T 
             v[j] = IO::ld(x + row * D, lane + 64 * j);
             s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
         }
-        const float mean = wave_sum64(s) * (1.0f / D);
+        const float mean = wave_sum(s) * (1.0f / D);
         float q = 0.0f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             v[j].x -= mean; v[j].y -= mean; v[j].z -= mean; v[j].w -= mean;
             q += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
         }
-        const float rstd = 1.0f / sqrtf(wave_sum64(q) * (1.0f / D) + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + eps);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o;
@@ -260,7 +254,7 @@ __global__ void __launch_bounds__(256) ln_lrelu_bwd_kernel(const typename IO::T 
             s1 += (d[j].x + d[j].y) + (d[j].z + d[j].w);
             s2 += (d[j].x * xh[j].x + d[j].y * xh[j].y) + (d[j].z * xh[j].z + d[j].w * xh[j].w);
         }
-        const float m1 = wave_sum64(s1) * (1.0f / D), m2 = wave_sum64(s2) * (1.0f / D);
+        const float m1 = wave_sum(s1) * (1.0f / D), m2 = wave_sum(s2) * (1.0f / D);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o;
@@ -344,14 +338,14 @@ __global__ void __launch_bounds__(256) outer_ln_lrelu_fwd_kernel(const float *__
             v[j] = make_float4(xr * wv[j].x + bv[j].x, xr * wv[j].y + bv[j].y, xr * wv[j].z + bv[j].z, xr * wv[j].w + bv[j].w);   // product, then sum: a K = 1 GEMM
             s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
         }
-        const float mean = wave_sum64(s) * (1.0f / D);
+        const float mean = wave_sum(s) * (1.0f / D);
         float q = 0.0f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             v[j].x -= mean; v[j].y -= mean; v[j].z -= mean; v[j].w -= mean;
             q += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
         }
-        const float rstd = 1.0f / sqrtf(wave_sum64(q) * (1.0f / D) + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + eps);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o;
@@ -408,7 +402,7 @@ __global__ void __launch_bounds__(256) outer_ln_lrelu_bwd_kernel(const typename 
             s1 += (d[j].x + d[j].y) + (d[j].z + d[j].w);
             s2 += (d[j].x * xh[j].x + d[j].y * xh[j].y) + (d[j].z * xh[j].z + d[j].w * xh[j].w);
         }
-        const float m1 = wave_sum64(s1) * (1.0f / D), m2 = wave_sum64(s2) * (1.0f / D);
+        const float m1 = wave_sum(s1) * (1.0f / D), m2 = wave_sum(s2) * (1.0f / D);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o;                                              // d (pre-activation): never stored

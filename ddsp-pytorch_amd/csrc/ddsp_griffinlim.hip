@@ -16,17 +16,20 @@
 // Transforms: ddsp_wave_fft.h.  n_fft = 64 .. 1024: two frames a, b packed as one complex sequence (a + i b); the inverse takes
 // Z[k] = A[k] + i B[k] over the Hermitian-extended spectra (imaginary parts of bins 0 and n_fft/2 dropped, as a c2r transform
 // does), the forward splits A = (Z[k] + conj Z[n-k]) / 2, B = -i (Z[k] - conj Z[n-k]) / 2.  n_fft = 2048: one real frame per
-// wavefront through a 1024-point complex transform, the packing of ddsp_mss_fft.hip's mss_wave2048_kernel.
+// wavefront through a 1024-point complex transform (ddsp_wave_fft.h's split2048 / pack2048).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "ddsp_hip.h"
+#include "ddsp_internal.h"
 #include "ddsp_wave_fft.h"
 
 namespace {
 
 using ddsp_wfft::cf;
+using ddsp_wfft::PairFft;
+using ddsp_wfft::PairUnit;
 
 constexpr int kMaxBlocks = 16384;   // grid-stride cap of the transform kernels (twiddle set-up is per block)
 
@@ -44,13 +47,6 @@ struct GlParams {
     int hop, F;
     float c;               // fl32(momentum / (1 + momentum))
 };
-
-__device__ __forceinline__ long reflect_index(long i, long L)
-{
-    if (i < 0) i = -i;
-    if (i >= L) i = 2 * (L - 1) - i;
-    return i;
-}
 
 // S * angles at element idx (torchaudio 0.8.1: angles = R - c R_prev; angles / (sqrt(re^2 + im^2) + 1e-16))
 __device__ __forceinline__ cf spec_at(const GlParams &p, long idx)
@@ -72,63 +68,6 @@ __device__ __forceinline__ cf spec_at(const GlParams &p, long idx)
 }
 
 // ---- n_fft = 64 .. 1024: frame pairs -----------------------------------------------------------------------------------------
-template <int N>
-struct PairUnit {
-    static constexpr int R1 = N / 64;                            // 1, 2, 4, 8, 16
-    static constexpr int PL = R1 < 8 ? 8 : R1;                   // points per lane
-    static constexpr int BT = PL / R1;                           // frame pairs per wavefront
-    static constexpr int STRIDE = N + (R1 < 8 ? 4 * R1 : 0);     // natural-order row of one pair's spectrum
-    static constexpr int EXCH = ddsp_wfft::buf_elems<(R1 < 8 ? 8 : R1)>();
-    static constexpr int BUF = BT * STRIDE > EXCH ? BT * STRIDE : EXCH;
-    static constexpr int BINS = N / 2 + 1;
-};
-
-// the lane's twiddles and the transforms of one unit (v[b R1 + n1] = z_b[64 n1 + lane] in, natural(i) out)
-template <int N>
-struct PairFft {
-    static constexpr int R1 = PairUnit<N>::R1, PL = PairUnit<N>::PL;
-    ddsp_wfft::Twiddles<(R1 < 8 ? 8 : R1)> tw;
-    cf t1s[R1 < 8 ? (R1 > 1 ? R1 : 1) : 1];
-    int lane;
-
-    __device__ __forceinline__ void init(int l)
-    {
-        lane = l;
-        if constexpr (R1 >= 8) {
-            ddsp_wfft::make_twiddles<R1>(tw, lane);
-        } else {
-#pragma unroll
-            for (int k2 = 0; k2 < 8; ++k2) {
-                float sn, cs;
-                sincospif(2.0f * (float)(((lane >> 3) * k2) & 63) / 64.0f, &sn, &cs);
-                tw.t2[0][k2] = make_float2(cs, -sn);
-            }
-#pragma unroll
-            for (int k1 = 0; k1 < (R1 > 1 ? R1 : 1); ++k1) {
-                float sn, cs;
-                sincospif(2.0f * (float)((lane * k1) & (N - 1)) / (float)N, &sn, &cs);
-                t1s[k1] = make_float2(cs, -sn);
-            }
-        }
-    }
-    template <bool INV>
-    __device__ __forceinline__ void run(cf (&v)[PL], cf *buf)
-    {
-        if constexpr (R1 == 16) ddsp_wfft::fft_wave<16, INV, false>(v, tw, buf, lane);
-        else if constexpr (R1 == 8) ddsp_wfft::fft_wave_batched<8, INV>(v, tw.t1, tw.t2[0], buf, lane);
-        else ddsp_wfft::fft_wave_batched<R1, INV>(v, t1s, tw.t2[0], buf, lane);
-    }
-    // result register i -> natural-order LDS address (pair's row * STRIDE + bin)
-    __device__ __forceinline__ int natural(int i) const
-    {
-        if constexpr (R1 == 16) return lane + 64 * (i >> 3) + 128 * (i & 7);
-        else {
-            const int sq = lane & 7, k2 = lane >> 3;
-            return (sq / R1) * PairUnit<N>::STRIDE + (sq % R1) + R1 * (k2 + 8 * i);
-        }
-    }
-};
-
 template <int N>
 __global__ void __launch_bounds__(64) gl_synth_pair_kernel(GlParams p, long nunits)
 {
@@ -242,29 +181,9 @@ __global__ void __launch_bounds__(64) gl_analysis_pair_kernel(GlParams p, long n
     }
 }
 
-// ---- n_fft = 2048: one real frame per wavefront through a 1024-point complex transform --------------------------------------
-// Forward: z[m] = x[2m] w[2m] + i x[2m+1] w[2m+1], Z = FFT_1024(z); Fe = (Z[k] + conj Z[M-k]) / 2, Fo = -i (Z[k] - conj Z[M-k]) / 2,
-//   T = W_2048^k Fo: X[k] = Fe + T, X[M-k] = conj(Fe - T).
-// Inverse (c2r): S = X[k] + conj X[M-k], D = X[k] - conj X[M-k]: Y[k] = S + i conj(W^k) D, Y[M-k] = conj(S) + i W^k conj(D), and
-//   IFFT_1024(Y)[m] = 2048 (x[2m] + i x[2m+1]).
+// ---- n_fft = 2048: one real frame per wavefront through a 1024-point complex transform (ddsp_wave_fft.h) -------------------
+// Forward: z[m] = x[2m] w[2m] + i x[2m+1] w[2m+1], Z = FFT_1024(z), split2048.  Inverse: pack2048, IFFT_1024.
 constexpr int kM = 1024;
-
-// W_2048^k for k = lane + 64 it: W_2048^lane * W_32^it (one product with an exact-to-the-ulp constant, as mss_wave2048_kernel)
-__device__ __forceinline__ cf twiddle2048(cf wbase, int it)
-{
-    constexpr float c32[9] = {1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
-                              0.55557023301960218f, 0.38268343236508977f, 0.19509032201612825f, 0.0f};
-    constexpr float s32[9] = {0.0f, 0.19509032201612825f, 0.38268343236508977f, 0.55557023301960218f, 0.70710678118654752f,
-                              0.83146961230254524f, 0.92387953251128674f, 0.98078528040323043f, 1.0f};
-    return make_float2(__fmaf_rn(wbase.x, c32[it], wbase.y * s32[it]), __fmaf_rn(wbase.y, c32[it], -(wbase.x * s32[it])));
-}
-
-__device__ __forceinline__ cf lane_w2048(int lane)
-{
-    float sn, cs;
-    sincospif(2.0f * (float)lane / 2048.0f, &sn, &cs);
-    return make_float2(cs, -sn);
-}
 
 __global__ void __launch_bounds__(64) gl_synth2048_kernel(GlParams p)
 {
@@ -276,7 +195,7 @@ __global__ void __launch_bounds__(64) gl_synth2048_kernel(GlParams p)
     const int lane = threadIdx.x;
     ddsp_wfft::Twiddles<R1> tw;
     ddsp_wfft::make_twiddles<R1>(tw, lane);
-    const cf wbase = lane_w2048(lane);
+    const cf wbase = ddsp_wfft::lane_w2048(lane);
     float2 wreg[R1];                                                        // window / N at the lane's sample pairs
 #pragma unroll
     for (int n1 = 0; n1 < R1; ++n1) {
@@ -290,16 +209,12 @@ __global__ void __launch_bounds__(64) gl_synth2048_kernel(GlParams p)
         for (int it = 0; it < 9; ++it) {
             const int k = lane + 64 * it;
             if (k <= kM / 2) {
-                const cf wk = twiddle2048(wbase, it);
                 cf X1 = spec_at(p, base + k), X2 = spec_at(p, base + kM - k);      // bins k and M - k (k = 0: bin 1024)
                 if (k == 0) { X1.y = 0.0f; X2.y = 0.0f; }                          // c2r: the DC and Nyquist bins are real
-                const cf S = make_float2(X1.x + X2.x, X1.y - X2.y), D = make_float2(X1.x - X2.x, X1.y + X2.y);
-                const cf cD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.x, D.y, -(wk.y * D.x)));   // conj(w) D
-                bufZ[k] = make_float2(S.x - cD.y, S.y + cD.x);
-                if (k != 0 && k != kM / 2) {
-                    const cf wD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.y, D.x, -(wk.x * D.y)));   // w conj(D)
-                    bufZ[kM - k] = make_float2(S.x - wD.y, -S.y + wD.x);
-                }
+                cf Y1, Y2;
+                ddsp_wfft::pack2048(X1, X2, ddsp_wfft::twiddle2048(wbase, it), Y1, Y2);
+                bufZ[k] = Y1;
+                if (k != 0 && k != kM / 2) bufZ[kM - k] = Y2;
             }
         }
         DDSP_WAVE_ORDER();
@@ -328,7 +243,7 @@ __global__ void __launch_bounds__(64) gl_analysis2048_kernel(GlParams p)
     const int lane = threadIdx.x;
     ddsp_wfft::Twiddles<R1> tw;
     ddsp_wfft::make_twiddles<R1>(tw, lane);
-    const cf wbase = lane_w2048(lane);
+    const cf wbase = ddsp_wfft::lane_w2048(lane);
     float2 wreg[R1];
 #pragma unroll
     for (int n1 = 0; n1 < R1; ++n1) wreg[n1] = reinterpret_cast<const float2 *>(p.window)[64 * n1 + lane];
@@ -357,13 +272,10 @@ __global__ void __launch_bounds__(64) gl_analysis2048_kernel(GlParams p)
         for (int it = 0; it < 9; ++it) {
             const int k = lane + 64 * it;
             if (k <= kM / 2) {
-                const cf wk = twiddle2048(wbase, it);
-                const int km = (kM - k) & (kM - 1);
-                const cf zk = bufZ[k], zm = bufZ[km];
-                const cf Fe = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)), Fo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                const cf T = make_float2(__fmaf_rn(wk.x, Fo.x, -(wk.y * Fo.y)), __fmaf_rn(wk.x, Fo.y, wk.y * Fo.x));
-                out[k] = make_float2(Fe.x + T.x, Fe.y + T.y);
-                if (k != kM / 2) out[kM - k] = make_float2(Fe.x - T.x, -(Fe.y - T.y));   // k = 0: the Nyquist bin 1024
+                cf X1, X2;
+                ddsp_wfft::split2048(bufZ[k], bufZ[(kM - k) & (kM - 1)], ddsp_wfft::twiddle2048(wbase, it), X1, X2);
+                out[k] = X1;
+                if (k != kM / 2) out[kM - k] = X2;                                 // k = 0: the Nyquist bin 1024
             }
         }
         DDSP_WAVE_ORDER();
@@ -411,8 +323,6 @@ __global__ void __launch_bounds__(256) gl_transpose_kernel(const V *__restrict__
         if (t < T && f < F) out[(b * T + t) * F + f] = tile[tx][r];
     }
 }
-
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct Layout {
     size_t S, A0, R0, R1, frames, total;
@@ -493,7 +403,7 @@ hipError_t run(GlParams p, const float *env, float *y, long B, long Lnat, int n_
 
 }  // namespace
 
-extern "C" int ddsp_griffinlim_supported(int n_fft) { return (n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0) ? 1 : 0; }
+extern "C" int ddsp_griffinlim_supported(int n_fft) { return ddsp_wfft::real_size_supported(n_fft) ? 1 : 0; }
 
 extern "C" size_t ddsp_griffinlim_workspace_bytes(long B, long T, int n_fft, int with_angles)
 {

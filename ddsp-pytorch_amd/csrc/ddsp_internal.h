@@ -1,4 +1,5 @@
-// Internal to libddsp_hip.so: optional per-kernel HIP-event timing (include/ddsp_hip.h: ddsp_profile_*).
+// Internal to libddsp_hip.so: optional per-kernel HIP-event timing (include/ddsp_hip.h: ddsp_profile_*) and the small helpers
+// that several sources share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,4 +25,28 @@ inline hipError_t ddsp_allow_big_lds(const void *fn, bool (&done)[64])
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) done[dev] = true;
     return e;
+}
+
+// scratch carving: offsets rounded up to 256 bytes
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// LDS operations of one wavefront execute in order: between a stage's stores and the next stage's loads only the
+// compiler has to be kept from reordering.
+#define DDSP_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
+
+// sum over the 64 lanes of a wavefront, every lane gets it: xor butterfly 32, 16, ..., 1 (a fixed order: deterministic bits)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// torch's 'reflect' padding (no repeated edge sample): -1 -> 1, L -> L - 2.  I: int or long, whichever the caller indexes in.
+template <typename I>
+__device__ __forceinline__ I reflect_index(I i, I L)
+{
+    if (i < 0) i = -i;
+    if (i >= L) i = 2 * (L - 1) - i;
+    return i;
 }

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "ddsp_hip.h"
+#include "ddsp_internal.h"
 #include "ddsp_wave_fft.h"
 
 namespace {
@@ -29,13 +30,6 @@ struct LoudParams {
     int hop;
 };
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // one bin's contribution, in the reference's operation order (encoder.py:148-151); |X| as a correctly rounded sqrt of |X|^2.
 // The fp32 spectrum plus the float64 weight is rounded to fp32 once, as torch's in-place `stft += a_weight` does.
 __device__ __forceinline__ float bin_term(float re, float im, double aw)
@@ -46,52 +40,16 @@ __device__ __forceinline__ float bin_term(float re, float im, double aw)
 }
 
 template <int N>
-struct PairUnit {
-    static constexpr int R1 = N / 64;                    // 1, 2, 4, 8, 16
-    static constexpr int PL = R1 < 8 ? 8 : R1;           // points per lane
-    static constexpr int BT = PL / R1;                   // frame pairs per unit
-    static constexpr int STRIDE = N + (R1 < 8 ? 4 * R1 : 0);
-    static constexpr int EXCH = ddsp_wfft::buf_elems<(R1 < 8 ? 8 : R1)>();
-    static constexpr int BUF = BT * STRIDE > EXCH ? BT * STRIDE : EXCH;
-    static constexpr int BINS = N / 2 + 1;
-};
-
-template <int N>
 __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nunits)
 {
-    using U = PairUnit<N>;
+    using U = ddsp_wfft::PairUnit<N>;
     using ddsp_wfft::cf;
     constexpr int R1 = U::R1, PL = U::PL, BT = U::BT, STRIDE = U::STRIDE, BINS = U::BINS;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     cf *buf = reinterpret_cast<cf *>(smem_f);
     const int lane = threadIdx.x;
-
-    ddsp_wfft::Twiddles<(R1 < 8 ? 8 : R1)> tw;
-    cf t1s[R1 < 8 ? (R1 > 1 ? R1 : 1) : 1];
-    if constexpr (R1 >= 8) {
-        ddsp_wfft::make_twiddles<R1>(tw, lane);
-    } else {
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) {
-            float sn, cs;
-            sincospif(2.0f * (float)(((lane >> 3) * k2) & 63) / 64.0f, &sn, &cs);
-            tw.t2[0][k2] = make_float2(cs, -sn);
-        }
-#pragma unroll
-        for (int k1 = 0; k1 < (R1 > 1 ? R1 : 1); ++k1) {
-            float sn, cs;
-            sincospif(2.0f * (float)((lane * k1) & (N - 1)) / (float)N, &sn, &cs);
-            t1s[k1] = make_float2(cs, -sn);
-        }
-    }
-    // result register i of this lane -> natural-order address (pair's row * STRIDE + bin)
-    auto natural = [&](int i) {
-        if constexpr (R1 == 16) return lane + 64 * (i >> 3) + 128 * (i & 7);
-        else {
-            const int sq = lane & 7, k2 = lane >> 3;
-            return (sq / R1) * STRIDE + (sq % R1) + R1 * (k2 + 8 * i);
-        }
-    };
+    ddsp_wfft::PairFft<N> fft;
+    fft.init(lane);
 
     for (long unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
         long frame[BT];
@@ -117,11 +75,9 @@ __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nu
                 v[b * R1 + n1] = make_float2(re, im);
             }
         }
-        if constexpr (R1 == 16) ddsp_wfft::fft_wave<16, false, false>(v, tw, buf, lane);
-        else if constexpr (R1 == 8) ddsp_wfft::fft_wave_batched<8, false>(v, tw.t1, tw.t2[0], buf, lane);
-        else ddsp_wfft::fft_wave_batched<R1, false>(v, t1s, tw.t2[0], buf, lane);
+        fft.template run<false>(v, buf);
 #pragma unroll
-        for (int i = 0; i < PL; ++i) buf[natural(i)] = v[i];
+        for (int i = 0; i < PL; ++i) buf[fft.natural(i)] = v[i];
         DDSP_WAVE_ORDER();
 #pragma unroll
         for (int b = 0; b < BT; ++b) {
@@ -144,28 +100,22 @@ __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nu
     }
 }
 
-// n_fft = 2048: Z = FFT_1024(x[2m] + i x[2m+1]);  Fe = (Z[k] + conj Z[M-k]) / 2,  Fo = -i (Z[k] - conj Z[M-k]) / 2,
-// T = W_2048^k Fo:  X[k] = Fe + T,  X[M-k] = conj(Fe - T)  (a lane owns bins k and M - k, k = 0 .. 512; k = 0 gives bins 0 and M)
+// n_fft = 2048: Z = FFT_1024(x[2m] + i x[2m+1]) and ddsp_wave_fft.h's real split (a lane owns bins k and M - k, k = 0 .. 512)
 __global__ void __launch_bounds__(64) loudness_2048_kernel(LoudParams p, long nunits)
 {
     using ddsp_wfft::cf;
-    constexpr int N = 2048, M = 1024, R1 = 16;
+    constexpr int M = 1024, R1 = 16;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     cf *buf = reinterpret_cast<cf *>(smem_f);
     const int lane = threadIdx.x;
     ddsp_wfft::Twiddles<R1> tw;
     ddsp_wfft::make_twiddles<R1>(tw, lane);
-    cf wbase;                                             // W_2048^lane
-    {
+    cf wbase;                                             // W_2048^lane: ddsp_wfft::lane_w2048 written out -- called, it costs
+    {                                                     // this kernel 20 more SGPRs (same values, another schedule)
         float sn, cs;
-        sincospif(2.0f * (float)lane / (float)N, &sn, &cs);
+        sincospif(2.0f * (float)lane / 2048.0f, &sn, &cs);
         wbase = make_float2(cs, -sn);
     }
-    // W_2048^(lane + 64 it) = W_2048^lane * W_32^it with exact-to-the-ulp constants (no running product)
-    constexpr float c32[9] = {1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
-                              0.55557023301960218f, 0.38268343236508977f, 0.19509032201612825f, 0.0f};
-    constexpr float s32[9] = {0.0f, 0.19509032201612825f, 0.38268343236508977f, 0.55557023301960218f, 0.70710678118654752f,
-                              0.83146961230254524f, 0.92387953251128674f, 0.98078528040323043f, 1.0f};
     for (long unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
         const long b = unit / p.F, fr = unit - b * p.F;
         const float *rs = p.x + b * p.L + fr * p.hop;
@@ -186,13 +136,12 @@ __global__ void __launch_bounds__(64) loudness_2048_kernel(LoudParams p, long nu
         for (int it = 0; it < 9; ++it) {
             const int k = lane + 64 * it;
             if (k <= M / 2) {
-                const cf wk = make_float2(__fmaf_rn(wbase.x, c32[it], wbase.y * s32[it]), __fmaf_rn(wbase.y, c32[it], -(wbase.x * s32[it])));
+                const cf wk = ddsp_wfft::twiddle2048(wbase, it);
                 const int km = (M - k) & (M - 1);
-                const cf zk = buf[k], zm = buf[km];
-                const cf Fe = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)), Fo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                const cf T = make_float2(__fmaf_rn(wk.x, Fo.x, -(wk.y * Fo.y)), __fmaf_rn(wk.x, Fo.y, wk.y * Fo.x));
-                s += bin_term(Fe.x + T.x, Fe.y + T.y, p.aw[k]);                         // bin k
-                if (k != M / 2) s += bin_term(Fe.x - T.x, -(Fe.y - T.y), p.aw[M - k]);   // bin M - k (k = 512 is its own partner)
+                cf X1, X2;
+                ddsp_wfft::split2048(buf[k], buf[km], wk, X1, X2);
+                s += bin_term(X1.x, X1.y, p.aw[k]);                         // bin k
+                if (k != M / 2) s += bin_term(X2.x, X2.y, p.aw[M - k]);     // bin M - k (k = 512 is its own partner)
             }
         }
         s = wave_sum(s);
@@ -204,7 +153,7 @@ __global__ void __launch_bounds__(64) loudness_2048_kernel(LoudParams p, long nu
 template <int N>
 hipError_t launch_pairs(const LoudParams &p, hipStream_t s)
 {
-    using U = PairUnit<N>;
+    using U = ddsp_wfft::PairUnit<N>;
     const long nunits = (p.npairs + U::BT - 1) / U::BT;
     const int blocks = (int)(nunits < kMaxBlocks ? nunits : kMaxBlocks);
     hipLaunchKernelGGL((loudness_pair_kernel<N>), dim3((unsigned)blocks), dim3(64), sizeof(float2) * U::BUF, s, p, nunits);
@@ -213,7 +162,7 @@ hipError_t launch_pairs(const LoudParams &p, hipStream_t s)
 
 }  // namespace
 
-extern "C" int ddsp_loudness_supported(int n_fft) { return (n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0) ? 1 : 0; }
+extern "C" int ddsp_loudness_supported(int n_fft) { return ddsp_wfft::real_size_supported(n_fft) ? 1 : 0; }
 
 extern "C" int ddsp_loudness(const float *x, const double *a_weight, float *out, long B, long L, int n_fft, int hop, void *stream)
 {

@@ -8,7 +8,7 @@
 #include <math.h>
 
 #include "ddsp_hip.h"
-#include "ddsp_osc_common.h"
+#include "ddsp_internal.h"
 
 namespace {
 
@@ -35,8 +35,8 @@ __global__ void __launch_bounds__(256) spectral_loss_kernel(const float2 *__rest
             grad[i] = make_float2(c * a.x, c * a.y);
         }
     }
-    lin = ddsp_osc::wave_sum(lin);
-    lg = ddsp_osc::wave_sum(lg);
+    lin = wave_sum(lin);
+    lg = wave_sum(lg);
     __shared__ float red[2][4];
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lin; red[1][threadIdx.x >> 6] = lg; }
     __syncthreads();

@@ -22,7 +22,7 @@
 #include <stdint.h>
 
 #include "ddsp_hip.h"
-#include "ddsp_osc_common.h"
+#include "ddsp_internal.h"
 #include "ddsp_wave_fft.h"
 
 namespace ddsp_mss {
@@ -53,28 +53,11 @@ __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcp
 
 __device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 
-__device__ __forceinline__ int reflect_index(int i, int L)
-{
-    if (i < 0) i = -i;
-    if (i >= L) i = 2 * (L - 1) - i;
-    return i;
-}
-
 // n_fft = 64 ... 1024: one wavefront owns a unit of PL = max(8, n_fft / 64) points per lane -- 512 / n_fft frame pairs for
-// n_fft <= 512, one pair for 1024; radix-R1 / 8 / 8 in registers with two padded LDS exchanges per transform;
-// frames are read straight into the transforms' input layout (reflect indexing, window in registers), the spectra are parked in
-// natural order in LDS only for the bin loop (a thread owns bins k and n - k), the gradient frames leave through LDS as whole
-// 256-byte runs.  Same arithmetic per pair whatever slot it lands in: rows stay independent, identical rows give P - Q = 0.
-template <int N>
-struct WaveUnit {
-    static constexpr int R1 = N / 64;                    // 1, 2, 4, 8, 16
-    static constexpr int PL = R1 < 8 ? 8 : R1;           // points per lane
-    static constexpr int BT = PL / R1;                   // frame pairs per unit
-    static constexpr int STRIDE = N + (R1 < 8 ? 4 * R1 : 0);   // natural-order row of one pair's spectrum (pad: conflict-free stores)
-    static constexpr int EXCH = ddsp_wfft::buf_elems<(R1 < 8 ? 8 : R1)>();
-    static constexpr int BUF = BT * STRIDE > EXCH ? BT * STRIDE : EXCH;
-    static constexpr int BINS = N / 2 + 1;
-};
+// n_fft <= 512, one pair for 1024 (ddsp_wave_fft.h's PairUnit); radix-R1 / 8 / 8 in registers with two padded LDS exchanges per
+// transform; frames are read straight into the transforms' input layout (reflect indexing, window in registers), the spectra are
+// parked in natural order in LDS only for the bin loop (a thread owns bins k and n - k), the gradient frames leave through LDS as
+// whole 256-byte runs.  Same arithmetic per pair whatever slot it lands in: rows stay independent, identical rows give P - Q = 0.
 
 // wavefronts per SIMD the register allocation aims at: up to 256 points four (128 VGPRs; left alone the compiler took 132 and 141
 // for 128 and 256 points -- three wavefronts -- which measured 38.5 / 39.2 us against 33.9 / 35.5 us with a handful of spilled
@@ -85,7 +68,7 @@ struct WaveUnit {
 template <int N>
 __global__ void __launch_bounds__(64, MSS_WAVES(N)) mss_wave_kernel(MssParams p, long nunits)
 {
-    using U = WaveUnit<N>;
+    using U = ddsp_wfft::PairUnit<N>;
     using ddsp_wfft::cf;
     constexpr int R1 = U::R1, PL = U::PL, BT = U::BT, STRIDE = U::STRIDE, BINS = U::BINS;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -95,46 +78,11 @@ __global__ void __launch_bounds__(64, MSS_WAVES(N)) mss_wave_kernel(MssParams p,
     const int L = (int)p.L;
 
     // twiddles and the window values of this lane's input points, for the whole kernel
-    ddsp_wfft::Twiddles<(R1 < 8 ? 8 : R1)> tw;           // R1 = 16: the 1024-point transform's; smaller: t2 only
-    cf t1s[R1 < 8 ? (R1 > 1 ? R1 : 1) : 1];
-    if constexpr (R1 >= 8) {
-        ddsp_wfft::make_twiddles<R1>(tw, lane);
-    } else {
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) {
-            float sn, cs;
-            sincospif(2.0f * (float)(((lane >> 3) * k2) & 63) / 64.0f, &sn, &cs);
-            tw.t2[0][k2] = make_float2(cs, -sn);
-        }
-#pragma unroll
-        for (int k1 = 0; k1 < (R1 > 1 ? R1 : 1); ++k1) {
-            float sn, cs;
-            sincospif(2.0f * (float)((lane * k1) & (N - 1)) / (float)N, &sn, &cs);
-            t1s[k1] = make_float2(cs, -sn);
-        }
-    }
+    ddsp_wfft::PairFft<N> fft;
+    fft.init(lane);
     float wreg[R1];
 #pragma unroll
     for (int n1 = 0; n1 < R1; ++n1) wreg[n1] = p.window[64 * n1 + lane];
-
-    auto forward = [&](cf (&v)[PL], cf *buf) {
-        if constexpr (R1 == 16) ddsp_wfft::fft_wave<16, false, false>(v, tw, buf, lane);
-        else if constexpr (R1 == 8) ddsp_wfft::fft_wave_batched<8, false>(v, tw.t1, tw.t2[0], buf, lane);
-        else ddsp_wfft::fft_wave_batched<R1, false>(v, t1s, tw.t2[0], buf, lane);
-    };
-    auto inverse = [&](cf (&v)[PL], cf *buf) {
-        if constexpr (R1 == 16) ddsp_wfft::fft_wave<16, true, false>(v, tw, buf, lane);
-        else if constexpr (R1 == 8) ddsp_wfft::fft_wave_batched<8, true>(v, tw.t1, tw.t2[0], buf, lane);
-        else ddsp_wfft::fft_wave_batched<R1, true>(v, t1s, tw.t2[0], buf, lane);
-    };
-    // result register i of this lane -> natural-order address (pair's row * STRIDE + bin)
-    auto natural = [&](int i) {
-        if constexpr (R1 == 16) return lane + 64 * (i >> 3) + 128 * (i & 7);          // v[d * 8 + k3] = X[lane + 64 d + 128 k3]
-        else {
-            const int sq = lane & 7, k2 = lane >> 3;                                   // v[k3] = X_b[k1 + R1 (k2 + 8 k3)], s = b R1 + k1
-            return (sq / R1) * STRIDE + (sq % R1) + R1 * (k2 + 8 * i);
-        }
-    };
 
     // where a unit's pairs live: lane b computes pair b (the 64-bit divisions happen once), the others read it from there
     struct Slots { long row[BT], frame[BT]; int start[BT], nvalid[BT]; };
@@ -212,14 +160,14 @@ __global__ void __launch_bounds__(64, MSS_WAVES(N)) mss_wave_kernel(MssParams p,
         cf v[PL];
 #pragma unroll
         for (int i = 0; i < PL; ++i) v[i] = make_float2(pp.v[i].x * wreg[i % R1], pp.v[i].y * wreg[i % R1]);
-        forward(v, bufZ);
+        fft.template run<false>(v, bufZ);
 #pragma unroll
-        for (int i = 0; i < PL; ++i) bufZ[natural(i)] = v[i];
+        for (int i = 0; i < PL; ++i) bufZ[fft.natural(i)] = v[i];
 #pragma unroll
         for (int i = 0; i < PL; ++i) v[i] = make_float2(pq.v[i].x * wreg[i % R1], pq.v[i].y * wreg[i % R1]);
-        forward(v, bufW);
+        fft.template run<false>(v, bufW);
 #pragma unroll
-        for (int i = 0; i < PL; ++i) bufW[natural(i)] = v[i];
+        for (int i = 0; i < PL; ++i) bufW[fft.natural(i)] = v[i];
         DDSP_WAVE_ORDER();
 
         // split, loss terms, gradient spectrum (in place in bufZ: a lane owns bins k and N - k of its pair)
@@ -262,9 +210,9 @@ __global__ void __launch_bounds__(64, MSS_WAVES(N)) mss_wave_kernel(MssParams p,
 #pragma unroll
                 for (int n1 = 0; n1 < R1; ++n1) v[b * R1 + n1] = bufZ[b * STRIDE + 64 * n1 + lane];
             DDSP_WAVE_ORDER();
-            inverse(v, bufW);
+            fft.template run<true>(v, bufW);
 #pragma unroll
-            for (int i = 0; i < PL; ++i) bufW[natural(i)] = v[i];
+            for (int i = 0; i < PL; ++i) bufW[fft.natural(i)] = v[i];
             DDSP_WAVE_ORDER();
 #pragma unroll
             for (int b = 0; b < BT; ++b) {
@@ -286,21 +234,19 @@ __global__ void __launch_bounds__(64, MSS_WAVES(N)) mss_wave_kernel(MssParams p,
         if (AHEAD) { sl = sn; pp = np; pq = nq; }
         else sl = get_slots(unit);
     }
-    lin = ddsp_osc::wave_sum(lin);
-    lg = ddsp_osc::wave_sum(lg);
+    lin = wave_sum(lin);
+    lg = wave_sum(lg);
     if (lane == 0) {
         p.partials[2 * blockIdx.x] = lin;
         p.partials[2 * blockIdx.x + 1] = lg;
     }
 }
 
-// n_fft = 2048: one REAL frame per wavefront through a 1024-point complex transform (2048 complex points of a frame pair
-// exceed a wavefront's registers): z[m] = x[2m] w[2m] + i x[2m+1] w[2m+1], Z = FFT_1024(z),
-//   Fe = (Z[k] + conj Z[M-k]) / 2,  Fo = -i (Z[k] - conj Z[M-k]) / 2,  T = W_2048^k Fo:   X[k] = Fe + T,  X[M-k] = conj(Fe - T)
-// (a lane owns the bins k and M - k, k = 0 .. 512; k = 0 yields the real bins 0 and M = 1024).  Gradient: with the one-sided
-// G'[k] = h c_k X[k] (h = 1/2 inside, 1 at bins 0 and M: the adjoint of an unnormalised rfft) the frame's gradient is the
-// complex-to-real transform g[2m] + i g[2m+1] = IFFT_1024(Y)[m],
-//   S = G'[k] + conj G'[M-k],  D = G'[k] - conj G'[M-k]:   Y[k] = S + i conj(W^k) D,   Y[M-k] = conj(S) + i W^k conj(D).
+// n_fft = 2048: one REAL frame per wavefront through a 1024-point complex transform (ddsp_wave_fft.h): z[m] = x[2m] w[2m] +
+// i x[2m+1] w[2m+1], Z = FFT_1024(z), split2048 into X[k], X[M-k] (a lane owns the bins k and M - k, k = 0 .. 512; k = 0 yields
+// the real bins 0 and M = 1024).  Gradient: with the one-sided G'[k] = h c_k X[k] (h = 1/2 inside, 1 at bins 0 and M: the
+// adjoint of an unnormalised rfft) the frame's gradient is the complex-to-real transform g[2m] + i g[2m+1] = IFFT_1024(Y)[m] of
+// Y = pack2048(G'[k], G'[M-k]).
 __global__ void __launch_bounds__(64) mss_wave2048_kernel(MssParams p, long nunits)
 {
     using ddsp_wfft::cf;
@@ -313,12 +259,7 @@ __global__ void __launch_bounds__(64) mss_wave2048_kernel(MssParams p, long nuni
     const int L = (int)p.L;
     ddsp_wfft::Twiddles<R1> tw;
     ddsp_wfft::make_twiddles<R1>(tw, lane);
-    cf wbase;                                             // W_2048^lane
-    {
-        float sn, cs;
-        sincospif(2.0f * (float)lane / (float)N, &sn, &cs);
-        wbase = make_float2(cs, -sn);
-    }
+    const cf wbase = ddsp_wfft::lane_w2048(lane);
     float2 wreg[R1];                                      // window at the lane's sample pairs
 #pragma unroll
     for (int n1 = 0; n1 < R1; ++n1) wreg[n1] = reinterpret_cast<const float2 *>(p.window)[64 * n1 + lane];
@@ -353,26 +294,15 @@ __global__ void __launch_bounds__(64) mss_wave2048_kernel(MssParams p, long nuni
         ddsp_wfft::store_natural<R1>(v, bufW, lane);
         DDSP_WAVE_ORDER();
 
-        // W_2048^k, k = lane + 64 it, = W_2048^lane * W_32^it: one product with an exact-to-the-ulp constant per trip (advancing a
-        // running twiddle by W_32 eight times costs 5e-7 of relative accuracy, which near-empty bins amplify a thousandfold)
-        constexpr float c32[9] = {1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
-                                  0.55557023301960218f, 0.38268343236508977f, 0.19509032201612825f, 0.0f};
-        constexpr float s32[9] = {0.0f, 0.19509032201612825f, 0.38268343236508977f, 0.55557023301960218f, 0.70710678118654752f,
-                                  0.83146961230254524f, 0.92387953251128674f, 0.98078528040323043f, 1.0f};
 #pragma unroll 1
         for (int it = 0; it < 9; ++it) {
             const int k = lane + 64 * it;
-            // (wx + i wy)(c - i s)
-            const cf wk = make_float2(__fmaf_rn(wbase.x, c32[it], wbase.y * s32[it]), __fmaf_rn(wbase.y, c32[it], -(wbase.x * s32[it])));
+            const cf wk = ddsp_wfft::twiddle2048(wbase, it);
             if (k <= M / 2) {
                 const int km = (M - k) & (M - 1);
-                const cf zk = bufZ[k], zm = bufZ[km], qk = bufW[k], qm = bufW[km];
-                const cf Fe = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)), Fo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                const cf Ge = make_float2(0.5f * (qk.x + qm.x), 0.5f * (qk.y - qm.y)), Go = make_float2(0.5f * (qk.y + qm.y), -0.5f * (qk.x - qm.x));
-                const cf T = make_float2(__fmaf_rn(wk.x, Fo.x, -(wk.y * Fo.y)), __fmaf_rn(wk.x, Fo.y, wk.y * Fo.x));
-                const cf Tq = make_float2(__fmaf_rn(wk.x, Go.x, -(wk.y * Go.y)), __fmaf_rn(wk.x, Go.y, wk.y * Go.x));
-                const cf X1 = make_float2(Fe.x + T.x, Fe.y + T.y), X2 = make_float2(Fe.x - T.x, -(Fe.y - T.y));      // bins k, M - k
-                const cf Q1 = make_float2(Ge.x + Tq.x, Ge.y + Tq.y), Q2 = make_float2(Ge.x - Tq.x, -(Ge.y - Tq.y));
+                cf X1, X2, Q1, Q2;                                                                      // bins k, M - k
+                ddsp_wfft::split2048(bufZ[k], bufZ[km], wk, X1, X2);
+                ddsp_wfft::split2048(bufW[k], bufW[km], wk, Q1, Q2);
                 const bool twice = k != M / 2;            // k = 512 is its own partner: one bin
                 const float P1 = __fmaf_rn(X1.x, X1.x, X1.y * X1.y), P2 = __fmaf_rn(X2.x, X2.x, X2.y * X2.y);
                 const float R1q = __fmaf_rn(Q1.x, Q1.x, Q1.y * Q1.y), R2q = __fmaf_rn(Q2.x, Q2.x, Q2.y * Q2.y);
@@ -386,15 +316,10 @@ __global__ void __launch_bounds__(64) mss_wave2048_kernel(MssParams p, long nuni
                     const float c1 = h * 2.0f * p.inv_n * (sgn(d1) - p.alpha * sgn(e1) * inv_ln2 * fast_rcp(P1 + p.eps));
                     const float c2 = h * 2.0f * p.inv_n * (sgn(d2) - p.alpha * sgn(e2) * inv_ln2 * fast_rcp(P2 + p.eps));
                     const cf G1 = make_float2(c1 * X1.x, c1 * X1.y), G2 = make_float2(c2 * X2.x, c2 * X2.y);         // G'[k], G'[M - k]
-                    const cf S = make_float2(G1.x + G2.x, G1.y - G2.y), D = make_float2(G1.x - G2.x, G1.y + G2.y);
-                    // i conj(w) D = i (wx + i*(-wy))... with w = (wx, wy): conj(w) D = (wx Dx + wy Dy, wx Dy - wy Dx)
-                    const cf cD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.x, D.y, -(wk.y * D.x)));
-                    bufZ[k] = make_float2(S.x - cD.y, S.y + cD.x);                                                   // S + i conj(w) D
-                    if (k != 0 && twice) {
-                        // w conj(D) = (wx Dx + wy Dy, wy Dx - wx Dy)
-                        const cf wD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.y, D.x, -(wk.x * D.y)));
-                        bufZ[km] = make_float2(S.x - wD.y, -S.y + wD.x);                                             // conj(S) + i w conj(D)
-                    }
+                    cf Y1, Y2;
+                    ddsp_wfft::pack2048(G1, G2, wk, Y1, Y2);
+                    bufZ[k] = Y1;
+                    if (k != 0 && twice) bufZ[km] = Y2;
                 }
             }
         }
@@ -412,8 +337,8 @@ __global__ void __launch_bounds__(64) mss_wave2048_kernel(MssParams p, long nuni
             DDSP_WAVE_ORDER();
         }
     }
-    lin = ddsp_osc::wave_sum(lin);
-    lg = ddsp_osc::wave_sum(lg);
+    lin = wave_sum(lin);
+    lg = wave_sum(lg);
     if (lane == 0) {
         p.partials[2 * blockIdx.x] = lin;
         p.partials[2 * blockIdx.x + 1] = lg;
@@ -434,7 +359,7 @@ hipError_t launch_wave2048(const MssParams &p0, hipStream_t s, int *blocks_out)
 template <int N>
 hipError_t launch_wave(const MssParams &p0, hipStream_t s, int *blocks_out)
 {
-    using U = WaveUnit<N>;
+    using U = ddsp_wfft::PairUnit<N>;
     const size_t lds = sizeof(float2) * 2 * U::BUF;
     MssParams p = p0;
     const long nunits = (p.npairs + U::BT - 1) / U::BT;
@@ -448,7 +373,7 @@ hipError_t launch_wave(const MssParams &p0, hipStream_t s, int *blocks_out)
 
 extern "C" size_t ddsp_mss_scale_scratch_bytes(void) { return sizeof(float) * 2 * kMaxBlocks; }
 
-extern "C" int ddsp_mss_scale_supported(int n_fft) { return (n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0) ? 1 : 0; }
+extern "C" int ddsp_mss_scale_supported(int n_fft) { return ddsp_wfft::real_size_supported(n_fft) ? 1 : 0; }
 
 extern "C" int ddsp_mss_scale(const float *x_pred, const float *x_true, const float *window, float *grad_frames, void *scratch, float *out3,
                               long B, long L, int n_fft, int hop, float alpha, float eps, void *stream)

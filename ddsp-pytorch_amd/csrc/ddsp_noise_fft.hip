@@ -18,12 +18,7 @@
 //         P[g] = [(A + B)(E + F) - i (A - B)(E - F)] / 4,  A = Cx[g], B = conj Cx[N-g], E = Ck[g], F = conj Ck[N-g]
 //      = X_a K_a + i X_b K_b, then ONE N-point inverse FFT gives y_a + i y_b; the first R samples are kept (:31)
 //   5. coalesced float4 stores (read-modify-write when accumulating into the oscillator's output, decoder.py:132)
-//
-// FFT of N = 64 * R1 points on one wavefront: n = 64 n1 + 8 n2 + n3, k = k1 + R1 k2 + 8 R1 k3;
-//   radix-R1 over n1 in registers (lane = 8 n2 + n3) -> twiddle W_N^(lane k1) -> LDS exchange -> radix-8 over n2
-//   (lane = k1 + R1 n3') -> twiddle W_64^(n3 k2) -> LDS exchange -> radix-8 over n3 (lane = k1 + R1 k2).
-// Twiddles live in registers (computed once per wavefront with sincospi); the exchange addresses are linear (lane base +
-// immediate offsets) and padded against bank conflicts.
+// The transforms are ddsp_wave_fft.h's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>

@@ -88,8 +88,6 @@ constexpr int kLdsFloats = FG * KS + FG * XS;
 #define DDSP_STAMP(i) do { } while (0)
 #endif
 
-#define DDSP_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
-
 template <bool ACC>   // ACC: add to the output buffer's contents (harmonics + noise, decoder.py:132) instead of overwriting them
 __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long ngroups)
 {

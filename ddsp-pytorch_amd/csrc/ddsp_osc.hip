@@ -59,9 +59,8 @@ __device__ __forceinline__ void walk_fast(const OscParams &p, FrameState<K> &st,
     // (tools/microbench/valu_rates.hip: "chain staged" vs "osc chain").
 #define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
     // LDS operations of one wavefront execute in order, so the staging buffer needs no s_waitcnt between lane 0's
-    // writes and the group's reads -- only the compiler must not reorder them.  (A wavefront-scope fence here also
-    // waits for the global stores of the previous flush: measured 2x slowdown of the short walks.)
-#define DDSP_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
+    // writes and the group's reads -- only the compiler must not reorder them (DDSP_WAVE_ORDER).  (A wavefront-scope fence
+    // here also waits for the global stores of the previous flush: measured 2x slowdown of the short walks.)
     // QKEEP: full-width synthesis walks (one sample per iteration) compute the modulo's quotient on every other sample only
     constexpr bool QKEEP = QREUSE && (MODE == MODE_SYNTH) && POW2 && NS == 1;
     float qk[QKEEP ? KL : 1];
@@ -215,7 +214,6 @@ __device__ __forceinline__ void walk_fast(const OscParams &p, FrameState<K> &st,
     // (one copy of the body, the choice is a scalar branch: two unrolled copies cost 30 more VGPRs and a wavefront per SIMD)
     for (int n = n_beg; n < n_end; n += NS) one_step(n, !QKEEP || ((n - n_beg) & 1) == 0);
 #undef DDSP_STAGE_END
-#undef DDSP_WAVE_ORDER
 }
 
 // Reference-exact walk: libm fmodf modulo, live offsets (:70), live state and debug phase outputs.

@@ -48,7 +48,6 @@ constexpr int kRow = 256 + 4;          // staging row: one float per thread of t
 constexpr float kReuseMaxInc = 4.8f;   // quotient reuse: r = P - q*2pi32 stays exact while |r| < 8, i.e. increments < 8 - pi
 
 #define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
-#define DDSP_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
 
 // F.interpolate weights inside a segment (App. A item 4 for a power-of-two hop): sample n has w1 = (2n+1)/(2 hop), exact, and
 // advances by exactly 1/hop per sample; segment 0 has its source index clamped to 0: w1 = 0 throughout.  (Built by the

@@ -93,13 +93,6 @@ __device__ __forceinline__ float group_sum(float v, int logG)
     return v;
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // torch CPU `%=` on floats (aten remainder): fmod, then shifted into the divisor's sign.
 __device__ __forceinline__ float remainder_two_pi(float p)
 {
@@ -180,7 +173,6 @@ __device__ __forceinline__ void load_synth_segment(const OscParams &p, FrameStat
 // ---- host side (defined in ddsp_osc.hip) ---------------------------------------------------------------
 struct Tiling { int K, logG; };
 bool pick_tiling(int H, long frames, Tiling *out);
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 // scratch layout: w | amp | loc | sup | flag; sup is sized for the smallest superblock (G = 64: 4 frames)
 inline size_t sup_elems(int B, int T, int H) { return (size_t)B * ((size_t)(T + 3) / 4) * H; }
 // Fills the shape-derived fields and carves the scratch buffer; returns false if no tiling exists for H.

@@ -12,16 +12,9 @@
 #include <stdint.h>
 
 #include "ddsp_hip.h"
+#include "ddsp_internal.h"
 
 namespace {
-
-// torch's 'reflect' padding (no repeated edge sample): -1 -> 1, N -> N - 2
-__device__ __forceinline__ long reflect_index(long p, long N)
-{
-    if (p < 0) p = -p;
-    if (p >= N) p = 2 * (N - 1) - p;
-    return p;
-}
 
 __global__ void __launch_bounds__(256) stft_frames_kernel(const float *__restrict__ x, const float *__restrict__ window,
                                                           float *__restrict__ frames, long B, long N, int n_fft, int hop, long F)

@@ -1,6 +1,7 @@
-// Wavefront-private complex FFTs in registers + LDS exchanges (gfx950), shared by the filtered-noise FFT form
-// (ddsp_noise_fft.hip) and the spectral-loss scales (ddsp_mss_fft.hip).  One wavefront owns its transforms and shares nothing
-// with other wavefronts: LDS operations of one wavefront execute in order, so the stage hand-offs need no barrier.
+// Wavefront-private complex FFTs in registers + LDS exchanges (gfx950), and the real-signal pieces around them, shared by the
+// filtered-noise FFT form (ddsp_noise_fft.hip), the spectral-loss scales (ddsp_mss_fft.hip), the encoder's loudness
+// (ddsp_loudness.hip) and Griffin-Lim (ddsp_griffinlim.hip).  One wavefront owns its transforms and shares nothing with other
+// wavefronts: LDS operations of one wavefront execute in order, so the stage hand-offs need no barrier (DDSP_WAVE_ORDER).
 //
 // FFT of N = 64 * R1 points on one wavefront: n = 64 n1 + 8 n2 + n3, k = k1 + R1 k2 + 8 R1 k3;
 //   radix-R1 over n1 in registers (lane = 8 n2 + n3) -> twiddle W_N^(lane k1) -> LDS exchange -> radix-8 over n2
@@ -9,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "ddsp_internal.h"
 
 namespace ddsp_wfft {
 
@@ -103,10 +106,6 @@ __device__ __forceinline__ void dft_r1(cf (&v)[R1])
         }
     }
 }
-
-// LDS operations of one wavefront execute in order: between a stage's stores and the next stage's loads only the
-// compiler has to be kept from reordering.
-#define DDSP_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
 
 // Per-wavefront twiddles of the 64*R1-point transform (forward values; the inverse conjugates on the fly).
 template <int R1>
@@ -275,6 +274,116 @@ __device__ __forceinline__ void fft_wave_batched(cf (&v)[8], const cf *t1, const
 #pragma unroll
     for (int k3 = 0; k3 < 8; ++k3) v[k3] = u[k3];
     DDSP_WAVE_ORDER();
+}
+
+
+// ---- real signals: n_fft a power of two in 64 .. 2048 -----------------------------------------------------------------------
+constexpr bool real_size_supported(int n_fft) { return n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0; }
+
+// n_fft = 64 ... 1024: two real frames a, b packed as one complex sequence a + i b.  One wavefront owns a unit of PL points per
+// lane -- BT = 512 / n_fft frame pairs for n_fft <= 512, one pair for 1024 -- in the layout v[b R1 + n1] = z_b[64 n1 + lane];
+// the spectra are parked in natural order in LDS, one row of STRIDE per pair.
+template <int N>
+struct PairUnit {
+    static constexpr int R1 = N / 64;                            // 1, 2, 4, 8, 16
+    static constexpr int PL = R1 < 8 ? 8 : R1;                   // points per lane
+    static constexpr int BT = PL / R1;                           // frame pairs per unit
+    static constexpr int STRIDE = N + (R1 < 8 ? 4 * R1 : 0);     // natural-order row of one pair's spectrum (pad: conflict-free stores)
+    static constexpr int EXCH = buf_elems<(R1 < 8 ? 8 : R1)>();
+    static constexpr int BUF = BT * STRIDE > EXCH ? BT * STRIDE : EXCH;
+    static constexpr int BINS = N / 2 + 1;
+};
+
+// the lane's twiddles and the transforms of one unit (v[b R1 + n1] = z_b[64 n1 + lane] in, natural(i) out): fft_wave for 1024
+// points, fft_wave_batched below
+template <int N>
+struct PairFft {
+    static constexpr int R1 = PairUnit<N>::R1, PL = PairUnit<N>::PL;
+    Twiddles<(R1 < 8 ? 8 : R1)> tw;                             // R1 = 16: the 1024-point transform's; smaller: t2 only
+    cf t1s[R1 < 8 ? (R1 > 1 ? R1 : 1) : 1];
+    int lane;
+
+    __device__ __forceinline__ void init(int l)
+    {
+        lane = l;
+        if constexpr (R1 >= 8) {
+            make_twiddles<R1>(tw, lane);
+        } else {
+#pragma unroll
+            for (int k2 = 0; k2 < 8; ++k2) {
+                float sn, cs;
+                sincospif(2.0f * (float)(((lane >> 3) * k2) & 63) / 64.0f, &sn, &cs);
+                tw.t2[0][k2] = make_float2(cs, -sn);
+            }
+#pragma unroll
+            for (int k1 = 0; k1 < (R1 > 1 ? R1 : 1); ++k1) {
+                float sn, cs;
+                sincospif(2.0f * (float)((lane * k1) & (N - 1)) / (float)N, &sn, &cs);
+                t1s[k1] = make_float2(cs, -sn);
+            }
+        }
+    }
+    template <bool INV>
+    __device__ __forceinline__ void run(cf (&v)[PL], cf *buf)
+    {
+        if constexpr (R1 == 16) fft_wave<16, INV, false>(v, tw, buf, lane);
+        else if constexpr (R1 == 8) fft_wave_batched<8, INV>(v, tw.t1, tw.t2[0], buf, lane);
+        else fft_wave_batched<R1, INV>(v, t1s, tw.t2[0], buf, lane);
+    }
+    // result register i -> natural-order LDS address (pair's row * STRIDE + bin)
+    __device__ __forceinline__ int natural(int i) const
+    {
+        if constexpr (R1 == 16) return lane + 64 * (i >> 3) + 128 * (i & 7);           // v[d * 8 + k3] = X[lane + 64 d + 128 k3]
+        else {
+            const int sq = lane & 7, k2 = lane >> 3;                                    // v[k3] = X_b[k1 + R1 (k2 + 8 k3)], s = b R1 + k1
+            return (sq / R1) * PairUnit<N>::STRIDE + (sq % R1) + R1 * (k2 + 8 * i);
+        }
+    }
+};
+
+// n_fft = 2048: one REAL frame per wavefront through a 1024-point complex transform (the 2048 complex points of a frame pair
+// exceed a wavefront's registers).  M = 1024; a lane owns the bins k and M - k, k = lane + 64 it <= 512 (k = 0: bins 0 and M).
+// Forward: z[m] = x[2m] + i x[2m+1], Z = FFT_1024(z):  split2048.   Inverse (c2r): pack2048, then IFFT_1024(Y)[m] = 2048 (x[2m] + i x[2m+1]).
+
+// W_2048^lane
+__device__ __forceinline__ cf lane_w2048(int lane)
+{
+    float sn, cs;
+    sincospif(2.0f * (float)lane / 2048.0f, &sn, &cs);
+    return make_float2(cs, -sn);
+}
+
+// W_2048^k for k = lane + 64 it, = W_2048^lane * W_32^it: one product with an exact-to-the-ulp constant per trip (advancing a
+// running twiddle by W_32 eight times costs 5e-7 of relative accuracy, which near-empty bins amplify a thousandfold)
+__device__ __forceinline__ cf twiddle2048(cf wbase, int it)
+{
+    constexpr float c32[9] = {1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
+                              0.55557023301960218f, 0.38268343236508977f, 0.19509032201612825f, 0.0f};
+    constexpr float s32[9] = {0.0f, 0.19509032201612825f, 0.38268343236508977f, 0.55557023301960218f, 0.70710678118654752f,
+                              0.83146961230254524f, 0.92387953251128674f, 0.98078528040323043f, 1.0f};
+    // (wx + i wy)(c - i s)
+    return make_float2(__fmaf_rn(wbase.x, c32[it], wbase.y * s32[it]), __fmaf_rn(wbase.y, c32[it], -(wbase.x * s32[it])));
+}
+
+// real-to-complex split, (Z[k], Z[M-k], W^k) -> (X[k], X[M-k]):
+//   Fe = (Z[k] + conj Z[M-k]) / 2,  Fo = -i (Z[k] - conj Z[M-k]) / 2,  T = W^k Fo:   X[k] = Fe + T,  X[M-k] = conj(Fe - T)
+__device__ __forceinline__ void split2048(cf zk, cf zm, cf wk, cf &xk, cf &xm)
+{
+    const cf Fe = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)), Fo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    const cf T = make_float2(__fmaf_rn(wk.x, Fo.x, -(wk.y * Fo.y)), __fmaf_rn(wk.x, Fo.y, wk.y * Fo.x));
+    xk = make_float2(Fe.x + T.x, Fe.y + T.y);
+    xm = make_float2(Fe.x - T.x, -(Fe.y - T.y));
+}
+
+// complex-to-real packing, (X[k], X[M-k], W^k) -> (Y[k], Y[M-k]):
+//   S = X[k] + conj X[M-k],  D = X[k] - conj X[M-k]:   Y[k] = S + i conj(W^k) D,   Y[M-k] = conj(S) + i W^k conj(D)
+__device__ __forceinline__ void pack2048(cf xk, cf xm, cf wk, cf &yk, cf &ym)
+{
+    const cf S = make_float2(xk.x + xm.x, xk.y - xm.y), D = make_float2(xk.x - xm.x, xk.y + xm.y);
+    const cf cD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.x, D.y, -(wk.y * D.x)));   // conj(w) D
+    yk = make_float2(S.x - cD.y, S.y + cD.x);
+    const cf wD = make_float2(__fmaf_rn(wk.x, D.x, wk.y * D.y), __fmaf_rn(wk.y, D.x, -(wk.x * D.y)));   // w conj(D)
+    ym = make_float2(S.x - wD.y, -S.y + wD.x);
 }
 
 }  // namespace ddsp_wfft
