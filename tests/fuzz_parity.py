@@ -6,8 +6,9 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked]   (`training`: the loss-side kernels against fp64 torch instead;
-`chunked`: the chunked oscillator form with forced tilings and chunk lengths)"""
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward]   (`training`: the loss-side kernels against fp64 torch instead;
+`chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's backward against the
+fp64 reference of tests/osc_grad_reference.py)"""
 import os
 import sys
 
@@ -20,6 +21,8 @@ sys.path.insert(0, ROOT)
 import ddsp_pytorch_amd as ddsp  # noqa: E402
 from ddsp_pytorch_amd import synthetic as syn  # noqa: E402
 from oracle import oracle  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import osc_grad_reference as R  # noqa: E402
 
 
 def bits(a):
@@ -165,6 +168,145 @@ def sweep_chunked(cases: int, seed: int, verbose: bool = True):
     return bad, worst
 
 
+# ---- the oscillator's backward (csrc/ddsp_osc_bwd.hip) against the fp64 reference -------------------------------------------
+# Elementwise |grad - fp64| <= OSC_BWD_TOL x the frame's local yardstick (Yc for grad_c, Ya for grad_a: osc_grad_reference.py).
+# Measured on an MI355X: worst 4.3e-7 (Nyquist crossings), every other family of tests/test_gpu_osc_backward.py and this sweep
+# <= 2e-7; fp32 torch autograd of the restatement reaches ~2.5e-7 on the CPU.  2e-6 stays under 8x the worst measured ratio.
+OSC_BWD_TOL = 2e-6
+OSC_KS = (4, 8, 12, 13, 15, 16, 20, 23, 25)
+
+
+def osc_bwd_variant(B, T, H, hop, sr):
+    """(K, G, pow2, use_lds) of the backward launch for this shape under the current tiling hook: K and G from osc_plan, pow2 and
+    use_lds by the formulas of setup_params (csrc/ddsp_osc.hip) and launch_bwd (csrc/ddsp_osc_bwd.hip)."""
+    plan = ddsp._lib.osc_plan(B, T, H, hop, sr)
+    K, G = plan["harmonics_per_lane"], plan["lanes_per_row"]
+    pow2 = (hop & (hop - 1)) == 0 and hop >= 2 and T * hop <= (1 << 23)
+    use_lds = 4 * (256 // G) * hop <= 64 * 1024
+    return K, G, pow2, use_lds
+
+
+def osc_exact_walk_expected(f0, H, hop, sr):
+    """Whether the inputs send some wavefront of the backward down the exact-modulo walk, from how they were built: a negative
+    f0, a harmonic with >= 1024 rad/sample (masked ones included: their phase still accumulates), or a harmonic whose
+    accumulated phase passes the fast modulo's limit (1e7 rad) within the clip."""
+    f = np.asarray(f0, np.float64)[..., 0]
+    if (f < 0).any():
+        return True
+    fin = np.where(np.isfinite(f), f, 0.0)
+    w_top = 2 * np.pi * H * fin / sr                              # rad/sample of the top harmonic, per frame
+    return bool(w_top.max() >= 1024.0 or (hop * w_top.sum(axis=1)).max() >= 1e7)
+
+
+def compare_osc_backward(ctl, gy, hop, sr, y, gc, ga, rows=None):
+    """Device forward y [B,N] and gradients gc [B,T,H], ga [B,T,1] (NumPy) against the oracle and the fp64 reference on `rows`
+    (default: all).  -> dict of the measured ratios and the checks the backward tests assert."""
+    f0, c, a = ctl["f0"], ctl["c"], ctl["a"]
+    B, T, H = c.shape
+    rows = list(range(B)) if rows is None else list(rows)
+    y64, gc64, ga64, Yc, Ya, yo = R.osc_grad_fp64(f0[rows], c[rows], a[rows], gy[rows], hop, sr, with_oracle_y=True)
+    r = {"rc": R.ratio(gc[rows], gc64, Yc), "ra": R.ratio(ga[rows], ga64, Ya)}
+    r["nonfinite_same"] = bool(np.array_equal(np.isfinite(gc[rows]), np.isfinite(gc64)) and
+                               np.array_equal(np.isfinite(ga[rows]), np.isfinite(ga64)))
+    mask = R.harmonic_mask(f0.reshape(-1, 1), H, sr).numpy().reshape(B, T, H)
+    r["masked_zero"] = bool((gc[mask] == 0.0).all())
+    quiet = [b for b in range(B) if not gy[b].any() and all(np.isfinite(ctl[k][b]).all() for k in ("f0", "c", "a"))]
+    r["quiet_rows"] = len(quiet)
+    r["quiet_zero"] = bool((gc[quiet] == 0.0).all() and (ga[quiet] == 0.0).all())
+    fin = np.isfinite(yo)
+    around = np.maximum(R.loudness_around(a[rows], hop), 1e-30)
+    r["y_err"] = float(np.max((np.abs(y[rows] - yo) / around)[fin])) if fin.any() else 0.0
+    r["y_nonfinite_same"] = bool(np.array_equal(np.isfinite(y[rows]), fin))
+    return r
+
+
+def osc_backward_case(ctl, gy, hop, sr, K=None, rows=None):
+    """Raw launchers: ddsp_osc_forward_ex (frame-form scratch kept) + ddsp_osc_backward twice, the tiling pinned to K (if given)
+    across the forward AND both backward calls (the backward re-runs pick_tiling to read the scratch's layout).
+    -> compare_osc_backward's dict + K, G, pow2, use_lds, exact and whether the repeat was bit-identical."""
+    L = ddsp._lib.lib()
+    B, T, H = ctl["c"].shape
+    d = {k: torch.from_numpy(np.ascontiguousarray(ctl[k])).cuda() for k in ("f0", "c", "a")}
+    g = torch.from_numpy(np.ascontiguousarray(gy)).cuda()
+    try:
+        if K:
+            ddsp._lib.check(L.ddsp_osc_set_tiling(K), "ddsp_osc_set_tiling")
+        Kp, G, pow2, use_lds = osc_bwd_variant(B, T, H, hop, sr)
+        y, _, _, scratch = ddsp.osc_forward(d["f0"], d["c"], d["a"], hop, sr, return_scratch=True)
+        gc, ga = ddsp.osc_backward(g, d["f0"], d["c"], d["a"], scratch, hop, sr)
+        gc2, ga2 = ddsp.osc_backward(g, d["f0"], d["c"], d["a"], scratch, hop, sr)
+        torch.cuda.synchronize()
+    finally:
+        if K:
+            L.ddsp_osc_set_tiling(0)
+    gc, ga, gc2, ga2 = (x.cpu().numpy() for x in (gc, ga, gc2, ga2))
+    r = compare_osc_backward(ctl, gy, hop, sr, y.cpu().numpy(), gc, ga, rows)
+    r.update(K=Kp, G=G, pow2=pow2, use_lds=use_lds, exact=osc_exact_walk_expected(ctl["f0"], H, hop, sr),
+             repeat_same=bool(np.array_equal(bits(gc), bits(gc2)) and np.array_equal(bits(ga), bits(ga2))))
+    return r
+
+
+def osc_backward_ok(r, tol=OSC_BWD_TOL):
+    """The assertions every backward case makes, as one bool (the tests assert the fields one by one)."""
+    return (r["rc"] <= tol and r["ra"] <= tol and r["nonfinite_same"] and r["masked_zero"] and r["quiet_zero"] and
+            r["repeat_same"] and r["y_err"] <= 1e-5 and r["y_nonfinite_same"])
+
+
+def sweep_osc_backward(cases: int, seed: int, verbose: bool = True):
+    """Random shapes of the oscillator backward against the fp64 reference: the tiling pinned in half the cases (G of 1, 4, 8 or 16
+    lanes), non-power-of-two and power-of-two hops (grad_y through LDS or global memory), silent stretches, exactly-zero harmonics,
+    loudness over seven decades, a row whose upstream gradient is zero, glissandi across Nyquist, and the odd f0 of sweep_chunked
+    (negative, x300, NaN).  B*N*H <= 4 M per case.  -> (failed, {family: worst max(err_c / Yc, err_a / Ya)})"""
+    rng = np.random.default_rng(seed)
+    worst = {}
+    bad = 0
+    for i in range(cases):
+        hop = int(rng.choice([1, 3, 7, 48, 100, 160, 441, 480, 1600] + [2, 64, 128, 256, 512, 1024, 2048]))
+        sr = int(rng.choice([8000, 16000, 22050, 44100, 48000]))
+        K = None
+        if rng.random() < 0.5:
+            K = int(rng.choice(OSC_KS))
+            G = int(rng.choice([1, 4, 8, 16]))
+            H = int(rng.integers(K * G // 2 + 1, K * G + 1)) if G > 1 else int(rng.integers(1, K + 1))
+        else:
+            H = int(rng.integers(1, 241))
+        B = int(rng.integers(1, 5))
+        T = int(rng.integers(1, max(2, min(300, 4_000_000 // (B * hop * H) + 1))))
+        kind = "musical" if rng.random() < 0.5 else "all_live"
+        ctl = syn.make_controls(syn.SynthShape("fz", B, sr, hop, T, H, 2), int(rng.integers(1 << 30)), kind)
+        gy = rng.standard_normal((B, T * hop)).astype(np.float32)
+        if rng.random() < 0.2:
+            ctl["f0"][0, T // 2:, 0] = 0.0
+        if rng.random() < 0.2:
+            ctl["c"][:, :, rng.integers(0, H)] = 0.0
+        if rng.random() < 0.3:
+            ctl["a"] = ctl["a"] * (10.0 ** rng.uniform(-4, 3, size=ctl["a"].shape)).astype(np.float32)
+        if rng.random() < 0.2:                                      # a glissando through Nyquist: the live-harmonic count changes
+            ctl["f0"][0, :, 0] = np.geomspace(0.5 * sr / (2 * H), 0.9 * sr / 2, T).astype(np.float32)
+        if B > 1 and rng.random() < 0.3:
+            gy[int(rng.integers(0, B))] = 0.0                        # a row with no upstream gradient: its gradient is exactly 0
+        odd = rng.random()
+        if odd < 0.08:
+            ctl["f0"][B - 1, rng.integers(0, T), 0] = -150.0
+        elif odd < 0.16:
+            ctl["f0"][B - 1, :, 0] *= 300.0
+        elif odd < 0.2:
+            ctl["f0"][B - 1, rng.integers(0, T), 0] = np.nan
+        r = osc_backward_case(ctl, gy, hop, sr, K=K)
+        okay = osc_backward_ok(r) and (K is None or r["K"] == K)
+        bad += not okay
+        e = max(r["rc"], r["ra"])
+        for fam in (f"K{r['K']}", "pow2" if r["pow2"] else "non-pow2", "grad_y in LDS" if r["use_lds"] else "grad_y global",
+                    "exact" if r["exact"] else "fast", "tiling pinned" if K else "automatic tiling"):
+            worst[fam] = max(worst.get(fam, 0.0), e)
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} backward B{B} T{T} H{H} hop{hop} sr{sr} K{r['K']} G{r['G']} {kind}"
+                  f"{' odd-f0' if odd < 0.2 else ''}: c {r['rc']:.1e} a {r['ra']:.1e} |dy| {r['y_err']:.1e} "
+                  f"{'' if r['nonfinite_same'] else 'NON-FINITE PATTERN DIFFERS '}{'' if r['masked_zero'] else 'MASKED NONZERO '}"
+                  f"{'' if r['quiet_zero'] else 'QUIET ROW NONZERO '}{'' if r['repeat_same'] else 'REPEAT DIFFERS'}", flush=True)
+    return bad, worst
+
+
 def sweep_training_kernels(cases: int, seed: int, verbose: bool = True):
     """Random shapes of the loss-side kernels against torch on the CPU in fp64: ddsp_mss_scale (+ the overlap-add gather) for random
     batch / length / transform size / overlap, the framing pair around a library rfft, and the column sums.  -> failed cases"""
@@ -248,6 +390,11 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] == "chunked":
         bad, worst = sweep_chunked(cases, seed, verbose=False)
         print(f"chunked oscillator form: cases {cases}, seed {seed}, failed {bad}, worst audio error {worst:.2e}")
+        sys.exit(1 if bad else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "backward":
+        bad, worst = sweep_osc_backward(cases, seed, verbose=False)
+        print(f"oscillator backward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per family: "
+              + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
         sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "training":
         bad = sweep_training_kernels(cases, seed, verbose=False)

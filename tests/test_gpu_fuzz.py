@@ -1,5 +1,6 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
-oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6."""
+oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
+plus the chunked oscillator form, the loss-side kernels and the oscillator backward."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,3 +24,11 @@ def test_random_shapes_of_the_loss_side_kernels_match_torch(seed):
 def test_random_shapes_of_the_chunked_oscillator_match_the_oracle(seed):
     bad, worst = fuzz_parity.sweep_chunked(60, seed, verbose=False)
     assert bad == 0 and worst <= 1e-5
+
+
+@pytest.mark.parametrize("seed", [505])
+def test_random_shapes_of_the_oscillator_backward_match_fp64(seed):
+    """40 random cases of ddsp_osc_backward against the fp64 reference (tests/osc_grad_reference.py), elementwise within
+    fuzz_parity.OSC_BWD_TOL of each frame's local yardstick: pinned and automatic tilings, both walks, both grad_y paths, odd f0."""
+    bad, worst = fuzz_parity.sweep_osc_backward(40, seed, verbose=False)
+    assert bad == 0, (bad, worst)
