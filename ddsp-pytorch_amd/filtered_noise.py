@@ -50,10 +50,24 @@ def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, 
 
 def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0, offset: int = 0, counter=None):
     """Raw launcher of ddsp_noise_backward_ws: grad_y [B,T*hop] -> grad_H [B,T,F] for the same draw as the forward
-    (`counter`: the device counter the forward read, still at the same value)."""
+    (`counter`: the device counter the forward read, still at the same value).  Checked before any launch, as noise_forward
+    checks its arguments: the kernels read B*T*hop samples of grad_y and uniform."""
+    if grad_y.dim() != 2 or hop <= 0 or grad_y.shape[1] % hop != 0:
+        raise ValueError(f"expected grad_y [B, T*hop] with hop = {hop}, got {tuple(grad_y.shape)}")
+    if n_filters < 2:
+        raise ValueError(f"n_filters must be >= 2, got {n_filters}")
+    if not grad_y.is_cuda:
+        raise _lib.DdspHipError("FilteredNoise runs on the GPU only (no CPU fallback): move the gradient to cuda")
     grad_y = grad_y.detach().contiguous().float()
     B = grad_y.shape[0]
     T = grad_y.shape[1] // hop
+    if uniform is not None:
+        if tuple(uniform.shape) != (B, T, hop) or uniform.dtype != torch.float32 or uniform.device != grad_y.device:
+            raise ValueError(f"uniform must be an fp32 [B,T,hop] = {(B, T, hop)} tensor on {grad_y.device}, "
+                             f"got {uniform.dtype} {tuple(uniform.shape)} on {uniform.device}")
+        uniform = uniform.detach().contiguous()
+    if counter is not None and (uniform is not None or counter.dtype != torch.int64 or counter.numel() != 1 or not counter.is_cuda):
+        raise ValueError("counter must be a 1-element int64 CUDA tensor and excludes an injected draw")
     grad_h = torch.empty((B, T, n_filters), device=grad_y.device, dtype=torch.float32)
     if B == 0:
         return grad_h

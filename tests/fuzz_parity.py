@@ -6,9 +6,10 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward]   (`training`: the loss-side kernels against fp64 torch instead;
-`chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's backward against the
-fp64 reference of tests/osc_grad_reference.py)"""
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward]   (`training`: the loss-side kernels against
+fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
+backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
+fp64 reference of tests/noise_grad_reference.py)"""
 import os
 import sys
 
@@ -23,6 +24,7 @@ from ddsp_pytorch_amd import synthetic as syn  # noqa: E402
 from oracle import oracle  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import osc_grad_reference as R  # noqa: E402
+import noise_grad_reference as R_noise  # noqa: E402
 
 
 def bits(a):
@@ -307,6 +309,196 @@ def sweep_osc_backward(cases: int, seed: int, verbose: bool = True):
     return bad, worst
 
 
+# ---- the filtered noise's backward (csrc/ddsp_noise.hip: ddsp_noise_backward_ws) against the fp64 reference ---------------------
+# Elementwise |dH - fp64| <= NOISE_BWD_TOL x the frame's yardstick Y[f] (noise_grad_reference.py), and per frame max |err| <= 1e-5 x
+# max |fp64| of the frame.  Exempt from the latter only: frames whose largest gradient is below NOISE_BWD_FRAME_FLOOR x Y[f] (the
+# gradient cancels to a small part of its absolute sum, and any fp32 evaluation's relative error grows as eps Y / max |fp64|), and
+# every frame at 2 bands, where each frame's whole gradient is one dot product of the hop's samples, dH[0] = dH[1] = sum_d x[d] g[d] / 2:
+# it cancels to any degree (measured on an MI355X: 1.3e-5 of the frame's peak at 2 bands / hop 64, peak ~ 3e-3 Y, error 4.7e-8 Y).
+# Measured on an MI355X (tests/test_gpu_noise_backward.py and 2 000 cases of this sweep): forms A and B <= 2e-8 of Y for frames at
+# 2^-100 and above (1.6e-7 for a frame below form A's equaliser clamp, 2^-110 next to a unit row); the direct forms reach 2.4e-7 (C) and
+# 4.2e-7 (D) at hops 7-8 with 35-44 bands.  There the impulse response is cropped to the hop, so only the window's edge values (~1e-3)
+# are used.  The kernels form the window as 0.5 - 0.5 cospif(2 m / S) in fp32 (csrc/ddsp_noise.hip); the oracle, and with it the fp64
+# reference, rounds an fp64 cosine instead.  Where the two cosines differ by an ulp near 1, the window value differs by ~1e-5 of
+# itself: a definitional difference between kernel and oracle, not rounding in the kernels' sums.  One ulp on every cosine moves the
+# fp64 reference by up to 1.3e-6 of Y at 35 bands / hop 7 (1e-9 at hop 512).  1e-6 is 2.4x the worst.
+NOISE_BWD_TOL = 1e-6
+NOISE_BWD_FRAME_REL = 1e-5
+NOISE_BWD_FRAME_FLOOR = 1e-3
+
+
+def noise_bwd_lpf_log(F, hop):
+    """pick_bwd_lpf_log (csrc/ddsp_noise.hip): log2 lanes per frame of the batched backward, -1 when no tile fits in LDS."""
+    S = 2 * (F - 1)
+    for limit in (48 * 1024, 80 * 1024, 160 * 1024):
+        for l in range(4):
+            fb = 64 >> l
+            if 4 * (((S + 3) & ~3) + fb * (hop + 4) + fb * (hop + 12) + (S // 2 + 1) * (fb + 4)) <= limit:
+                return l
+    return -1
+
+
+def noise_bwd_form(B, T, F, hop, mode=0, aligned=True):
+    """The kernel form ddsp_noise_backward_ws takes: 'A' (in-LDS FFT correlation), 'B' (FFT correlation + split-bf16 product),
+    'C0'..'C3' (batched direct kernel, log2 lanes per frame), 'D' (one frame per workgroup) -- by the dispatch's own conditions."""
+    if not mode & 3 and hop == 512 and aligned:
+        if not mode & 16 and ddsp._lib.lib().ddsp_noise_workspace_bytes(B, T, F, hop) > 0:
+            return "B"
+        if 2 * (F - 1) == 512:
+            return "A"
+    lpf = noise_bwd_lpf_log(F, hop)
+    if not mode & 1 and hop % 8 == 0 and lpf >= 0:
+        return f"C{lpf}"
+    return "D"
+
+
+def misaligned(a):
+    """A contiguous CUDA copy of `a` whose data starts 4 bytes into its storage (not 16-byte aligned)."""
+    a = torch.as_tensor(np.ascontiguousarray(a))
+    buf = torch.empty(a.numel() + 1, dtype=a.dtype, device="cuda")
+    v = buf[1:].view(a.shape)
+    v.copy_(a.cuda())
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v
+
+
+def noise_backward_run(gy, F, hop, uniform=None, seed=0, offset=0, counter=None, mode=0, misalign=()):
+    """Two launches of ddsp.noise_backward under ddsp_noise_set_generic(mode) -> (dH, repeat) as NumPy.  `misalign`: the names
+    of the inputs ('grad_y', 'uniform') passed as views 4 bytes into their storage."""
+    L = ddsp._lib.lib()
+
+    def put(a, name):
+        return misaligned(a) if name in misalign else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    g = put(gy, "grad_y")
+    kw = dict(uniform=put(uniform, "uniform")) if uniform is not None else dict(seed=seed, offset=offset)
+    if counter is not None:
+        kw["counter"] = torch.tensor([counter], dtype=torch.int64, device="cuda")
+    try:
+        ddsp._lib.check(L.ddsp_noise_set_generic(mode), "ddsp_noise_set_generic")
+        a = ddsp.noise_backward(g, hop, F, **kw)
+        b = ddsp.noise_backward(g, hop, F, **kw)
+        torch.cuda.synchronize()
+    finally:
+        L.ddsp_noise_set_generic(0)
+    return a.cpu().numpy(), b.cpu().numpy()
+
+
+def compare_noise_backward(got, ref, Y, gy, hop, paired=False):
+    """Device dH [B,T,F] against the fp64 reference (ref, Y) -> dict of the measured ratios and the checks the tests assert.
+    `paired`: the kernel shares transforms between frames 2p and 2p + 1 (forms A and B, ddsp_noise_fft.hip: load_rows), so the
+    partner of a frame with a non-finite gradient may come out entirely non-finite; never finite and wrong."""
+    B, T, F = ref.shape
+    g = np.asarray(gy, np.float32).reshape(B * T, hop)
+    got, ref, Y = got.reshape(B * T, F), ref.reshape(B * T, F), Y.reshape(B * T)
+    bad = ~np.isfinite(g).all(axis=1)
+    partner = np.zeros_like(bad)
+    if paired:
+        idx = np.flatnonzero(bad)
+        partner[np.minimum(idx ^ 1, B * T - 1)] = True       # (an odd last frame is paired with itself)
+        partner &= ~bad
+    fin_got = np.isfinite(got).all(axis=1)
+    lost = partner & ~np.isfinite(got).any(axis=1)            # partners that came out entirely non-finite
+    judged = ~bad & ~lost
+    r = {"frames": B * T, "bad_frames": int(bad.sum()), "partners_lost": int(lost.sum())}
+    r["nonfinite_ok"] = bool((~np.isfinite(got[bad])).all() and fin_got[judged].all())
+    per = R_noise.ratio(got[judged], ref[judged], Y[judged])
+    r["ratio"] = float(per.max()) if per.size else 0.0
+    err = np.abs(got[judged] - ref[judged]).max(axis=1) if F else np.zeros(0)
+    peak = np.abs(ref[judged]).max(axis=1)
+    keep = (peak >= NOISE_BWD_FRAME_FLOOR * Y[judged]) & (F > 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.where(err[keep] == 0.0, 0.0, err[keep] / peak[keep])
+    r["frame_rel"] = float(np.nan_to_num(rel, nan=np.inf).max()) if rel.size else 0.0
+    zero = ~g.any(axis=1) & ~partner
+    r["zero_frames"] = int(zero.sum())
+    r["zero_exact"] = bool((got[zero] == 0.0).all())
+    return r
+
+
+def noise_backward_case(gy, F, hop, uniform=None, seed=0, offset=0, counter=None, mode=0, misalign=(), against_d=True, same_as=None):
+    """ddsp.noise_backward twice (bit-identical repeat) against noise_grad_reference.noise_grad_fp64 of the same draw (the Philox
+    offset includes the counter's value).  against_d: also the same call under mode 1 (the one-frame-per-workgroup kernel), which
+    must meet the same contract and -- when the default took another form -- differ from it bitwise.  same_as: also the same call
+    under that mode; r['same_as'] tells whether the two results are bit-identical (mode 2 forces the direct kernels: a call that
+    declined forms A and B equals it, one that took them does not).  -> dict (+ 'form')."""
+    g = np.ascontiguousarray(gy, np.float32)
+    B, T = g.shape[0], g.shape[1] // hop
+    form = noise_bwd_form(B, T, F, hop, mode, aligned="grad_y" not in misalign and (uniform is None or "uniform" not in misalign))
+    ref, Y = R_noise.noise_grad_fp64(g, F, hop, uniform=uniform, seed=seed, offset=offset + (counter or 0))
+    got, again = noise_backward_run(g, F, hop, uniform, seed, offset, counter, mode, misalign)
+    r = compare_noise_backward(got, ref, Y, g, hop, paired=form in ("A", "B"))
+    r.update(form=form, F=F, repeat_same=bool(np.array_equal(bits(got), bits(again))))
+    if same_as is not None:
+        other, _ = noise_backward_run(g, F, hop, uniform, seed, offset, counter, same_as, misalign)
+        r["same_as"] = bool(np.array_equal(bits(got), bits(other)))
+    if against_d and form != "D":
+        d, _ = noise_backward_run(g, F, hop, uniform, seed, offset, counter, 1, misalign)
+        rd = compare_noise_backward(d, ref, Y, g, hop)
+        r["differs_from_d"] = not np.array_equal(bits(got), bits(d))
+        r["d_ok"] = rd["ratio"] <= NOISE_BWD_TOL and rd["frame_rel"] <= NOISE_BWD_FRAME_REL and rd["nonfinite_ok"] and rd["zero_exact"]
+        r["d_ratio"] = rd["ratio"]
+    return r
+
+
+def noise_backward_ok(r, tol=NOISE_BWD_TOL):
+    """The assertions every noise backward case makes, as one bool (the tests assert the fields one by one)."""
+    return (r["ratio"] <= tol and r["frame_rel"] <= NOISE_BWD_FRAME_REL and r["nonfinite_ok"] and r["zero_exact"] and r["repeat_same"]
+            and r.get("d_ok", True) and r.get("differs_from_d", True))
+
+
+def frame_levels(rng, B, T, decades=True):
+    """Per-frame levels [B,T,1] of the upstream gradient: 10^U(-4,3) (seven decades), or ones."""
+    if not decades:
+        return np.ones((B, T, 1), np.float32)
+    return (10.0 ** rng.uniform(-4, 3, size=(B, T, 1))).astype(np.float32)
+
+
+def sweep_noise_backward(cases: int, seed: int, verbose: bool = True):
+    """Random shapes of the noise backward against the fp64 reference: odd hops, multiples of 8, 256, 512 (every form: in-LDS FFT at
+    257 bands, the split-bf16 product in the 193..224-band range at >= 512 frames, batched direct at every lane count, one frame per
+    workgroup), the injected draw or the in-kernel one at 64-bit offsets (a device counter in some), frame levels over seven decades,
+    zero frames, forced modes 0 / 1 / 2 / 16.  B*T*hop <= 1.5 M per case.  -> (failed, {form: worst error / yardstick})"""
+    rng = np.random.default_rng(seed)
+    worst = {}
+    bad = 0
+    for i in range(cases):
+        kind = rng.random()
+        if kind < 0.15:                                              # the matrix-product form's band range, >= 512 frames
+            hop, F = 512, int(rng.integers(193, 225))
+            n = int(rng.integers(512, 700)) if rng.random() < 0.8 else int(rng.integers(400, 512))
+        elif kind < 0.3:
+            hop, F = 512, 257 if rng.random() < 0.6 else int(rng.integers(2, 400))
+            n = int(rng.integers(1, 120))
+        else:
+            hop = int(rng.choice([1, 3, 5, 7, 12, 100, 441, 8, 16, 40, 64, 128, 160, 256, 480, 1024]))
+            F = int(rng.integers(2, min(1100, 2 * hop + 40) + 1))
+            n = int(rng.integers(1, max(2, min(200, 1_500_000 // hop))))
+        B = int(rng.choice([d for d in (1, 2, 3, 4) if n % d == 0])) if n > 3 else 1
+        T = n // B
+        gy = rng.standard_normal((B, T, hop)).astype(np.float32) * frame_levels(rng, B, T, rng.random() < 0.5)
+        if n > 1 and rng.random() < 0.3:
+            gy[rng.integers(0, B), rng.integers(0, T)] = 0.0          # a frame with no upstream gradient: exact zeros
+        gy = gy.reshape(B, T * hop)
+        mode = int(rng.choice([0, 0, 0, 1, 2, 16]))
+        kw = {}
+        if rng.random() < 0.5:
+            kw["uniform"] = rng.random((B, T, hop), dtype=np.float32)
+        else:
+            kw["seed"], kw["offset"] = int(rng.integers(1 << 62)), int(rng.integers(1 << 62))
+            if rng.random() < 0.3:
+                kw["counter"] = int(rng.integers(1 << 40))
+        r = noise_backward_case(gy, F, hop, mode=mode, against_d=False, **kw)
+        okay = noise_backward_ok(r)
+        bad += not okay
+        worst[r["form"]] = max(worst.get(r["form"], 0.0), r["ratio"])
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} noise backward B{B} T{T} F{F} hop{hop} mode {mode} form {r['form']} "
+                  f"{'injected' if 'uniform' in kw else 'philox'}: {r['ratio']:.1e} of Y, frame {r['frame_rel']:.1e}"
+                  f"{'' if r['nonfinite_ok'] else ' NON-FINITE'}{'' if r['zero_exact'] else ' ZERO FRAME NONZERO'}"
+                  f"{'' if r['repeat_same'] else ' REPEAT DIFFERS'}", flush=True)
+    return bad, worst
+
+
 def sweep_training_kernels(cases: int, seed: int, verbose: bool = True):
     """Random shapes of the loss-side kernels against torch on the CPU in fp64: ddsp_mss_scale (+ the overlap-add gather) for random
     batch / length / transform size / overlap, the framing pair around a library rfft, and the column sums.  -> failed cases"""
@@ -394,6 +586,11 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] == "backward":
         bad, worst = sweep_osc_backward(cases, seed, verbose=False)
         print(f"oscillator backward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per family: "
+              + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
+        sys.exit(1 if bad else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "noise_backward":
+        bad, worst = sweep_noise_backward(cases, seed, verbose=False)
+        print(f"noise backward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per form: "
               + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
         sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "training":

@@ -1,6 +1,6 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
 oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
-plus the chunked oscillator form, the loss-side kernels and the oscillator backward."""
+plus the chunked oscillator form, the loss-side kernels and the backward of the oscillator and of the filtered noise."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,4 +31,12 @@ def test_random_shapes_of_the_oscillator_backward_match_fp64(seed):
     """40 random cases of ddsp_osc_backward against the fp64 reference (tests/osc_grad_reference.py), elementwise within
     fuzz_parity.OSC_BWD_TOL of each frame's local yardstick: pinned and automatic tilings, both walks, both grad_y paths, odd f0."""
     bad, worst = fuzz_parity.sweep_osc_backward(40, seed, verbose=False)
+    assert bad == 0, (bad, worst)
+
+
+@pytest.mark.parametrize("seed", [606])
+def test_random_shapes_of_the_noise_backward_match_fp64(seed):
+    """40 random cases of ddsp_noise_backward_ws against the fp64 reference (tests/noise_grad_reference.py), elementwise within
+    fuzz_parity.NOISE_BWD_TOL of each frame's yardstick: every kernel form, injected and in-kernel draws, forced modes, zero frames."""
+    bad, worst = fuzz_parity.sweep_noise_backward(40, seed, verbose=False)
     assert bad == 0, (bad, worst)
