@@ -13,8 +13,11 @@ batch 512 per GPU, 16 kHz, 100 harmonics, hop 128, 4 s clips, 65 noise bands (cf
 weak scaling: every rank synthesises its own 512 rows, no collective on the data path).
 
 Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (osc_frame_synth) from HIP events
-recorded on the launch stream during the timed region; `cpu_baseline` times the torch-op restatement of
-the reference's CPU path (oracle/torch_restatement.py) on this box's host cores (rank 0, N=1 only).
+recorded on the launch stream during the timed region.  A plain run does only what that line needs: set-up (the
+noise kernel's residency calibration included), warm-up, the timed steps, --dump-outputs.  `--full` adds the figures
+that take runs of their own, after the timed region: the shader clock probe, the other kernels' averages, the live
+HBM traffic, the secondary configurations and `cpu_baseline` (the torch-op restatement of the reference's CPU path,
+oracle/torch_restatement.py, on this box's host cores; rank 0, N=1 only).
 """
 import argparse
 import json
@@ -513,13 +516,16 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="rows per GPU (default: the metric's 512)")
     ap.add_argument("--tiling", type=int, default=0, help="force harmonics per lane (tuning)")
     ap.add_argument("--harmonics", type=int, default=0, help="override the number of harmonics (tuning experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="synth mode: after the timed region also measure the shader clock, the other kernels' averages, the live HBM "
+                         "traffic, the secondary configurations and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not measure roofline.traffic with two rocprofv3 child passes after the timed region (N = 1); use the committed profile")
+                    help="--full: do not measure roofline.traffic with two rocprofv3 child passes after the timed region (N = 1); use the committed profile")
     ap.add_argument("--no-calibrate", action="store_true",
                     help="keep the noise kernel's default residency (4 wavefronts per CU) instead of measuring this box first")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary figures (cfg1, cfg2, cfg3, musical f0, live callback, training step) timed after the headline at N = 1")
+                    help="--full: skip the secondary figures (cfg1, cfg2, cfg3, musical f0, live callback, training step) timed after the headline at N = 1")
     ap.add_argument("--mode", default="synth", choices=["synth", "train"],
                     help="synth: the headline hot path; train: BASELINE.json configs[4] (decoder + MSS loss + Adam, "
                          "batch 32/GPU, flat RCCL gradient all-reduce) -- a secondary figure, not the metric")
@@ -659,13 +665,16 @@ def main():
     idle_kernel = {}
     for name, ms in idle_records:
         idle_kernel.setdefault(name, []).append(ms)
-    # the shader clock this box's synth kernel runs at, measured in the kernel right after the timed region (every VALU
-    # fraction below is quoted against the 2.4 GHz peak AND against the peak at this clock: boxes of the pool differ by 10 %)
-    clock = measure_clock(x, shape, step) if rank == 0 else None
-    # the synth kernel's average: the timed region's own events; the other kernels': K more steps each, after the clock probe
-    kern_ms = kernel_breakdown(step, done + args.warmup + args.steps, args.steps, [k for k in KERNELS if k != "osc_frame_synth"])
-    kern_ms["osc_frame_synth"] = float(np.mean([ms for name, ms in records if name == "osc_frame_synth"]))
-    kern_ms = {k: kern_ms[k] for k in KERNELS if k in kern_ms}
+    # the synth kernel's average: the timed region's own events
+    kern_ms = {"osc_frame_synth": float(np.mean([ms for name, ms in records if name == "osc_frame_synth"]))}
+    clock = None
+    if args.full:
+        # the shader clock this box's synth kernel runs at, measured in the kernel right after the timed region (every VALU
+        # fraction below is quoted against the 2.4 GHz peak AND against the peak at this clock: boxes of the pool differ by 10 %)
+        clock = measure_clock(x, shape, step) if rank == 0 else None
+        # the other kernels' averages: K more steps each, after the clock probe
+        kern_ms.update(kernel_breakdown(step, done + args.warmup + args.steps, args.steps, [k for k in KERNELS if k != "osc_frame_synth"]))
+        kern_ms = {k: kern_ms[k] for k in KERNELS if k in kern_ms}
     # every rank's own clock and per-kernel averages, gathered so that the first multi-GPU run diagnoses itself: a slow rank
     # (clock, thermal, a noisy neighbour on its XCDs) shows up by index instead of hiding inside the MAX
     diag = gather_rows(dist, [1e3 * own_elapsed / args.steps] + [kern_ms.get(k, float("nan")) for k in KERNELS], world, rank)
@@ -695,18 +704,12 @@ def main():
         traffic = traffic_of("osc_chunk_synth_kernel") or traffic_of("osc_synth_kernel")
         traffic_src = f"profiles/{pmc_name} (FETCH_SIZE x2 + WRITE_SIZE)" if traffic else None
         traffic_committed = traffic
-        if world == 1 and not args.no_live_pmc and not (args.batch or args.tiling or args.harmonics):
+        if args.full and world == 1 and not args.no_live_pmc and not (args.batch or args.tiling or args.harmonics):
             live, how = live_traffic(args.f0)
             if live:
                 traffic, traffic_src = live, how
             else:
                 traffic_src = (traffic_src or "none") + f" [live measurement skipped: {how}]"
-        # the kernel SURVEY §8(d) says can approach the HBM roof: 4 (y) + 4 F / hop (H) bytes per sample (the draw is made
-        # in the kernel; the accumulate's read of y is the oscillator's output coming back, not counted as algorithmic)
-        noise_ms = kern_ms.get("noise_frame", float("nan"))
-        noise_bps = 4.0 + 4.0 * shape.n_noise_filters / shape.hop
-        noise_achieved = launch_samples * noise_bps / (noise_ms * 1e-3) / 1e9
-        noise_macs = shape.hop / 2.0 + shape.n_noise_filters          # direct form: truncated convolution + inverse DFT, per sample
         at_clock = (NOMINAL_GHZ / clock) if clock else None     # peak at this clock = nominal peak x clock / 2.4
         line = {
             "metric": "audio samples/sec/GPU + %HBM-roofline, 16kHz/100-harmonic/batch512",
@@ -736,11 +739,7 @@ def main():
                              "from_idle": {"ms_per_step": 1e3 * idle_elapsed / args.steps,
                                            "value": samples_per_step * args.steps / idle_elapsed,
                                            "kernel_ms": {k: float(np.mean(v)) for k, v in idle_kernel.items()}}},
-            "clock_ghz": clock, "clock_nominal_ghz": NOMINAL_GHZ,
-            "clock_source": "in-kernel: shader-clock ticks over 100 MHz wall-clock ticks across one synth wavefront (ddsp_osc_clock); "
-                            "median of 3 readings, each the synth launch after 11 more back-to-back steps, right after the timed region",
             "osc_plan": ddsp._lib.osc_plan(shape.batch, shape.frames, shape.n_harmonics, shape.hop, shape.sample_rate),
-            "kernel_Mcycles": {k: v * 1e-3 * clock * 1e3 for k, v in kern_ms.items()} if clock else None,
             "roofline": {"bound": "hbm", "kernel": "osc_frame_synth", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "traffic_committed_profile": traffic_committed,
@@ -758,29 +757,41 @@ def main():
                                   "survey_frac": hs_per_s * SURVEY_FLOPS_PER_HS / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
                                   "survey_frac_at_clock": hs_per_s * SURVEY_FLOPS_PER_HS / 1e12 / FP32_VECTOR_PEAK_TFLOPS * at_clock if at_clock else None,
                                   "survey_frac_whole_step": (launch_samples * shape.n_harmonics / (elapsed / args.steps))
-                                                            * SURVEY_FLOPS_PER_HS / 1e12 / FP32_VECTOR_PEAK_TFLOPS},
-                         "noise_frame": {"bound": "hbm", "kernel": "noise_frame", "achieved": noise_achieved, "peak": HBM_PEAK_GBS,
-                                         "unit": "GB/s", "frac": noise_achieved / HBM_PEAK_GBS, "traffic": traffic_of("noise_wave_kernel"),
-                                         "algorithmic_bytes_per_launch": launch_samples * noise_bps,
-                                         "algorithmic_bytes_per_sample": noise_bps, "avg_launch_ms": noise_ms,
-                                         "note": "wavefront-private form at hop 128 (round 3): truncated convolution hop/2 multiply-adds per sample on the vector "
-                                                 "pipe + F per sample as split-bf16 matrix-core products + 10 Philox rounds per 4 samples -> VALU-bound",
-                                         "valu": {"mac_per_sample": noise_macs,
-                                                  "achieved_Tlaneops": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12,
-                                                  "peak_Tlaneops": VALU_PEAK_TLANEOPS,
-                                                  "frac": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12 / VALU_PEAK_TLANEOPS,
-                                                  "frac_at_clock": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12 / VALU_PEAK_TLANEOPS * at_clock if at_clock else None}}},
+                                                            * SURVEY_FLOPS_PER_HS / 1e12 / FP32_VECTOR_PEAK_TFLOPS}},
             "kernel_ms": kern_ms,
-            "kernel_ms_source": "osc_frame_synth: HIP events inside the timed region; each other kernel: K more steps with events around that kernel "
-                                "only.  An event pair is not a barrier: a reading includes what was left of the preceding kernel (the noise kernel's "
+            "kernel_ms_source": "osc_frame_synth: HIP events inside the timed region; each other kernel (--full): K more steps with events around "
+                                "that kernel only.  An event pair is not a barrier: a reading includes what was left of the preceding kernel (the noise kernel's "
                                 "tail in osc_frame_totals: +0.03 ms against the rocprofv3 trace, profiles/rNN_kernel_stats.csv)",
             "per_rank_ms": [float(v) for v in diag[:, 0]],
-            "per_rank_kernel_ms": {k: [float(v) for v in diag[:, 1 + j]] for j, k in enumerate(KERNELS)},
+            "per_rank_kernel_ms": {k: [float(v) for v in diag[:, 1 + j]] for j, k in enumerate(KERNELS) if k in kern_ms},
             "slowest_rank": int(np.argmax(diag[:, 0])),
             "collective_backend": dist.get_backend() if dist is not None else None,
             "rccl_ranks": dist.get_world_size() if dist is not None else 1,
         }
-        if world == 1 and not args.no_secondary and not (args.batch or args.harmonics or args.tiling):
+        if args.full:
+            line.update({"clock_ghz": clock, "clock_nominal_ghz": NOMINAL_GHZ,
+                         "clock_source": "in-kernel: shader-clock ticks over 100 MHz wall-clock ticks across one synth wavefront (ddsp_osc_clock); "
+                                         "median of 3 readings, each the synth launch after 11 more back-to-back steps, right after the timed region",
+                         "kernel_Mcycles": {k: v * 1e-3 * clock * 1e3 for k, v in kern_ms.items()} if clock else None})
+            # the kernel SURVEY §8(d) says can approach the HBM roof: 4 (y) + 4 F / hop (H) bytes per sample (the draw is made
+            # in the kernel; the accumulate's read of y is the oscillator's output coming back, not counted as algorithmic)
+            noise_ms = kern_ms.get("noise_frame", float("nan"))
+            noise_bps = 4.0 + 4.0 * shape.n_noise_filters / shape.hop
+            noise_achieved = launch_samples * noise_bps / (noise_ms * 1e-3) / 1e9
+            noise_macs = shape.hop / 2.0 + shape.n_noise_filters          # direct form: truncated convolution + inverse DFT, per sample
+            line["roofline"]["noise_frame"] = {
+                "bound": "hbm", "kernel": "noise_frame", "achieved": noise_achieved, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": noise_achieved / HBM_PEAK_GBS, "traffic": traffic_of("noise_wave_kernel"),
+                "algorithmic_bytes_per_launch": launch_samples * noise_bps,
+                "algorithmic_bytes_per_sample": noise_bps, "avg_launch_ms": noise_ms,
+                "note": "wavefront-private form at hop 128 (round 3): truncated convolution hop/2 multiply-adds per sample on the vector "
+                        "pipe + F per sample as split-bf16 matrix-core products + 10 Philox rounds per 4 samples -> VALU-bound",
+                "valu": {"mac_per_sample": noise_macs,
+                         "achieved_Tlaneops": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12,
+                         "peak_Tlaneops": VALU_PEAK_TLANEOPS,
+                         "frac": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12 / VALU_PEAK_TLANEOPS,
+                         "frac_at_clock": launch_samples * noise_macs / (noise_ms * 1e-3) / 1e12 / VALU_PEAK_TLANEOPS * at_clock if at_clock else None}}
+        if args.full and world == 1 and not args.no_secondary and not (args.batch or args.harmonics or args.tiling):
             # SECONDARY figures, timed AFTER (outside) the headline's timed region: BASELINE.json configs[1] and configs[2] on this GPU,
             # 10 steps each.  `value` above is the metric's configuration only.
             del x, osc
@@ -791,7 +802,7 @@ def main():
                                "musical": time_config(syn.CFG4_PER_GPU, 1004, 10, 2, f0_kind="musical"),
                                "live_callback": live_callback_ms(),
                                "train_step": train_step_figures()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(shape)
             if "configs" in line:
                 line["configs"]["cfg1"].update(cfg1_cpu())

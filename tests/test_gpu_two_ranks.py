@@ -125,10 +125,11 @@ def test_overlapped_bucketed_reduction_equals_the_flat_one(rank_outputs):
 
 def test_bench_self_launches_two_ranks():
     """bench.py --gpus 2 with no WORLD_SIZE: the parent (GPU-free) starts two ranks under torch.distributed.run, both on
-    this box's one GPU (--one-device, gloo), small batch; rank 0 prints the one JSON line."""
+    this box's one GPU (--one-device, gloo), small batch; rank 0 prints the one JSON line.  --full: every rank's per-kernel
+    averages come from the passes after the timed region."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--batch", "16", "--backend", "gloo", "--one-device"], env=env, capture_output=True, text=True,
+                        "--batch", "16", "--backend", "gloo", "--one-device", "--full"], env=env, capture_output=True, text=True,
                        timeout=420)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
