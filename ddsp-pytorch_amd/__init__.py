@@ -22,8 +22,11 @@ from .spectral import griffinlim  # noqa: F401
 from . import style  # noqa: F401
 from .style import (normalize_audio, prepare_spectra, gram_matrix, FeatureExtractor, ContentLoss, StyleLoss,  # noqa: F401
                     style_transfer)
+from . import trainer  # noqa: F401
+from .trainer import DeviceBatches, PlateauRate, Trainer, gather_batch, load_checkpoint, latest_checkpoint  # noqa: F401
 from .training import MSSLoss, train_step, allreduce_gradients, OverlappedGradientReducer  # noqa: F401
 
 __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "Crepe", "F0Encoder", "LoudnessEncoder", "Encoder", "AutoEncoder", "AudioData", "PLHDataset", "load_audio", "example_geometry", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency", "griffinlim",
            "normalize_audio", "prepare_spectra", "gram_matrix", "FeatureExtractor", "ContentLoss", "StyleLoss", "style_transfer",
-           "synthetic"]
+           "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
+           "latest_checkpoint"]

@@ -165,14 +165,26 @@ class GraphedTrainStep:
       forward and the backward kernel, advanced by a node of the graph): every replay gets fresh noise, the same sequence as
       the eager steps; `step()` also advances the modules' host-side offsets by the same amount, so eager calls of the model
       between graphed steps continue the stream.
-    * fp32 or `amp_dtype=torch.bfloat16` (no GradScaler: fp16 needs its host-side decisions); every rank must hold rows.
+    * fp32 or `amp_dtype=torch.bfloat16` without a scaler; every rank must hold rows.
+    * `scaler=torch.amp.GradScaler("cuda")` (with `amp_dtype=torch.float16`: the reference's precision=16) puts the loss scaling
+      inside the replay: the scaled backward, the non-finite check, the taken-or-skipped update and the scale's growth / back-off
+      are all nodes of the graph, with no host read per step.  That needs an optimiser whose step takes the scale and the
+      found-inf flag as device tensors (`torch.optim.Adam(..., fused=True, capturable=True)`); any other raises.  Single rank only.
+    * `prologue`: a callable captured in front of the forward, e.g. the gather of the next batch into the static inputs
+      (trainer.DeviceBatches).  It is NOT run during the warm-up, which steps on the example batch: run it once eagerly before.
+      With `static_batch=True` the example batch's own tensors become the static inputs (the prologue writes them) instead of copies.
+    * A learning rate that changes between replays must live in a device tensor (`Adam(lr=torch.tensor(1e-3, device=...))`): a
+      Python float is a constant of the captured update.  `set_lr` writes that tensor.
     * The persistent GRU launches inside a graph are ordered by the graph only: do not run another recurrence on a second
       stream of the same device while a replay is in flight (DESIGN.md par. 9a).
     """
 
-    def __init__(self, model, loss_fn, optimizer, example_batch, group=None, amp_dtype=None, warmup: int = 3):
+    def __init__(self, model, loss_fn, optimizer, example_batch, group=None, amp_dtype=None, warmup: int = 3,
+                 scaler=None, prologue=None, static_batch: bool = False):
         import torch.distributed as dist
         self.model, self.loss_fn, self.opt, self.group, self.amp_dtype = model, loss_fn, optimizer, group, amp_dtype
+        self.scaler = scaler if scaler is not None and scaler.is_enabled() else None
+        self.prologue = prologue
         self.params = [p for p in model.parameters() if p.requires_grad]
         if not self.params or not self.params[0].is_cuda:
             raise _lib.DdspHipError("GraphedTrainStep needs the model on a GPU")
@@ -180,7 +192,15 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep needs a capturable optimiser, e.g. torch.optim.Adam(params, capturable=True)")
         dev = self.params[0].device
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        self.batch = {k: (v.detach().to(dev).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
+        if self.scaler is not None:
+            if self.world > 1:
+                raise ValueError("GraphedTrainStep: scaler= is single-rank only (the skip decision would have to follow the all-reduce)")
+            if not getattr(optimizer, "_step_supports_amp_scaling", False):
+                raise ValueError("GraphedTrainStep: scaler= needs an optimiser that takes the scale on the device, "
+                                 "e.g. torch.optim.Adam(params, fused=True, capturable=True)")
+        # (static_batch: the example's own CUDA tensors ARE the static inputs -- whoever fills them, e.g. the prologue, owns them)
+        self.batch = dict(example_batch) if static_batch else \
+            {k: (v.detach().to(dev).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         if next((v.shape[0] for v in self.batch.values() if torch.is_tensor(v)), 0) == 0:
             raise ValueError("GraphedTrainStep cannot capture an empty shard")
         self.noises = [m for m in model.modules() if isinstance(m, FilteredNoise) and m.rng == "device"]
@@ -192,17 +212,19 @@ class GraphedTrainStep:
         self._capture(dev, warmup)
 
     # one step in two halves (a collective sits between them when there is more than one rank)
-    def _forward_backward(self):
+    def _forward_backward(self, prologue: bool = False):
         for m, c in zip(self.noises, self.counters):
             m.counter, m._last_draws = c, 0
         try:
+            if prologue and self.prologue is not None:
+                self.prologue()
             if self.amp_dtype is not None:
                 dense.lowp_weights.refresh(self.amp_dtype)
             with torch.autocast("cuda", dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None):
                 audio = self.model(self.batch)
             dense.lowp_weights.release()               # (the copies the captured forward uses are refreshed by the graph itself)
             loss = self.loss_fn(audio.float(), self.batch)
-            loss.backward()
+            (self.scaler.scale(loss) if self.scaler is not None else loss).backward()
             self._draws = [m._last_draws for m in self.noises]     # host constants of the captured shape
             for m, c in zip(self.noises, self.counters):
                 if m._last_draws:                      # (0: the caller injected its own draw, the counter was not read)
@@ -212,6 +234,21 @@ class GraphedTrainStep:
             for m in self.noises:
                 m.counter = None
         return loss.detach()
+
+    def _update(self):
+        if self.scaler is not None:
+            self.scaler.step(self.opt)        # (a fused optimiser: unscale, found-inf and the skip happen inside its kernels)
+            self.scaler.update()
+        else:
+            self.opt.step()
+
+    def set_lr(self, value: float) -> None:
+        """A new learning rate for the following replays: written into the device tensor(s) the captured update reads."""
+        for g in self.opt.param_groups:
+            if not torch.is_tensor(g["lr"]) or not g["lr"].is_cuda:
+                raise ValueError("GraphedTrainStep.set_lr: the captured update holds this optimiser's Python-float learning rate as a "
+                                 "constant; construct it with lr=torch.tensor(value, device=...)")
+            g["lr"].fill_(float(value))
 
     def _reduce(self):
         import torch.distributed as dist
@@ -226,6 +263,10 @@ class GraphedTrainStep:
         had = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.opt.state.get(p, {}).items()}
                for g in self.opt.param_groups for p in g["params"]}
         counters = [c.clone() for c in self.counters]
+        sc = self.scaler
+        # (a scaler that has not scaled anything yet has no tensors: the warm-up creates them, from these initial values)
+        sc_state = None if sc is None else ((float(sc._scale), int(sc._growth_tracker)) if sc._scale is not None
+                                            else (sc._init_scale, sc._init_growth_tracker))
 
         def restore():
             with torch.no_grad():
@@ -240,6 +281,9 @@ class GraphedTrainStep:
                                 v.copy_(old) if old is not None else v.zero_()
                 for live_c, c in zip(self.counters, counters):
                     live_c.copy_(c)
+                if sc is not None:
+                    sc._scale.fill_(sc_state[0])
+                    sc._growth_tracker.fill_(sc_state[1])
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -249,16 +293,16 @@ class GraphedTrainStep:
                 self._forward_backward()
                 if self.world > 1:
                     self._reduce()
-                self.opt.step()
+                self._update()
         torch.cuda.current_stream(dev).wait_stream(side)
         restore()
         self.opt.zero_grad(set_to_none=True)          # the captured backward allocates the gradients inside the graph's pool
         self._graph = torch.cuda.CUDAGraph()
         self._graph_update = None
         with torch.cuda.graph(self._graph):
-            self.loss = self._forward_backward()
+            self.loss = self._forward_backward(prologue=True)
             if self.world == 1:
-                self.opt.step()
+                self._update()
         if self.world > 1:
             self._graph_update = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph_update, pool=self._graph.pool()):

@@ -435,6 +435,26 @@ size_t ddsp_griffinlim_workspace_bytes(long B, long T, int n_fft, int with_angle
 int ddsp_griffinlim(const float *mag, const float *angles, const float *window, const float *env, float *y, void *workspace,
                     size_t workspace_bytes, long B, long T, int n_fft, int hop, long L, int n_iter, float c, void *stream);
 
+/*
+ * The trainer's batch fetch from a device-resident training set (train/train.py:48: DataLoader(shuffle=True), collate, copy).
+ *
+ * ddsp_gather_batch  for each of n_arrays (<= DDSP_GATHER_MAX_ARRAYS) fp32 arrays: dst[a] [rows, row_floats[a]] row r <-
+ *                    src[a] [n_examples, row_floats[a]] row perm[*cursor + r].  src, dst and row_floats are HOST arrays of
+ *                    n_arrays entries (device addresses / lengths), read during the call; perm [perm_len] int64, cursor (one
+ *                    int64) and error (one 32-bit word) are DEVICE memory, read when the kernel runs -- so a captured call
+ *                    fetches the next batch at every replay.  With advance != 0 a second launch on the same stream then adds
+ *                    rows to *cursor.  All arrays are copied by ONE launch whose grid is sized by bytes; rows whose length is a
+ *                    multiple of 4 floats between 16-byte aligned bases move as 16-byte accesses, others as 4-byte ones.
+ *                    No bad index is ever dereferenced: a position *cursor + r outside [0, perm_len) sets
+ *                    DDSP_GATHER_BAD_CURSOR in *error, an example outside [0, n_examples) DDSP_GATHER_BAD_INDEX, and that row of
+ *                    every dst is zero-filled.  The caller clears *error and reads it when it synchronises anyway.
+ */
+#define DDSP_GATHER_MAX_ARRAYS 8
+#define DDSP_GATHER_BAD_INDEX 1
+#define DDSP_GATHER_BAD_CURSOR 2
+int ddsp_gather_batch(const void **src, void **dst, const long *row_floats, int n_arrays, const long *perm, long *cursor,
+                      long perm_len, long n_examples, int rows, int advance, unsigned *error, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
