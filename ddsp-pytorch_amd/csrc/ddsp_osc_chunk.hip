@@ -17,10 +17,16 @@
 //     sample in the flush, not once per lane and sample.
 //
 //   * Silent harmonics (above Nyquist, :31-32) are skipped per chunk: pass 1 records, per (row, chunk), the highest
-//     harmonic slot that is audible anywhere in the chunk; a wavefront walks 1/8, 1/4, 1/2, 3/4 or all of the K slots,
-//     and pass 2 orders the rows of every chunk index so that rows which stop at the same slot share a wavefront.
+//     harmonic number that is audible anywhere in the chunk; a wavefront walks 1/8, 1/4, 1/2, 3/4 or all of the root slots
+//     (with the derived slots they feed; the plan says up to which harmonic each of those walks suffices), and pass 2
+//     orders the rows of every chunk index so that rows which stop at the same slot share a wavefront.
 //
-// Launches: osc_chunk_totals_kernel (rows w / amp, chunk totals, highest audible slot per row and chunk),
+//   * Only some of a lane's K slots -- KR ROOT slots -- walk the increment / fp64 accumulate chain.  The other KD = K - KR are
+//     DERIVED: the unwrapped fp32 phase of harmonic 2^t * r is bit for bit 2^t times that of harmonic r, so a
+//     derived slot multiplies the rounded phase of a root slot of its lane by 2^t.  Which harmonic sits in which slot is the
+//     slot plan (ddsp_osc_plan.h), computed on the host and handed over in the kernel arguments; KR = K is the all-roots mapping.
+//
+// Launches: osc_chunk_totals_kernel (rows w / amp, chunk totals of the root slots, highest audible harmonic per row and chunk),
 // osc_chunk_scan_kernel (exclusive scan of the chunk totals along the row, flag reset), osc_chunk_synth_kernel
 // (audio; a wavefront that has to decline its chunk -- phases beyond the fast modulo's exact range, negative or NaN
 // increments -- walks it a second time with the exact modulo: DDSP_CHUNK_INLINE_REPAIR).
@@ -32,10 +38,14 @@
 #include <atomic>
 #include <mutex>
 #include <stdlib.h>
+#include <vector>
 
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
 #include "ddsp_osc_common.h"
+#include "ddsp_osc_plan.h"
+
+#include <stddef.h>
 
 using namespace ddsp_osc;
 
@@ -94,10 +104,34 @@ __device__ __forceinline__ double ldd(const double *base, unsigned idx)
     return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (size_t)(idx * 8u));
 }
 
+// Kernel arguments of the chunked kernels.  The slot plan is read per lane (lane j of a row group, slot m: element j*K + m)
+// straight from the kernel-argument segment, never through the by-value copy: a per-lane index into that would move the
+// whole table to private memory.
+struct ChunkArgs {
+    OscParams p;
+    PlanTable t;
+};
+__device__ __forceinline__ const PlanTable *plan_table()
+{
+    return reinterpret_cast<const PlanTable *>((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(ChunkArgs, t));
+}
+
+// derived_parent(K, .) as a table, so that an unrolled loop's index folds to a register name
 template <int K>
+struct ParentTable {
+    int v[kPlanMaxK];
+    constexpr ParentTable() : v()
+    {
+        for (int d = 0; d < kPlanMaxK; ++d) v[d] = derived_parent(K, d);
+    }
+};
+#define DDSP_PARENT(K, d) (par.v[d])   // with `constexpr ParentTable<K> par` in scope
+
+// slots [0, KR) are roots, [KR, K) derived (derived slot d = slot KR + d reads root slot DDSP_PARENT(K, d))
+template <int K, int KR>
 struct ChunkState {
-    double acc[K];
-    float x0[K], x1[K];  // increments of the segment's bracketing rows
+    double acc[KR];
+    float x0[KR], x1[KR];  // increments of the segment's bracketing rows (root slots)
     float a1[K], da[K];  // amplitude of the NEWER row and (newer - older): A(n) = a1 - w0 * da, so that crossing into the next
                          // segment needs the new row only (the older amplitude is the a1 already held)   (synth only)
 };
@@ -135,15 +169,22 @@ __device__ __forceinline__ void segment_rows(int s, int T, int &r0, int &r1)
     r1 = s == 0 ? min(1, T - 1) : min(s, T - 1);
 }
 
-// ---- production walk: samples [n_beg, n_end) of the current segment, the lane's first KL harmonic slots ---------
+// ---- production walk: samples [n_beg, n_end) of the current segment, the lane's first KLR root slots and KLD derived ones ----
+// (the derived slots those roots feed: class_derived).  Stages 1-5 -- increment, fp64 accumulate, rounding -- run over the roots,
+// one multiply by 2^t forms each derived phase, every later stage runs over all KL = KLR + KLD slots.
 // NS samples per iteration (a stage then covers NS*KL independent instructions); QKEEP: the modulo's quotient is
 // computed on even samples and reused on the odd ones (increments < kReuseMaxInc, checked by the caller).
 // Every lane parks its partial sum in LDS; after each 32nd sample the G lanes of a row group each sum the partials of
 // 32/G samples, apply the loudness and store: one whole 128-byte line per row.
-template <int K, int KL, int NS, int QMODE>
-__device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K> &st, float *ystage, float *yrow, int j,
-                                           bool active, int i_abs, int n_beg, int n_end, bool clamp0, float L0, float L1, int slot)
+template <int K, int KR, int KLR, int NS, int QMODE>
+__device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR> &st, const float (&fac)[K - KR + 1], float *ystage,
+                                           float *yrow, int j, bool active, int i_abs, int n_beg, int n_end, bool clamp0, float L0,
+                                           float L1, int slot)
 {
+    constexpr int KLD = KR < K ? class_derived(K, KLR) : 0;   // the derived slots the walked roots feed
+    constexpr int KL = KLR + KLD;                             // v[.][m]: m < KLR root slot m, else derived slot m - KLR
+#define DDSP_SLOT(m) ((m) < KLR ? (m) : KR + ((m) - KLR))
+    constexpr ParentTable<K> par;
     const int G = 1 << p.logG, per = 32 >> p.logG;
     float lam, dlam;
     segment_lambda(p, n_beg, clamp0, lam, dlam);
@@ -172,23 +213,23 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K> &st
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = w1[e] * st.x1[m];
+            for (int m = 0; m < KLR; ++m) v[e][m] = w1[e] * st.x1[m];
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = __fmaf_rn(w0[e], st.x0[m], v[e][m]);   // fl32(fma(w0,x[i0],fl32(w1*x[i1])))
+            for (int m = 0; m < KLR; ++m) v[e][m] = __fmaf_rn(w0[e], st.x0[m], v[e][m]);   // fl32(fma(w0,x[i0],fl32(w1*x[i1])))
         DDSP_STAGE_END();
-        double d[NS][KL];
+        double d[NS][KLR];
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) d[e][m] = (double)v[e][m];
+            for (int m = 0; m < KLR; ++m) d[e][m] = (double)v[e][m];
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) {
+            for (int m = 0; m < KLR; ++m) {
                 st.acc[m] += d[e][m];                                                     // :41 double accumulator
                 d[e][m] = st.acc[m];
             }
@@ -196,8 +237,15 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K> &st
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = (float)d[e][m];                        // ... rounded to fp32 per sample
+            for (int m = 0; m < KLR; ++m) v[e][m] = (float)d[e][m];                       // ... rounded to fp32 per sample
         DDSP_STAGE_END();
+        if (KLD > 0) {   // derived slots: the root's rounded phase times 2^t, exact
+#pragma unroll
+            for (int e = 0; e < NS; ++e)
+#pragma unroll
+                for (int m = KLR; m < KL; ++m) v[e][m] = fac[m - KLR] * v[e][DDSP_PARENT(K, m - KLR)];
+            DDSP_STAGE_END();
+        }
         // P - q*2pi32 is exact in fp32 for q = rint(P/2pi32) < 2^21; nearest multiple instead of floor
         float q[NS][KL];
         const bool fresh = QMODE != 1 || (n & 1) == 0;   // wave-uniform
@@ -243,7 +291,7 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K> &st
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) q[e][m] = __fmaf_rn(-w0[e], st.da[m], st.a1[m]);
+            for (int m = 0; m < KL; ++m) q[e][m] = __fmaf_rn(-w0[e], st.da[DDSP_SLOT(m)], st.a1[DDSP_SLOT(m)]);
         DDSP_STAGE_END();
         float s0[NS], s1[NS];
 #pragma unroll
@@ -305,24 +353,33 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K> &st
             DDSP_WAVE_ORDER();
         }
     }
+#undef DDSP_SLOT
 }
 
 // Reference-exact walk of the same samples: libm fmodf modulo, per-sample cross-lane sum, direct stores.
-template <int K>
-__device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<K> &st, float *yrow, int j, bool active,
-                                                 int i_abs, int n_beg, int n_end, bool clamp0, float L0, float L1)
+template <int K, int KR>
+__device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<K, KR> &st, const float (&fac)[K - KR + 1], float *yrow,
+                                                 int j, bool active, int i_abs, int n_beg, int n_end, bool clamp0, float L0, float L1)
 {
+    constexpr ParentTable<K> par;
     float lam, dlam;
     segment_lambda(p, n_beg, clamp0, lam, dlam);
     for (int n = n_beg; n < n_end; ++n) {
         const float w1 = lam, w0 = 1.0f - lam;
         lam += dlam;
         float sum = 0.0f;
+        float ph[K];
 #pragma unroll
-        for (int m = 0; m < K; ++m) {
+        for (int m = 0; m < KR; ++m) {
             const float inc = __fmaf_rn(w0, st.x0[m], w1 * st.x1[m]);
             st.acc[m] += (double)inc;
-            const float r = remainder_two_pi((float)st.acc[m]);   // :42, exact
+            ph[m] = (float)st.acc[m];
+        }
+#pragma unroll
+        for (int m = KR; m < K; ++m) ph[m] = fac[m - KR] * ph[DDSP_PARENT(K, m - KR)];
+#pragma unroll
+        for (int m = 0; m < K; ++m) {
+            const float r = remainder_two_pi(ph[m]);   // :42, exact
             const float sn = __builtin_amdgcn_sinf(r * kRevPerRad);
             sum = __fmaf_rn(__fmaf_rn(-w0, st.da[m], st.a1[m]), sn, sum);
         }
@@ -331,7 +388,7 @@ __device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<
     }
 }
 
-// frame totals' chain only (increment, fp64 accumulate) over all K slots
+// frame totals' chain only (increment, fp64 accumulate) over the K root slots it is given
 template <int K>
 __device__ __forceinline__ void walk_totals(const OscParams &p, double (&acc)[K], const float (&x0)[K], const float (&x1)[K],
                                             int n_beg, int n_end, bool clamp0, int slot)
@@ -364,17 +421,18 @@ __device__ __forceinline__ void walk_totals(const OscParams &p, double (&acc)[K]
     }
 }
 
-// OR over the G lanes of a row group
-__device__ __forceinline__ unsigned group_or(unsigned v, int logG)
+// max over the G lanes of a row group
+__device__ __forceinline__ int group_max(int v, int logG)
 {
-    for (int o = 1; o < (1 << logG); o <<= 1) v |= (unsigned)__shfl_xor((int)v, o);
+    for (int o = 1; o < (1 << logG); o <<= 1) v = max(v, __shfl_xor(v, o));
     return v;
 }
 
-// ---- pass 1: rows, chunk totals, highest audible slot ----------------------------------------------------------
-template <int K>
-__global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(OscParams p)
+// ---- pass 1: rows, chunk totals of the root slots, highest audible harmonic ------------------------------------------
+template <int K, int KR>
+__global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(ChunkArgs args)
 {
+    const OscParams &p = args.p;
     const int wt = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (wt >= p.RB * p.NC) return;
     Task k = decode_task(p, wt);
@@ -382,20 +440,27 @@ __global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(
     const long rowbase = (long)k.b * p.T;
     const int i_beg = k.i;
     const int slot = wave_slot();
-    unsigned nz = 0u;   // this lane's slots with a non-zero amplitude (NaN counts) at any row the chunk interpolates from
+    int hs[K];          // this lane's slot plan: 0-based harmonic of every slot (padding: kNoHarmonic >= H)
+    {
+        const PlanTable *tab = plan_table();
+#pragma unroll
+        for (int m = 0; m < K; ++m) hs[m] = tab->h[k.j * K + m];
+    }
+    int hmax = 0;       // highest harmonic number of this lane with a non-zero amplitude (NaN counts) at any row the chunk interpolates from
 
-    // row r of this lane's batch row: increments (:26-35) and masked, normalised amplitudes (:31-33); stored by the
-    // chunk in which the row first becomes the NEWER row of a segment (every row exactly once)
-    auto make_row = [&](int r, float (&w)[K]) {
+    // row r of this lane's batch row: increments (:26-35) and masked, normalised amplitudes (:31-33) of EVERY slot; stored by the
+    // chunk in which the row first becomes the NEWER row of a segment (every row exactly once).  The root slots' increments
+    // come back in w.
+    auto make_row = [&](int r, float (&w)[KR]) {
         const float fb = p.f0[rowbase + r];
         const unsigned crow = ((unsigned)k.b * p.T + r) * p.H;
         float a0[K];
         float s = 0.0f;
 #pragma unroll
-        for (int m = 0; m < K; ++m) a0[m] = ldf(p.c, crow + min(k.j + m * G, p.H - 1));   // unconditional, inside the caller's tensor
+        for (int m = 0; m < K; ++m) a0[m] = ldf(p.c, crow + min(hs[m], p.H - 1));   // unconditional, inside the caller's tensor
 #pragma unroll
         for (int m = 0; m < K; ++m) {
-            const int h = k.j + m * G;
+            const int h = hs[m];
             const bool ok = h < p.H;
             const float hz = (float)(h + 1) * fb;
             a0[m] = (ok && !(hz > p.nyquist)) ? a0[m] : 0.0f;     // :31-32 strict >, integer Nyquist
@@ -407,55 +472,55 @@ __global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(
         const bool own = k.active && seg_start >= i_beg && seg_start < k.i_end;
 #pragma unroll
         for (int m = 0; m < K; ++m) {
-            const int h = k.j + m * G;
+            const int h = hs[m];
             const bool ok = h < p.H;
-            w[m] = ok ? frame_increment(h, fb, p.sr) : 0.0f;
+            const float wv = ok ? frame_increment(h, fb, p.sr) : 0.0f;
+            if (m < KR) w[m < KR ? m : 0] = wv;
             const float amp = ok ? a0[m] * rs : 0.0f;
-            if (amp != 0.0f) nz |= 1u << m;
+            if (amp != 0.0f) hmax = max(hmax, h + 1);
             if (ok && own) {
-                p.w[crow + h] = w[m];
+                p.w[crow + h] = wv;
                 p.amp[crow + h] = amp;
             }
         }
     };
 
-    float x0[K], x1[K];
+    float x0[KR], x1[KR];
     int r0, r1;
     segment_rows(k.s, p.T, r0, r1);
     make_row(r0, x0);
     make_row(r1, x1);
-    double acc[K];
+    double acc[KR];
 #pragma unroll
-    for (int m = 0; m < K; ++m) acc[m] = 0.0;
+    for (int m = 0; m < KR; ++m) acc[m] = 0.0;
     while (true) {
         const int n_end = min(p.R, k.n + (k.i_end - k.i));
-        walk_totals<K>(p, acc, x0, x1, k.n, n_end, k.s == 0, slot);
+        walk_totals<KR>(p, acc, x0, x1, k.n, n_end, k.s == 0, slot);
         k.i += n_end - k.n;
         if (k.i >= k.i_end) break;
         ++k.s; k.n = 0;
         if (k.s >= 2) {
 #pragma unroll
-            for (int m = 0; m < K; ++m) x0[m] = x1[m];
+            for (int m = 0; m < KR; ++m) x0[m] = x1[m];
             if (k.s <= p.T - 1) make_row(k.s, x1);
         }
     }
-    nz = group_or(nz, p.logG);
+    hmax = group_max(hmax, p.logG);
     if (k.active) {
-        double *cp = p.ctot + ((long)k.b * p.NC + k.c) * p.H;
+        // one column per root slot: column m*G + j (the all-roots mapping: the harmonic itself)
+        double *cp = p.ctot + ((long)k.b * p.NC + k.c) * p.HC + k.j;
 #pragma unroll
-        for (int m = 0; m < K; ++m) {
-            const int h = k.j + m * G;
-            if (h < p.H) cp[h] = acc[m];
-        }
-        if (k.j == 0) p.rlive[(long)k.b * p.NC + k.c] = nz ? 32 - __builtin_clz(nz) : 0;
+        for (int m = 0; m < KR; ++m)
+            if (hs[m] < p.H) cp[m * G] = acc[m];
+        if (k.j == 0) p.rlive[(long)k.b * p.NC + k.c] = hmax;
     }
 }
 
 // ---- pass 2: exclusive scan of the chunk totals along the row; rows ordered by audible slots; flag reset --------------
 // The first nscan_blocks workgroups scan the columns (exact fp64 sums, so the order of the additions is free); the wavefronts
 // of the others take one chunk index each: perm[c][.] = the batch rows ordered by the class of their highest
-// audible slot in chunk c (all K slots first, then 3/4, 1/2, 1/4, 1/8), so that the rows a synth wavefront walks together
-// stop at the same slot; entries past B are -1.
+// audible harmonic in chunk c (all slots first, then 3/4, 1/2, 1/4, 1/8 of the root slots: p.cls_max), so that the rows a
+// synth wavefront walks together stop at the same slot; entries past B are -1.
 __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int nscan_blocks, int Q)
 {
     __shared__ double seg_tot[8][64];
@@ -467,11 +532,11 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
     if ((int)blockIdx.x < nscan_blocks) {
         // 64 columns per workgroup, coalesced along h; the chunk range is cut into Q <= 8 segments, one per wavefront: first the
         // segment totals (independent loads), then each segment's exclusive scan starting from the totals before it
-        const long ncol = (long)p.B * p.H;
+        const long ncol = (long)p.B * p.HC;
         const long idx = (long)blockIdx.x * 64 + lane;
         const bool live = idx < ncol && q < Q;
-        const int b = live ? (int)(idx / p.H) : 0, h = live ? (int)(idx - (long)b * p.H) : 0;
-        double *col = p.ctot + (long)b * p.NC * p.H + h;
+        const int b = live ? (int)(idx / p.HC) : 0, h = live ? (int)(idx - (long)b * p.HC) : 0;
+        double *col = p.ctot + (long)b * p.NC * p.HC + h;
         const int per = (p.NC + Q - 1) / Q, c_beg = q * per, c_end = min(c_beg + per, p.NC);
         if (per <= 32) {
             // the whole segment stays in registers between the two steps: one read, one write
@@ -479,7 +544,7 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
             double tot = 0.0;
 #pragma unroll
             for (int i = 0; i < 32; ++i) {
-                v[i] = (live && c_beg + i < c_end) ? col[(long)(c_beg + i) * p.H] : 0.0;
+                v[i] = (live && c_beg + i < c_end) ? col[(long)(c_beg + i) * p.HC] : 0.0;
                 tot += v[i];
             }
             seg_tot[q][lane] = tot;
@@ -489,7 +554,7 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
 #pragma unroll
             for (int i = 0; i < 32; ++i)
                 if (live && c_beg + i < c_end) {
-                    col[(long)(c_beg + i) * p.H] = run;
+                    col[(long)(c_beg + i) * p.HC] = run;
                     run += v[i];
                 }
             return;
@@ -499,7 +564,7 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
             for (int s0 = c_beg; s0 < c_end; s0 += 16) {
                 double v[16];
 #pragma unroll
-                for (int i = 0; i < 16; ++i) v[i] = (s0 + i < c_end) ? col[(long)(s0 + i) * p.H] : 0.0;
+                for (int i = 0; i < 16; ++i) v[i] = (s0 + i < c_end) ? col[(long)(s0 + i) * p.HC] : 0.0;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) tot += v[i];
             }
@@ -512,11 +577,11 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
             for (int s0 = c_beg; s0 < c_end; s0 += 16) {
                 double v[16];
 #pragma unroll
-                for (int i = 0; i < 16; ++i) v[i] = (s0 + i < c_end) ? col[(long)(s0 + i) * p.H] : 0.0;
+                for (int i = 0; i < 16; ++i) v[i] = (s0 + i < c_end) ? col[(long)(s0 + i) * p.HC] : 0.0;
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
                     if (s0 + i < c_end) {
-                        col[(long)(s0 + i) * p.H] = run;
+                        col[(long)(s0 + i) * p.HC] = run;
                         run += v[i];
                     }
             }
@@ -528,12 +593,10 @@ __global__ void __launch_bounds__(512) osc_chunk_scan_kernel(OscParams p, int ns
     if (c >= p.NC) return;
     const int Bpad = p.RB * (64 >> p.logG);
     int *out = p.perm + (long)c * Bpad;
-    const int K = p.K;
-    const int lim[4] = {(3 * K + 3) / 4, (K + 1) / 2, (K + 3) / 4, (K + 7) / 8};   // osc_chunk_synth_kernel: KT, KH, KQ, KE
     auto cls_of = [&](int ml) {   // 0 = walks every slot ... 4 = an eighth; -1 = no such row
         if (ml < 0) return -1;
         int q = 0;
-        while (q < 4 && ml <= lim[q]) ++q;
+        while (q < 4 && ml <= p.cls_max[q]) ++q;   // osc_chunk_synth_kernel: KT, KH, KQ, KE root slots
         return q;
     };
     int base[5], cnt[5] = {0, 0, 0, 0, 0};
@@ -574,12 +637,22 @@ extern "C" int ddsp_osc_read_stamps(long *host, int ntasks)
 #ifndef DDSP_CHUNK_INLINE_REPAIR
 #define DDSP_CHUNK_INLINE_REPAIR 1
 #endif
-template <int K, bool EXACT>
-__global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_synth_kernel(OscParams p)
+template <int K, int KR, bool EXACT>
+__global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_synth_kernel(ChunkArgs args)
 {
+    const OscParams &p = args.p;
     extern __shared__ float ystage[];   // [32][kRow] (fast kernel only)
-    constexpr int KE = (K + 7) / 8, KQ = (K + 3) / 4, KH = (K + 1) / 2, KT = (3 * K + 3) / 4;   // walk lengths below K
+    constexpr int KD = K - KR;
+    constexpr ParentTable<K> par;
+    // root slots walked by the classes below all (ddsp_osc_plan.h: class_prefix; each takes the derived slots its roots feed)
+    constexpr int KE = class_prefix(KR, 3), KQ = class_prefix(KR, 2), KH = class_prefix(KR, 1), KT = class_prefix(KR, 0);
     const int ntasks = p.RB * p.NC;
+    const PlanTable *tab = plan_table();
+    const int jj = (threadIdx.x & 63) & ((1 << p.logG) - 1);
+    float fac[KD + 1];                  // derived slot d: 2^t
+#pragma unroll
+    for (int d = 0; d < KD; ++d) fac[d] = (float)(1u << tab->shift[jj * K + KR + d]);
+    fac[KD] = 1.0f;
     int wt = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (EXACT && *p.redo_flag == 0) return;
     for (; wt < ntasks; wt += gridDim.x * 4) {
@@ -600,22 +673,22 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
         const int G = 1 << p.logG;
         const long rowbase = (long)k.b * p.T;
         float *yrow = p.y + (long)k.b * p.T * p.R;
-        ChunkState<K> st;
+        ChunkState<K, KR> st;
         const int slot = exact ? 0 : wave_slot();
         bool bad = false;   // per lane: increments negative / NaN, phases beyond the fast modulo's range
-        // issues them back to back instead of one exec-masked branch per element)
-        // (padded slots, h >= H, read whatever follows inside the scratch buffer and are zeroed by a select: every load is
+        // (padded slots read a column inside the scratch buffer all the same and are zeroed by a select: every load is
         // unconditional, so the compiler issues them back to back instead of one exec-masked branch per element)
-        const unsigned cbase = ((unsigned)k.b * p.NC + k.c) * p.H + k.j;
+        const unsigned cbase = ((unsigned)k.b * p.NC + k.c) * p.HC + k.j;
 #pragma unroll
-        for (int m = 0; m < K; ++m) {
+        for (int m = 0; m < KR; ++m) {
             const double v = ldd(p.ctot, cbase + (unsigned)(m * G));
-            st.acc[m] = (k.j + m * G < p.H) ? v : 0.0;
+            st.acc[m] = (tab->h[k.j * K + m] < p.H) ? v : 0.0;
             bad = bad || !(st.acc[m] >= 0.0);
         }
-        // slots above the highest audible one of the wavefront's rows are silent for the whole chunk and their phase feeds
-        // nothing else (the next chunk starts from the scanned totals): walk 1/8, 1/4, 1/2, 3/4 or all of the K slots
-        int mlive = K;
+        // harmonics above the highest audible one of the wavefront's rows are silent for the whole chunk and their phase feeds
+        // nothing else (the next chunk starts from the scanned totals): walk 1/8, 1/4, 1/2, 3/4 or all of the root slots, with the
+        // derived slots they feed (p.cls_max: the highest harmonic number each of those walks still holds, from the slot plan)
+        int mlive = p.H;
         if (!exact) {
             mlive = p.rlive[(long)k.b * p.NC + k.c];
 #pragma unroll
@@ -626,21 +699,28 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
         segment_rows(k.s, p.T, r0, r1);
         float L0, L1;
         auto load_rows = [&](int ra, int rb2, bool first) {
-            const unsigned o0 = ((unsigned)k.b * p.T + ra) * p.H + k.j, o1 = ((unsigned)k.b * p.T + rb2) * p.H + k.j;
-            float t0[K], t1[K], u0[K], u1[K];
+            const unsigned o0 = ((unsigned)k.b * p.T + ra) * p.H, o1 = ((unsigned)k.b * p.T + rb2) * p.H;
+            float t0[KR], t1[KR], u0[K], u1[K];
+            int hs[K];      // the lane's slot plan, read again at every row: cheaper than K registers held through the walk
+#pragma unroll
+            for (int m = 0; m < K; ++m) hs[m] = tab->h[k.j * K + m];
 #pragma unroll
             for (int m = 0; m < K; ++m) {
-                const unsigned g = (unsigned)(m * G);
-                t0[m] = first ? ldf(p.w, o0 + g) : 0.0f;
-                t1[m] = ldf(p.w, o1 + g);
+                const unsigned g = (unsigned)min(hs[m], p.H - 1);
+                if (m < KR) {
+                    t0[m < KR ? m : 0] = first ? ldf(p.w, o0 + g) : 0.0f;
+                    t1[m < KR ? m : 0] = ldf(p.w, o1 + g);
+                }
                 u0[m] = first ? ldf(p.amp, o0 + g) : 0.0f;
                 u1[m] = ldf(p.amp, o1 + g);
             }
 #pragma unroll
             for (int m = 0; m < K; ++m) {
-                const bool ok = k.j + m * G < p.H;
-                if (first) st.x0[m] = ok ? t0[m] : 0.0f;
-                st.x1[m] = ok ? t1[m] : 0.0f;
+                const bool ok = hs[m] < p.H;
+                if (m < KR) {
+                    if (first) st.x0[m < KR ? m : 0] = ok ? t0[m < KR ? m : 0] : 0.0f;
+                    st.x1[m < KR ? m : 0] = ok ? t1[m < KR ? m : 0] : 0.0f;
+                }
                 const float older = first ? (ok ? u0[m] : 0.0f) : st.a1[m];   // (after the first segment: the row already held)
                 st.a1[m] = ok ? u1[m] : 0.0f;
                 st.da[m] = st.a1[m] - older;
@@ -654,7 +734,7 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
         if (DDSP_CHUNK_STAMPS == 2) {   // (forces the first rows to have arrived: the prologue's length)
             float chk = 0.0f;
 #pragma unroll
-            for (int m = 0; m < K; ++m) chk += st.x1[m] + st.da[m];
+            for (int m = 0; m < KR; ++m) chk += st.x1[m] + st.da[m];
             if (__any(chk == 123456.0f)) bad = true;
             stamp_walk = wall_clock64();
         }
@@ -664,38 +744,44 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
             const bool clamp0 = k.s == 0;
             bool big = false;
 #pragma unroll
-            for (int m = 0; m < K; ++m) {
+            for (int m = 0; m < KR; ++m) {
                 bad = bad || !(st.x0[m] >= 0.0f) || !(st.x1[m] >= 0.0f);
                 big = big || !(st.x0[m] < kReuseMaxInc) || !(st.x1[m] < kReuseMaxInc);
             }
+#pragma unroll
+            for (int d = 0; d < KD; ++d)   // (a positive factor leaves the sign / NaN check as it is)
+                big = big || !(fac[d] * st.x0[DDSP_PARENT(K, d)] < kReuseMaxInc) || !(fac[d] * st.x1[DDSP_PARENT(K, d)] < kReuseMaxInc);
             if (exact) {
-                walk_synth_exact<K>(p, st, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1);
-            } else if (mlive <= KE && KE < KQ) {
-                walk_synth<K, KE, 4, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
-            } else if (mlive <= KQ && KQ < KH) {
-                walk_synth<K, KQ, 4, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
-            } else if (mlive <= KH && KH < KT) {
-                walk_synth<K, KH, 2, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
-            } else if (mlive <= KT && KT < K) {
-                walk_synth<K, KT, 1, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth_exact<K, KR>(p, st, fac, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1);
+            } else if (mlive <= p.cls_max[3] && KE < KQ) {
+                walk_synth<K, KR, KE, 4, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+            } else if (mlive <= p.cls_max[2] && KQ < KH) {
+                walk_synth<K, KR, KQ, 4, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+            } else if (mlive <= p.cls_max[1] && KH < KT) {
+                walk_synth<K, KR, KH, 2, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+            } else if (mlive <= p.cls_max[0] && KT < KR) {
+                walk_synth<K, KR, KT, 1, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else if (!__any(big)) {
-                walk_synth<K, K, 1, 1>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KR, 1, 1>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else {
-                walk_synth<K, K, 1, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KR, 1, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             }
             k.i += n_end - k.n;
             if (k.i >= k.i_end) break;
             ++k.s; k.n = 0;
             if (k.s >= 2) {
 #pragma unroll
-                for (int m = 0; m < K; ++m) st.x0[m] = st.x1[m];
+                for (int m = 0; m < KR; ++m) st.x0[m] = st.x1[m];
                 segment_rows(k.s, p.T, r0, r1);
                 load_rows(r0, r1, false);
             }
         }
         if (!exact) {
 #pragma unroll
-            for (int m = 0; m < K; ++m) bad = bad || !(st.acc[m] < (double)kFastPhaseLimit);
+            for (int m = 0; m < KR; ++m) bad = bad || !(st.acc[m] < (double)kFastPhaseLimit);
+            // (the fast modulo's range holds for a derived slot when it holds for 2^t times its root's phase)
+#pragma unroll
+            for (int d = 0; d < KD; ++d) bad = bad || !((double)fac[d] * st.acc[DDSP_PARENT(K, d)] < (double)kFastPhaseLimit);
             const bool redo = __any(bad);
             if (DDSP_CHUNK_INLINE_REPAIR && redo) { exact = true; continue; }
             if ((threadIdx.x & 63) == 0) {
@@ -723,7 +809,7 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct Residency { int cus, wg_per_cu; };
 
-template <int K>
+template <int K, int KR>
 hipError_t synth_residency(Residency *out)
 {
     static std::mutex mu;
@@ -737,7 +823,7 @@ hipError_t synth_residency(Residency *out)
         int cus = 0, nb = 0;
         e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, osc_chunk_synth_kernel<K, false>, 256, sizeof(float) * 32 * kRow);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, osc_chunk_synth_kernel<K, KR, false>, 256, sizeof(float) * 32 * kRow);
         if (e != hipSuccess) return e;
         if (cus <= 0 || nb <= 0) return hipErrorInvalidValue;
         cache[dev].cus = cus;
@@ -745,6 +831,28 @@ hipError_t synth_residency(Residency *out)
     }
     *out = cache[dev];
     return hipSuccess;
+}
+
+// The slot plan of (H, K, G): derived slots where the planner packs K's shape, else the all-roots mapping -- which
+// DDSP_OSC_CHUNK_ALL_ROOTS=1 forces under DDSP_TEST_HOOKS=1 (the A/B baseline and the tests' comparison arm).
+const SlotPlan &slot_plan(int H, int K, int G)
+{
+    struct Entry { bool all_roots; SlotPlan pl; };
+    static std::mutex mu;
+    static std::vector<Entry *> cache;   // (plans live as long as the library)
+    bool all_roots = false;
+    if (ddsp_hooks_on()) {
+        const char *e = getenv("DDSP_OSC_CHUNK_ALL_ROOTS");
+        all_roots = e && atoi(e) != 0;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (const Entry *en : cache)
+        if (en->pl.H == H && en->pl.K == K && en->pl.G == G && en->all_roots == all_roots) return en->pl;
+    Entry *en = new Entry;
+    en->all_roots = all_roots;
+    if (all_roots || !plan_slots(H, K, G, en->pl)) plan_all_roots(H, K, G, en->pl);
+    cache.push_back(en);
+    return en->pl;
 }
 
 }  // namespace
@@ -813,8 +921,11 @@ template <int K>
 hipError_t chunk_geometry(OscParams &p, Residency *res_out)
 {
     Residency res;
-    hipError_t e = synth_residency<K>(&res);
+    const SlotPlan &pl = slot_plan(p.H, K, 1 << p.logG);
+    hipError_t e = pl.KD ? synth_residency<K, plan_roots(K)>(&res) : synth_residency<K, K>(&res);
     if (e != hipSuccess) return e;
+    p.HC = pl.KD ? pl.KR << p.logG : p.H;   // columns of the chunk totals: one per root slot (all roots: the harmonics)
+    for (int q = 0; q < 4; ++q) p.cls_max[q] = pl.cls_max[q];
     const int GPW = 64 >> p.logG;
     p.RB = (p.B + GPW - 1) / GPW;
     p.lgR = 0;
@@ -862,6 +973,32 @@ void carve_chunk_scratch(OscParams &p, void *scratch)
     p.redo_flag = (int *)((char *)p.redo + align256((size_t)p.RB * p.NC * sizeof(int)));
 }
 
+template <int K, int KR>
+hipError_t launch_plan(const OscParams &p, const SlotPlan &pl, hipStream_t s)
+{
+    ChunkArgs args;
+    args.p = p;
+    args.t = pl.t;
+    const long tasks = (long)p.RB * p.NC;
+    const unsigned grid = (unsigned)((tasks + 3) / 4);
+    int slot = ddsp_prof::begin(ddsp_prof::TOTALS, s);
+    hipLaunchKernelGGL((osc_chunk_totals_kernel<K, KR>), dim3(grid), dim3(256), 0, s, args);
+    ddsp_prof::end(slot, s);
+    slot = ddsp_prof::begin(ddsp_prof::SCAN, s);
+    const long nscan_blocks = ((long)p.B * p.HC + 63) / 64;
+    const int Q = p.NC > 128 ? 8 : (p.NC > 64 ? 4 : (p.NC > 32 ? 2 : 1));   // <= 32 chunks per wavefront up to 256 chunks: the register form
+    hipLaunchKernelGGL(osc_chunk_scan_kernel, dim3((unsigned)(nscan_blocks + (p.NC + Q - 1) / Q)), dim3(64 * Q), 0, s, p, (int)nscan_blocks, Q);   // one wavefront per segment
+    ddsp_prof::end(slot, s);
+    slot = ddsp_prof::begin(ddsp_prof::SYNTH, s);
+    hipLaunchKernelGGL((osc_chunk_synth_kernel<K, KR, false>), dim3(grid), dim3(256), sizeof(float) * 32 * kRow, s, args);
+    ddsp_prof::end(slot, s);
+    if (!DDSP_CHUNK_INLINE_REPAIR) {
+        const unsigned rgrid = grid < 256u ? grid : 256u;
+        hipLaunchKernelGGL((osc_chunk_synth_kernel<K, KR, true>), dim3(rgrid), dim3(256), 0, s, args);
+    }
+    return hipGetLastError();
+}
+
 template <int K>
 hipError_t launch_chunked(OscParams p, void *scratch, hipStream_t s)
 {
@@ -869,25 +1006,8 @@ hipError_t launch_chunked(OscParams p, void *scratch, hipStream_t s)
     hipError_t e = chunk_geometry<K>(p, &res);
     if (e != hipSuccess) return e;
     carve_chunk_scratch(p, scratch);
-
-    const long tasks = (long)p.RB * p.NC;
-    const unsigned grid = (unsigned)((tasks + 3) / 4);
-    int slot = ddsp_prof::begin(ddsp_prof::TOTALS, s);
-    hipLaunchKernelGGL((osc_chunk_totals_kernel<K>), dim3(grid), dim3(256), 0, s, p);
-    ddsp_prof::end(slot, s);
-    slot = ddsp_prof::begin(ddsp_prof::SCAN, s);
-    const long nscan_blocks = ((long)p.B * p.H + 63) / 64;
-    const int Q = p.NC > 128 ? 8 : (p.NC > 64 ? 4 : (p.NC > 32 ? 2 : 1));   // <= 32 chunks per wavefront up to 256 chunks: the register form
-    hipLaunchKernelGGL(osc_chunk_scan_kernel, dim3((unsigned)(nscan_blocks + (p.NC + Q - 1) / Q)), dim3(64 * Q), 0, s, p, (int)nscan_blocks, Q);   // one wavefront per segment
-    ddsp_prof::end(slot, s);
-    slot = ddsp_prof::begin(ddsp_prof::SYNTH, s);
-    hipLaunchKernelGGL((osc_chunk_synth_kernel<K, false>), dim3(grid), dim3(256), sizeof(float) * 32 * kRow, s, p);
-    ddsp_prof::end(slot, s);
-    if (!DDSP_CHUNK_INLINE_REPAIR) {
-        const unsigned rgrid = grid < 256u ? grid : 256u;
-        hipLaunchKernelGGL((osc_chunk_synth_kernel<K, true>), dim3(rgrid), dim3(256), 0, s, p);
-    }
-    return hipGetLastError();
+    const SlotPlan &pl = slot_plan(p.H, K, 1 << p.logG);
+    return pl.KD ? launch_plan<K, plan_roots(K)>(p, pl, s) : launch_plan<K, K>(p, pl, s);
 }
 
 hipError_t chunk_geometry_k(OscParams &p, int *cus, int *wg_per_cu)

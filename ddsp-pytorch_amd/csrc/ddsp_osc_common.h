@@ -39,12 +39,14 @@ struct OscParams {
     int stage_out;    // synth: stage 32 output samples per frame in LDS, store whole 128-byte lines (pow2 hop >= 64, G in 4..16)
     int pow2;         // hop is a power of two and the clip has <= 2^23 samples: incremental weights, uniform loops
     // chunked form (ddsp_osc_chunk.hip): power-of-two hop >= 64, 4..16 lanes per row group
-    double *ctot;     // scratch [B,NC,H]: chunk totals, then (in place) their exclusive scan along the row
-    int *rlive;       // scratch [B,NC]: 1 + highest harmonic slot with a non-zero amplitude anywhere in the row's chunk
+    double *ctot;     // scratch [B,NC,HC]: chunk totals of the root slots, then (in place) their exclusive scan along the row
+    int *rlive;       // scratch [B,NC]: highest harmonic NUMBER (1-based, 0 = none) with a non-zero amplitude anywhere in the row's chunk
     int *perm;        // scratch [NC, RB*64/G]: per chunk index, the batch rows grouped by how many slots they walk (-1 = none)
     int *redo;        // scratch [RB*NC]: wave tasks the fast synth kernel declined
     int *frame_flag;  // the frame layout's flag words inside this scratch buffer (chunked launches clear the tag there)
     int Lc, NC, RB;   // chunk length in samples, chunks per row, row blocks (64/G rows each)
+    int HC;           // columns of ctot: root slots per lane * G (<= H), or H for the all-roots mapping
+    int cls_max[4];   // highest audible harmonic number for which 3/4, 1/2, 1/4, 1/8 of the root slots suffice (ddsp_osc_plan.h)
     int lgR;          // log2(R)
     int nres;         // wavefronts per SIMD the chunks were sized for (turn-taking modulus, <= 3)
     int turn_shift;   // log2 of the turn-taking epoch in 100 MHz ticks
