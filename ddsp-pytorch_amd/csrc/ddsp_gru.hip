@@ -76,20 +76,86 @@ struct GruParams {
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
-__device__ __forceinline__ unsigned long long pack_granule(unsigned epoch, float v)
+// ---- the hand-off: granule formats, publish, sweep -------------------------------------------------------------------
+// A granule is one 64-bit word {tag | payload}; a format says where the tag sits, what tag an epoch has, how values are packed into
+// the payload and how a granule that arrived is unpacked into the poller's LDS image (row stride DS elements).
+//   GranuleF32    {epoch:32 | value:32}                 fp32 kernels: one value per granule
+// The matrix cores consume bf16 operands, so the hand-off of the bf16 variants carries bf16: the polls' volume through the L2 -- what a
+// step's time grows with (measured: +0.27 us per batch row forward, +0.54 backward with one fp32 value per granule) -- shrinks 2x / 3x.
+//   GranulePack2  {epoch:32 | v1:16 | v0:16}            forward: h of batch rows 2r and 2r+1, one unit; image rows 2r, 2r+1 = batch rows
+//   GranulePack3  {epoch:16 | v2:16 | v1:16 | v0:16}    backward: the three gate-gradient payloads of one (row, unit); epochs < 2^16;
+//                                                       image rows 3r + gate
+struct GranuleF32 {
+    typedef float image_t;
+    static constexpr int kTagShift = 32;
+    static __device__ __forceinline__ unsigned tag(unsigned epoch) { return epoch; }
+    static __device__ __forceinline__ unsigned long long pack(unsigned epoch, float v)
+    {
+        return ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v);
+    }
+    static __device__ __forceinline__ void unpack(unsigned long long x, float *dst, int row, int DS, int col)
+    {
+        dst[row * DS + col] = __uint_as_float((unsigned)x);
+    }
+};
+
+__device__ __forceinline__ unsigned bf16_bits(float v)
 {
-    return ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v);
+    const __bf16 b = (__bf16)v;     // round to nearest even, as the fragments' conversion did before
+    return (unsigned)__builtin_bit_cast(unsigned short, b);
+}
+// the N 16-bit values of a packed granule go to image rows row * N + i
+template <int N>
+__device__ __forceinline__ void unpack_bf16(unsigned long long x, __bf16 *dst, int row, int DS, int col)
+{
+    unsigned short *img = reinterpret_cast<unsigned short *>(dst);
+#pragma unroll
+    for (int i = 0; i < N; ++i) img[(row * N + i) * DS + col] = (unsigned short)(x >> (16 * i));
 }
 
-// Polls `rows` granule rows of width Hd (row stride HP granules) until every tag equals `epoch`; values go to LDS.
+struct GranulePack2 {
+    typedef __bf16 image_t;
+    static constexpr int kTagShift = 32;
+    static __device__ __forceinline__ unsigned tag(unsigned epoch) { return epoch; }
+    static __device__ __forceinline__ unsigned long long pack(unsigned epoch, float v0, float v1)
+    {
+        return ((unsigned long long)epoch << 32) | ((unsigned long long)bf16_bits(v1) << 16) | (unsigned long long)bf16_bits(v0);
+    }
+    static __device__ __forceinline__ void unpack(unsigned long long x, __bf16 *dst, int row, int DS, int col) { unpack_bf16<2>(x, dst, row, DS, col); }
+};
+
+struct GranulePack3 {
+    typedef __bf16 image_t;
+    static constexpr int kTagShift = 48;
+    static __device__ __forceinline__ unsigned tag(unsigned epoch) { return epoch & 0xffffu; }
+    static __device__ __forceinline__ unsigned long long pack(unsigned epoch, float v0, float v1, float v2)
+    {
+        return ((unsigned long long)(epoch & 0xffffu) << 48) | ((unsigned long long)bf16_bits(v2) << 32) |
+               ((unsigned long long)bf16_bits(v1) << 16) | (unsigned long long)bf16_bits(v0);
+    }
+    static __device__ __forceinline__ void unpack(unsigned long long x, __bf16 *dst, int row, int DS, int col) { unpack_bf16<3>(x, dst, row, DS, col); }
+};
+
+// One granule store: relaxed, agent scope (sc1, written through), visible to a poll from any XCD.
+__device__ __forceinline__ void publish(gu64 *dst, unsigned long long granule)
+{
+    __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Polls `rows` granule rows of width Hd (row stride HP granules) until every tag is that of `epoch`; values go to the LDS image `dst`
+// (row stride DS) as the format G unpacks them.
 // A thread owns columns tid and tid + NT (NT = workgroup size) of every row; rows are polled RB at a time (2 RB independent loads in
 // flight per lane), and a batch whose tags all matched is not polled again.  Returns false (wave-uniform) on
 // timeout / abort.
-template <int RB, bool FIRST_LIGHT, typename DT = float>
-__device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd, int HP, unsigned epoch, gu32 *status, int NT,
-                                           long spin_ticks, int DS = 0)
+// (Tried on top, same-process A/B at 512 units: the backward WITHOUT first light 2.72 -> 3.05 us per step at batch 32, and two sets of polls
+//  in flight half a round trip apart 1.83 -> 2.24 forward / 2.72 -> 3.29 backward -- every extra poll slows the L2 for the publishers;
+//  first light on ONE granule per publisher instead of one per column: polled by every wavefront 2.65 -> 3.0, polled by wavefront 0 alone
+//  + a barrier 2.65 -> 2.66 at batch 32 (2.31 -> 2.05 at batch 8): not taken.)
+template <int RB, bool FIRST_LIGHT, typename G>
+__device__ __forceinline__ bool sweep(gu64 *src, typename G::image_t *dst, int rows, int Hd, int HP, int DS, unsigned epoch, gu32 *status,
+                                      int NT, long spin_ticks)
 {
-    if (DS == 0) DS = HP;                                 // destination row stride in LDS (the granule rows are HP apart)
+    const unsigned want = G::tag(epoch);
     const long t0 = wall_clock64();
     const int kc[2] = {(int)threadIdx.x, (int)threadIdx.x + NT};
     const int nb = (rows + RB - 1) / RB;                  // <= 16 batches
@@ -103,7 +169,7 @@ __device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd,
         gu64 *sentinel = src + (size_t)(rows - 1) * HP + kc[0];
         for (unsigned pass = 0;; ++pass) {
             const unsigned long long x = __hip_atomic_load(sentinel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((unsigned)(x >> 32) == epoch)) break;
+            if (__all((unsigned)(x >> G::kTagShift) == want)) break;
             if ((pass & 63) == 63) {
                 if (wall_clock64() - t0 > spin_ticks) return false;
                 if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
@@ -120,7 +186,7 @@ __device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd,
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int row = bi * RB + r;
-                    x[r][c] = (unsigned long long)epoch << 32;
+                    x[r][c] = (unsigned long long)want << G::kTagShift;
                     if (row < rows && kc[c] < Hd)
                         x[r][c] = __hip_atomic_load(src + (size_t)row * HP + kc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -128,7 +194,7 @@ __device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd,
 #pragma unroll
             for (int r = 0; r < RB; ++r)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) ok = ok && (unsigned)(x[r][c] >> 32) == epoch;
+                for (int c = 0; c < 2; ++c) ok = ok && (unsigned)(x[r][c] >> G::kTagShift) == want;
             if (__all(ok)) {   // the whole batch arrived: store it without per-granule predication
                 todo &= ~(1u << bi);
 #pragma unroll
@@ -137,7 +203,7 @@ __device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd,
                     if (row < rows) {
 #pragma unroll
                         for (int c = 0; c < 2; ++c)
-                            if (kc[c] < Hd) dst[row * DS + kc[c]] = (DT)__uint_as_float((unsigned)x[r][c]);
+                            if (kc[c] < Hd) G::unpack(x[r][c], dst, row, DS, kc[c]);
                     }
                 }
             }
@@ -151,103 +217,105 @@ __device__ __forceinline__ bool sweep_rows(gu64 *src, DT *dst, int rows, int Hd,
     }
 }
 
-// One granule store: relaxed, agent scope (sc1, written through), visible to a poll from any XCD.
-__device__ __forceinline__ void publish(gu64 *dst, unsigned epoch, float v)
-{
-    __hip_atomic_store(dst, pack_granule(epoch, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// ---- what the four kernels share besides the hand-off ------------------------------------------------------------------
+// (Each piece is inlined into its callers; the kernels' register, scratch and LDS footprints are those of the separate copies these
+//  replaced.  The workgroup prologue, the backward's fetch of a step's inputs and its gate gradients with their stores stay written out in
+//  the kernels: every shared form tried for them moved the register allocation of some kernel.  See also ForwardCell.)
 
-// ---- packed granules of the bf16 matrix-core variants ----------------------------------------------------------------
-// The matrix cores consume bf16 operands, so the hand-off carries bf16: the polls' volume through the L2 -- what a step's time
-// grows with (measured: +0.27 us per batch row forward, +0.54 backward with one fp32 value per granule) -- shrinks 2x / 3x.
-//   PACK2  {epoch:32 | v1:16 | v0:16}            forward: h of batch rows 2r and 2r+1, one unit
-//   PACK3  {epoch:16 | v2:16 | v1:16 | v0:16}    backward: the three gate-gradient payloads of one (row, unit); epochs < 2^16
-__device__ __forceinline__ unsigned bf16_bits(float v)
-{
-    const __bf16 b = (__bf16)v;     // round to nearest even, as the fragments' conversion did before
-    return (unsigned)__builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ void publish2(gu64 *dst, unsigned epoch, float v0, float v1)
-{
-    const unsigned long long g = ((unsigned long long)epoch << 32) | ((unsigned long long)bf16_bits(v1) << 16) | (unsigned long long)bf16_bits(v0);
-    __hip_atomic_store(dst, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void publish3(gu64 *dst, unsigned epoch, float v0, float v1, float v2)
-{
-    const unsigned long long g = ((unsigned long long)(epoch & 0xffffu) << 48) | ((unsigned long long)bf16_bits(v2) << 32) |
-                                 ((unsigned long long)bf16_bits(v1) << 16) | (unsigned long long)bf16_bits(v0);
-    __hip_atomic_store(dst, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// (Tried on top, same-process A/B at 512 units: the backward WITHOUT first light 2.72 -> 3.05 us per step at batch 32, and two sets of polls
-//  in flight half a round trip apart 1.83 -> 2.24 forward / 2.72 -> 3.29 backward -- every extra poll slows the L2 for the publishers;
-//  first light on ONE granule per publisher instead of one per column: polled by every wavefront 2.65 -> 3.0, polled by wavefront 0 alone
-//  + a barrier 2.65 -> 2.66 at batch 32 (2.31 -> 2.05 at batch 8): not taken.)
-// sweep_rows for packed granules: `rows` granule rows of width Hd (stride HP); PACK values of each granule go to the bf16 LDS image at
-// dst[(row * PACK + i) * DS + column] (PACK2: image rows 2r, 2r+1 = batch rows; PACK3: image rows 3r + gate).
-template <int RB, bool FIRST_LIGHT, int PACK>
-__device__ __forceinline__ bool sweep_packed(gu64 *src, unsigned short *dst, int rows, int Hd, int HP, unsigned epoch, gu32 *status,
-                                             long spin_ticks, int DS)
-{
-    constexpr int NT = 256;
-    constexpr int TAG_SHIFT = PACK == 3 ? 48 : 32;
-    const unsigned want = PACK == 3 ? (epoch & 0xffffu) : epoch;
-    const long t0 = wall_clock64();
-    const int kc[2] = {(int)threadIdx.x, (int)threadIdx.x + NT};
-    const int nb = (rows + RB - 1) / RB;
-    unsigned todo = (1u << nb) - 1u;
-    if (FIRST_LIGHT && kc[0] < Hd) {
-        gu64 *sentinel = src + (size_t)(rows - 1) * HP + kc[0];
-        for (unsigned pass = 0;; ++pass) {
-            const unsigned long long x = __hip_atomic_load(sentinel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((unsigned)(x >> TAG_SHIFT) == want)) break;
-            if ((pass & 63) == 63) {
-                if (wall_clock64() - t0 > spin_ticks) return false;
-                if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
+// LDS layouts, in one place for the kernels' carve-up and the host's sizes.  Every layout ends in the failure flag (4 words reserved).
+//   fp32 forward    float [rows][HP] h_{t-1}                    | flag         rows = BL rounded up to the register tile
+//   fp32 backward   float [rows][3][HP] gate gradients          | flag
+//   bf16 forward    bf16 [16][HS] h_{t-1}                       | flag         HS = HP + 8: a fragment is one conflict-free 16-byte read
+//   bf16 backward   bf16 [16][3][HS] gate gradients | float red [4][16][16] partial tiles | flag
+constexpr int kMfmaRows = 16;     // rows of one MFMA tile = the most batch rows a group may hold in the bf16 variants
+template <int KP>
+struct GruLds {
+    static constexpr int HP = 16 * KP, HS = HP + 8;
+    __host__ __device__ static constexpr int padded_rows(int BL, int RT) { return (BL + RT - 1) & ~(RT - 1); }   // whole register tiles
+    static constexpr int kRed = 4 * 256;                                                                       // floats
+    __host__ __device__ static constexpr int image(int rows, int payloads) { return rows * payloads * HP; }    // fp32 kernels: floats
+    __host__ __device__ static constexpr size_t bytes(int rows, int payloads) { return sizeof(float) * (image(rows, payloads) + 4); }
+    __host__ __device__ static constexpr int mfma_image(int payloads) { return kMfmaRows * payloads * HS; }    // bf16 kernels: bf16 elements
+    __host__ __device__ static constexpr size_t mfma_bytes(bool backward)
+    {
+        return backward ? sizeof(__bf16) * mfma_image(3) + sizeof(float) * (kRed + 4) : sizeof(__bf16) * mfma_image(1) + sizeof(float) * 4;
     }
-    for (unsigned pass = 0;; ++pass) {
-        for (int bi = 0; bi < nb; ++bi) {
-            if (!((todo >> bi) & 1u)) continue;           // wave-uniform
-            unsigned long long x[RB][2];
+};
+
+// Test hook (ddsp_gru_set_mode(2)): workgroup 0 withholds its publishes from step GruParams::fault_step on.
+__device__ __forceinline__ int fault_from(int fault_step) { return (fault_step >= 0 && blockIdx.x == 0) ? fault_step : 0x7fffffff; }
+
+// Failure handling.  A sweep that gave up raises the workgroup's LDS flag (the result is wave-uniform: one lane per wavefront writes);
+// after the barrier everybody leaves the time loop, the status word is raised for the peers and the host, and everything the workgroup owns
+// of the steps it did not complete becomes NaN: loud failure -- the buffers come from torch.empty, stale memory would otherwise flow
+// into the weight gradients as finite garbage.
+template <int RB, bool FIRST_LIGHT, typename G>
+__device__ __forceinline__ void sweep_or_flag(gu64 *src, typename G::image_t *dst, int rows, int Hd, int HP, int DS, unsigned epoch, gu32 *status,
+                                              int NT, long spin_ticks, int *fail_s)
+{
+    const bool ok = sweep<RB, FIRST_LIGHT, G>(src, dst, rows, Hd, HP, DS, epoch, status, NT, spin_ticks);
+    if (!ok && (threadIdx.x & 63) == 0) *fail_s = 1;
+}
+__device__ __forceinline__ void raise_timeout(gu32 *status)
+{
+    if (threadIdx.x == 0) __hip_atomic_store(status, (unsigned)GRU_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The forward cell of one (batch row, unit): gate math and blend from the input-projection terms gi*, the recurrent products
+// s* = (W_hh h_{t-1})[gate, unit] and the unit's own h_{t-1}.  compute() returns h_t and leaves r, z, n and W_hn h + b_hn for the caller's
+// stores.  (The stores of y / gates / hn / hT and the forward poison stay written out in the two forward kernels, and the bf16 forward
+// kernel also keeps its fault_step expression: shared forms of them re-scheduled the forward kernels' time loops, and the bf16 one
+// measured 1 - 1.5 % slower per step.)
+struct ForwardCell {
+    float r, z, n, ghn, h;
+    __device__ __forceinline__ float compute(float gir, float giz, float gin, float sr, float sz, float sn, const float (&bh)[3], float hp)
+    {
+        ghn = sn + bh[2];
+        r = sigmoidf_(gir + (sr + bh[0]));
+        z = sigmoidf_(giz + (sz + bh[1]));
+        n = tanhf_(__fmaf_rn(r, ghn, gin));
+        h = __fmaf_rn(hp - n, z, n);
+        return h;
+    }
+};
+
+// Backward: everything the gate gradients need besides dh itself is linear in dh, so the five factors (and dy) of a step are derived
+// one step ahead from the step's fetched inputs raw = {r, z, n, W_hn h + b_hn, h_{t-1}, dy}.
+__device__ __forceinline__ void derive_step(const float (&raw)[6], float &dyv, float &f_r, float &f_z, float &f_hn, float &f_n, float &f_dir)
+{
+    const float r = raw[0], z = raw[1], n = raw[2], ghn = raw[3], hp = raw[4];
+    dyv = raw[5];
+    f_n = (1.0f - z) * (1.0f - n * n);        // d(n pre-activation) / dh
+    f_r = (f_n * ghn) * (r * (1.0f - r));     // d(r pre-activation) / dh
+    f_z = (hp - n) * (z * (1.0f - z));        // d(z pre-activation) / dh
+    f_hn = f_n * r;                           // d(W_hn h + b_hn) / dh
+    f_dir = z;                                // direct path h_{t-1} -> h_t
+}
+
+// d_gi / d_gh as the caller's GEMMs want them: fp32, or -- MAY16, the bf16 variants with GruParams::io16 -- bf16 arrays behind the float
+// pointers.  (The fp32 kernels write fp32 only: no branch there.)
+// (The forward's gi stays fp32: read as bf16 -- even with the conversion deferred to the step that uses the value -- the forward
+//  kernel measured 0.87 -> 1.05 ms at the training shape; the cast pass in front of it costs 0.02 ms.)
+template <bool MAY16>
+__device__ __forceinline__ void store_gate_grad(const GruParams &p, float *base, size_t i, float v)
+{
+    if (MAY16 && p.io16) reinterpret_cast<__bf16 *>(base)[i] = (__bf16)v;
+    else base[i] = v;
+}
+
+// Backward failure: the gate gradients of step t of one (batch row, column) become NaN -- for every step the workgroup did not reach, and
+// dh0 with them, so that the weight gradients (d_gh^T h, sum d_gh, d_gi through autograd) are NaN instead of stale memory.
+template <bool MAY16>
+__device__ __forceinline__ void poison_backward_step(const GruParams &p, int row, int k, int t)
+{
+    const int Hd = p.Hd;
+    const size_t G3 = (size_t)3 * Hd;
+    const float nan = __builtin_nanf("");
+    const size_t bt = (size_t)row * p.T + t;
 #pragma unroll
-            for (int r = 0; r < RB; ++r)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int row = bi * RB + r;
-                    x[r][c] = (unsigned long long)want << TAG_SHIFT;
-                    if (row < rows && kc[c] < Hd)
-                        x[r][c] = __hip_atomic_load(src + (size_t)row * HP + kc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            bool ok = true;
-#pragma unroll
-            for (int r = 0; r < RB; ++r)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) ok = ok && (unsigned)(x[r][c] >> TAG_SHIFT) == want;
-            if (__all(ok)) {
-                todo &= ~(1u << bi);
-#pragma unroll
-                for (int r = 0; r < RB; ++r) {
-                    const int row = bi * RB + r;
-                    if (row < rows) {
-#pragma unroll
-                        for (int c = 0; c < 2; ++c)
-                            if (kc[c] < Hd) {
-#pragma unroll
-                                for (int i = 0; i < PACK; ++i) dst[(row * PACK + i) * DS + kc[c]] = (unsigned short)(x[r][c] >> (16 * i));
-                            }
-                    }
-                }
-            }
-        }
-        if (todo == 0u) return true;
-        if ((pass & 63) == 63) {
-            if (wall_clock64() - t0 > spin_ticks) return false;
-            if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
+    for (int g = 0; g < 3; ++g) {
+        store_gate_grad<MAY16>(p, p.d_gi, bt * G3 + g * Hd + k, nan);
+        store_gate_grad<MAY16>(p, p.d_gh, bt * G3 + g * Hd + k, nan);
     }
 }
 
@@ -262,8 +330,8 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_fwd_kernel(GruParams p)
     const int row0 = group * p.BL;
     const int nrows = min(p.BL, p.B - row0);
     if (nrows <= 0) return;
-    const int BLpad = (p.BL + RT - 1) & ~(RT - 1);
-    int *fail_s = reinterpret_cast<int *>(h_s + BLpad * HP);
+    const int BLpad = GruLds<KP>::padded_rows(p.BL, RT);
+    int *fail_s = reinterpret_cast<int *>(h_s + GruLds<KP>::image(BLpad, 1));
     const int rs = threadIdx.x >> 8, lt = threadIdx.x & 255;   // row set, thread within the set
     const int ks = lt & 15, ul = lt >> 4;
     const int u = member * kUnits + ul;
@@ -303,14 +371,12 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_fwd_kernel(GruParams p)
         for (int g = 0; g < 3; ++g) pre[g] = p.gi[bt * G3 + g * Hd + u];
     }
 
-    const int fault_from = (p.fault_step >= 0 && blockIdx.x == 0) ? p.fault_step : 0x7fffffff;   // test hook: this workgroup stops publishing
+    const int no_publish_from = fault_from(p.fault_step);
     int t_reached = 0;                                             // steps [0, t_reached) were completed by this workgroup
     for (int t = 0; t < p.T; ++t) {
-        if (t > 0) {
-            const bool ok = sweep_rows<4, false>(xg + (size_t)((t - 1) & 1) * p.BL * HP, h_s, nrows, Hd, HP, (unsigned)t, p.status, 256 * NRS,
-                                                 p.spin_ticks);
-            if (!ok && (threadIdx.x & 63) == 0) *fail_s = 1;
-        }
+        if (t > 0)
+            sweep_or_flag<4, false, GranuleF32>(xg + (size_t)((t - 1) & 1) * p.BL * HP, h_s, nrows, Hd, HP, HP, (unsigned)t, p.status, 256 * NRS,
+                                                p.spin_ticks, fail_s);
         __syncthreads();
         if (*fail_s) break;
         t_reached = t + 1;
@@ -354,29 +420,23 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_fwd_kernel(GruParams p)
                 if (ks == r) { sr = acc[r][0]; sz = acc[r][1]; sn = acc[r][2]; }
             }
             if (mine) {
-                const float hp = h_s[bl * HP + u];
-                const float ghn = sn + bh[2];
-                const float r = sigmoidf_(gir + (sr + bh[0]));
-                const float z = sigmoidf_(giz + (sz + bh[1]));
-                const float n = tanhf_(__fmaf_rn(r, ghn, gin));
-                const float hnew = __fmaf_rn(hp - n, z, n);
-                if (t < fault_from) publish(xg + ((size_t)(t & 1) * p.BL + bl) * HP + u, (unsigned)t + 1u, hnew);
+                ForwardCell cell;
+                const float hnew = cell.compute(gir, giz, gin, sr, sz, sn, bh, h_s[bl * HP + u]);
+                if (t < no_publish_from) publish(xg + ((size_t)(t & 1) * p.BL + bl) * HP + u, GranuleF32::pack((unsigned)t + 1u, hnew));
                 p.y[bt * Hd + u] = hnew;
                 if (p.gates) {
-                    p.gates[bt * G3 + u] = r;
-                    p.gates[bt * G3 + Hd + u] = z;
-                    p.gates[bt * G3 + 2 * Hd + u] = n;
+                    p.gates[bt * G3 + u] = cell.r;
+                    p.gates[bt * G3 + Hd + u] = cell.z;
+                    p.gates[bt * G3 + 2 * Hd + u] = cell.n;
                 }
-                if (p.hn) p.hn[bt * Hd + u] = ghn;
+                if (p.hn) p.hn[bt * Hd + u] = cell.ghn;
                 if (t == p.T - 1) p.hT[(size_t)(row0 + bl) * Hd + u] = hnew;
             }
         }
         __syncthreads();  // h_s is rewritten by the next sweep
     }
     if (*fail_s) {
-        // Loud failure: everything this workgroup owns of the steps it did not complete becomes NaN (the buffers come from
-        // torch.empty: stale memory would otherwise flow into the weight gradients as finite garbage).
-        if (threadIdx.x == 0) __hip_atomic_store(p.status, (unsigned)GRU_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        raise_timeout(p.status);
         const float nan = __builtin_nanf("");
         if (unit_ok && rs == 0)
             for (int bl = ks; bl < nrows; bl += 16) {
@@ -410,8 +470,8 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
     const int row0 = group * p.BL;
     const int nrows = min(p.BL, p.B - row0);
     if (nrows <= 0) return;
-    const int BLpad = (p.BL + RT - 1) & ~(RT - 1);
-    int *fail_s = reinterpret_cast<int *>(d_s + BLpad * 3 * HP);
+    const int BLpad = GruLds<KP>::padded_rows(p.BL, RT);
+    int *fail_s = reinterpret_cast<int *>(d_s + GruLds<KP>::image(BLpad, 3));
     const int rs = threadIdx.x >> 8, lt = threadIdx.x & 255;   // row set, thread within the set
     const int us = lt & 15, kl = lt >> 4;
     const int k = member * kUnits + kl;
@@ -442,8 +502,8 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
         carry[q] = (gate_lane && bl < nrows && p.dhT) ? p.dhT[(size_t)(row0 + bl) * Hd + k] : 0.0f;
     }
 
-    // Everything the gate gradients need besides dh itself is linear in dh: the five factors (and dy) of step t are
-    // prepared one step ahead, so the critical path of a step is one add and five multiplies before the publish.
+    // The five factors (and dy) of step t are prepared one step ahead (derive_step), so the critical path of a step is one add and
+    // five multiplies before the publish.
     float dyv[Q], f_r[Q], f_z[Q], f_hn[Q], f_n[Q], f_dir[Q];
     float raw[Q][6];  // r, z, n, W_hn h + b_hn, h_{t-1}, dy of the NEXT step: loaded a whole step before they are used
     auto fetch = [&](int t) {
@@ -463,15 +523,7 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
     };
     auto derive = [&]() {
 #pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const float r = raw[q][0], z = raw[q][1], n = raw[q][2], ghn = raw[q][3], hp = raw[q][4];
-            dyv[q] = raw[q][5];
-            f_n[q] = (1.0f - z) * (1.0f - n * n);        // d(n pre-activation) / dh
-            f_r[q] = (f_n[q] * ghn) * (r * (1.0f - r));  // d(r pre-activation) / dh
-            f_z[q] = (hp - n) * (z * (1.0f - z));        // d(z pre-activation) / dh
-            f_hn[q] = f_n[q] * r;                        // d(W_hn h + b_hn) / dh
-            f_dir[q] = z;                                // direct path h_{t-1} -> h_t
-        }
+        for (int q = 0; q < Q; ++q) derive_step(raw[q], dyv[q], f_r[q], f_z[q], f_hn[q], f_n[q], f_dir[q]);
     };
 #pragma unroll
     for (int q = 0; q < Q; ++q)
@@ -481,7 +533,7 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
     derive();
     if (p.T > 1) fetch(p.T - 2);
 
-    const int fault_from = (p.fault_step >= 0 && blockIdx.x == 0) ? p.fault_step : 0x7fffffff;   // test hook: this workgroup stops publishing
+    const int no_publish_from = fault_from(p.fault_step);
     int s_reached = 0;                                             // steps [0, s_reached) (t = T-1-s) wrote their gradients
     for (int s = 0; s < p.T; ++s) {
         const int t = p.T - 1 - s;
@@ -499,10 +551,10 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
                 const float dr_pre = dh * f_r[q], dz_pre = dh * f_z[q], dhn = dh * f_hn[q], dn_pre = dh * f_n[q];
                 direct[q] = dh * f_dir[q];
                 gu64 *gdst = slot + (size_t)bl * 3 * HP + k;
-                if (s < fault_from) {
-                    publish(gdst, epoch, dr_pre);
-                    publish(gdst + HP, epoch, dz_pre);
-                    publish(gdst + 2 * HP, epoch, dhn);
+                if (s < no_publish_from) {
+                    publish(gdst, GranuleF32::pack(epoch, dr_pre));
+                    publish(gdst + HP, GranuleF32::pack(epoch, dz_pre));
+                    publish(gdst + 2 * HP, GranuleF32::pack(epoch, dhn));
                 }
                 p.d_gi[bt * G3 + k] = dr_pre;
                 p.d_gi[bt * G3 + Hd + k] = dz_pre;
@@ -514,10 +566,7 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
         }
         s_reached = s + 1;
         // 2. the group's gate gradients -> LDS  (rows of 3 payloads: treated as 3*nrows rows of width Hd)
-        {
-            const bool ok = sweep_rows<12, NRS == 1>(slot, d_s, 3 * nrows, Hd, HP, epoch, p.status, 256 * NRS, p.spin_ticks);
-            if (!ok && (threadIdx.x & 63) == 0) *fail_s = 1;
-        }
+        sweep_or_flag<12, NRS == 1, GranuleF32>(slot, d_s, 3 * nrows, Hd, HP, HP, epoch, p.status, 256 * NRS, p.spin_ticks, fail_s);
         __syncthreads();
         if (*fail_s) break;
         // factors of the next step from what was fetched a whole step ago, then the fetch for the step after it
@@ -555,23 +604,14 @@ __global__ void __launch_bounds__(256 * NRS, 1) gru_bwd_kernel(GruParams p)
         __syncthreads();  // d_s is rewritten by the next sweep
     }
     if (*fail_s) {
-        // Loud failure: dh0 and the gate gradients of every step this workgroup did not reach become NaN, so the weight
-        // gradients (d_gh^T h, sum d_gh, d_gi through autograd) are NaN instead of stale memory.
-        if (threadIdx.x == 0) __hip_atomic_store(p.status, (unsigned)GRU_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        raise_timeout(p.status);
         const float nan = __builtin_nanf("");
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             carry[q] = nan;
             const int bl = (q * NRS + rs) * RT + us;
             if (gate_lane && bl < nrows)
-                for (int s = s_reached; s < p.T; ++s) {
-                    const size_t bt = (size_t)(row0 + bl) * p.T + (p.T - 1 - s);
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        p.d_gi[bt * G3 + g * Hd + k] = nan;
-                        p.d_gh[bt * G3 + g * Hd + k] = nan;
-                    }
-                }
+                for (int s = s_reached; s < p.T; ++s) poison_backward_step<false>(p, row0 + bl, k, p.T - 1 - s);
         }
     }
 #pragma unroll
@@ -599,16 +639,6 @@ __device__ __forceinline__ bf16x8_t to_bf16x8(float4 a, float4 b)
     return r;
 }
 
-// d_gi / d_gh as the caller's GEMMs want them (GruParams::io16): bf16 arrays behind the float pointers, or fp32.
-// (The forward's gi stays fp32: read as bf16 -- even with the conversion deferred to the step that uses the value -- the forward
-//  kernel measured 0.87 -> 1.05 ms at the training shape; the cast pass in front of it costs 0.02 ms.)
-__device__ __forceinline__ void store_gate_grad(const GruParams &p, float *base, size_t i, float v)
-{
-    if (p.io16) reinterpret_cast<__bf16 *>(base)[i] = (__bf16)v;
-    else base[i] = v;
-}
-
-constexpr int kMfmaRows = 16;     // rows of one MFMA tile = the most batch rows a group may hold in these variants
 
 // Forward: the tile is turned round -- M = (unit, gate) packed four to a unit (r, z, n, pad), N = the group's rows -- so that one
 // wavefront owns 4 units over the WHOLE K range and each lane ends up with the three pre-activations of one (row, unit) pair
@@ -618,8 +648,8 @@ __global__ void __launch_bounds__(256, 1) gru_fwd_mfma_kernel(GruParams p)
 {
     // [16][HS] h_{t-1} as the matrix cores take it (bf16: the poller converts each value once, a B fragment is one 16-byte read) | failure flag
     extern __shared__ __attribute__((aligned(16))) __bf16 h_bf[];
-    constexpr int HP = 16 * KP, HS = HP + 8, NKS = HP / 32;
-    int *fail_s = reinterpret_cast<int *>(h_bf + kMfmaRows * HS);
+    constexpr int HP = 16 * KP, HS = GruLds<KP>::HS, NKS = HP / 32;
+    int *fail_s = reinterpret_cast<int *>(h_bf + GruLds<KP>::mfma_image(1));
     const int group = blockIdx.x % p.NGpad, member = blockIdx.x / p.NGpad;
     if (group >= p.NG) return;
     const int row0 = group * p.BL;
@@ -668,14 +698,12 @@ __global__ void __launch_bounds__(256, 1) gru_fwd_mfma_kernel(GruParams p)
 #pragma unroll
         for (int g = 0; g < 3; ++g) pre[g] = p.gi[bt * G3 + g * Hd + gu];
     }
-    const int fault_from = (p.fault_step >= 0 && blockIdx.x == 0) ? p.fault_step : 0x7fffffff;
+    const int no_publish_from = (p.fault_step >= 0 && blockIdx.x == 0) ? p.fault_step : 0x7fffffff;
     int t_reached = 0;
     for (int t = 0; t < p.T; ++t) {
-        if (t > 0) {
-            const bool ok = sweep_packed<4, false, 2>(xg + (size_t)((t - 1) & 1) * PRW * HP, reinterpret_cast<unsigned short *>(h_bf), (nrows + 1) / 2,
-                                                      Hd, HP, (unsigned)t, p.status, p.spin_ticks, HS);
-            if (!ok && (threadIdx.x & 63) == 0) *fail_s = 1;
-        }
+        if (t > 0)
+            sweep_or_flag<4, false, GranulePack2>(xg + (size_t)((t - 1) & 1) * PRW * HP, h_bf, (nrows + 1) / 2, Hd, HP, HS, (unsigned)t, p.status, 256,
+                                                  p.spin_ticks, fail_s);
         __syncthreads();
         if (*fail_s) break;
         t_reached = t + 1;
@@ -700,14 +728,11 @@ __global__ void __launch_bounds__(256, 1) gru_fwd_mfma_kernel(GruParams p)
         __syncthreads();   // every wavefront has read h_bf: the next sweep may overwrite it
         float hnew = 0.0f;
         if (gate) {
-            const float sr = acc0[0] + acc1[0], sz = acc0[1] + acc1[1], sn = acc0[2] + acc1[2];
-            const size_t bt = (size_t)(row0 + gr) * p.T + t;
-            const float ghn = sn + bh[2];
-            const float r = sigmoidf_(gir + (sr + bh[0]));
-            const float z = sigmoidf_(giz + (sz + bh[1]));
-            const float n = tanhf_(__fmaf_rn(r, ghn, gin));
-            hnew = __fmaf_rn(hp - n, z, n);
+            ForwardCell cell;
+            hnew = cell.compute(gir, giz, gin, acc0[0] + acc1[0], acc0[1] + acc1[1], acc0[2] + acc1[2], bh, hp);
             hp = hnew;
+            const float r = cell.r, z = cell.z, n = cell.n, ghn = cell.ghn;
+            const size_t bt = (size_t)(row0 + gr) * p.T + t;
             p.y[bt * Hd + gu] = hnew;
             if (p.gates) {
                 p.gates[bt * G3 + gu] = r;
@@ -721,13 +746,13 @@ __global__ void __launch_bounds__(256, 1) gru_fwd_mfma_kernel(GruParams p)
         // row) with one DPP move and publishes the pair
         {
             const float nb = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, hnew), 0x101 /* row_shl:1 */, 0xf, 0xf, true));
-            if (gate && (gr & 1) == 0 && t < fault_from)
-                publish2(xg + ((size_t)(t & 1) * PRW + (gr >> 1)) * HP + gu, (unsigned)t + 1u, hnew, nb);
+            if (gate && (gr & 1) == 0 && t < no_publish_from)
+                publish(xg + ((size_t)(t & 1) * PRW + (gr >> 1)) * HP + gu, GranulePack2::pack((unsigned)t + 1u, hnew, nb));
         }
     }
     __syncthreads();
     if (*fail_s) {
-        if (threadIdx.x == 0) __hip_atomic_store(p.status, (unsigned)GRU_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        raise_timeout(p.status);
         const float nan = __builtin_nanf("");
         if (gate) {
             p.hT[(size_t)(row0 + gr) * Hd + gu] = nan;
@@ -749,9 +774,9 @@ template <int KP>
 __global__ void __launch_bounds__(256, 1) gru_bwd_mfma_kernel(GruParams p)
 {
     extern __shared__ __attribute__((aligned(16))) __bf16 d_bf[];   // [16][3][HS] gate gradients (bf16, as the matrix cores take them) | red [4][16][16] fp32 | failure flag
-    constexpr int HP = 16 * KP, HS = HP + 8, NKS = 3 * HP / 32, KSW = (NKS + 3) / 4;
-    float *red = reinterpret_cast<float *>(d_bf + kMfmaRows * 3 * HS);
-    int *fail_s = reinterpret_cast<int *>(red + 4 * 256);
+    constexpr int HP = 16 * KP, HS = GruLds<KP>::HS, NKS = 3 * HP / 32, KSW = (NKS + 3) / 4;
+    float *red = reinterpret_cast<float *>(d_bf + GruLds<KP>::mfma_image(3));
+    int *fail_s = reinterpret_cast<int *>(red + GruLds<KP>::kRed);
     const int group = blockIdx.x % p.NGpad, member = blockIdx.x / p.NGpad;
     if (group >= p.NG) return;
     const int row0 = group * p.BL;
@@ -804,20 +829,12 @@ __global__ void __launch_bounds__(256, 1) gru_bwd_mfma_kernel(GruParams p)
             raw[5] = p.dy[bt * Hd + gk];
         }
     };
-    auto derive = [&]() {
-        const float r = raw[0], z = raw[1], n = raw[2], ghn = raw[3], hp = raw[4];
-        dyv = raw[5];
-        f_n = (1.0f - z) * (1.0f - n * n);
-        f_r = (f_n * ghn) * (r * (1.0f - r));
-        f_z = (hp - n) * (z * (1.0f - z));
-        f_hn = f_n * r;
-        f_dir = z;
-    };
+    auto derive = [&]() { derive_step(raw, dyv, f_r, f_z, f_hn, f_n, f_dir); };
     fetch(p.T - 1);
     derive();
     if (p.T > 1) fetch(p.T - 2);
 
-    const int fault_from = (p.fault_step >= 0 && blockIdx.x == 0) ? p.fault_step : 0x7fffffff;
+    const int no_publish_from = fault_from(p.fault_step);
     int s_reached = 0;
     for (int s = 0; s < p.T; ++s) {
         const int t = p.T - 1 - s;
@@ -832,20 +849,17 @@ __global__ void __launch_bounds__(256, 1) gru_bwd_mfma_kernel(GruParams p)
             const float dh = dyv + carry;
             const float dr_pre = dh * f_r, dz_pre = dh * f_z, dhn = dh * f_hn, dn_pre = dh * f_n;
             direct = dh * f_dir;
-            if (s < fault_from) publish3(slot + (size_t)gr * HP + gk, epoch, dr_pre, dz_pre, dhn);
-            store_gate_grad(p, p.d_gi, bt * G3 + gk, dr_pre);
-            store_gate_grad(p, p.d_gi, bt * G3 + Hd + gk, dz_pre);
-            store_gate_grad(p, p.d_gi, bt * G3 + 2 * Hd + gk, dn_pre);
-            store_gate_grad(p, p.d_gh, bt * G3 + gk, dr_pre);
-            store_gate_grad(p, p.d_gh, bt * G3 + Hd + gk, dz_pre);
-            store_gate_grad(p, p.d_gh, bt * G3 + 2 * Hd + gk, dhn);
+            if (s < no_publish_from) publish(slot + (size_t)gr * HP + gk, GranulePack3::pack(epoch, dr_pre, dz_pre, dhn));
+            store_gate_grad<true>(p, p.d_gi, bt * G3 + gk, dr_pre);
+            store_gate_grad<true>(p, p.d_gi, bt * G3 + Hd + gk, dz_pre);
+            store_gate_grad<true>(p, p.d_gi, bt * G3 + 2 * Hd + gk, dn_pre);
+            store_gate_grad<true>(p, p.d_gh, bt * G3 + gk, dr_pre);
+            store_gate_grad<true>(p, p.d_gh, bt * G3 + Hd + gk, dz_pre);
+            store_gate_grad<true>(p, p.d_gh, bt * G3 + 2 * Hd + gk, dhn);
         }
         s_reached = s + 1;
         // 2. the group's gate gradients -> LDS (3 * nrows rows of width Hd)
-        {
-            const bool ok = sweep_packed<4, true, 3>(slot, reinterpret_cast<unsigned short *>(d_bf), nrows, Hd, HP, epoch, p.status, p.spin_ticks, HS);
-            if (!ok && (threadIdx.x & 63) == 0) *fail_s = 1;
-        }
+        sweep_or_flag<4, true, GranulePack3>(slot, d_bf, nrows, Hd, HP, HS, epoch, p.status, 256, p.spin_ticks, fail_s);
         __syncthreads();
         if (*fail_s) break;
         derive();
@@ -867,18 +881,10 @@ __global__ void __launch_bounds__(256, 1) gru_bwd_mfma_kernel(GruParams p)
         __syncthreads();   // `red` complete (read at the top of the next step); d_bf free for the next sweep
     }
     if (*fail_s) {
-        if (threadIdx.x == 0) __hip_atomic_store(p.status, (unsigned)GRU_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float nan = __builtin_nanf("");
+        raise_timeout(p.status);
         if (gate) {
-            p.dh0[(size_t)(row0 + gr) * Hd + gk] = nan;
-            for (int s = s_reached; s < p.T; ++s) {
-                const size_t bt = (size_t)(row0 + gr) * p.T + (p.T - 1 - s);
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    store_gate_grad(p, p.d_gi, bt * G3 + g * Hd + gk, nan);
-                    store_gate_grad(p, p.d_gh, bt * G3 + g * Hd + gk, nan);
-                }
-            }
+            p.dh0[(size_t)(row0 + gr) * Hd + gk] = __builtin_nanf("");
+            for (int s = s_reached; s < p.T; ++s) poison_backward_step<true>(p, row0 + gr, gk, p.T - 1 - s);
         }
         return;
     }
@@ -907,18 +913,24 @@ struct DeviceGate {
 };
 DeviceGate g_gate[64];
 
-// Groups / rows per group for a [B, Hd] problem on a device with `cus` compute units; false if it does not fit.
+// Groups that can be co-resident on `cus` compute units when a group takes NW workgroups, one workgroup per CU (two per CU measured
+// slower: the waiting workgroup's polls slow its neighbour and the L2).
 // `spread` (test hook): an odd blockIdx modulus NG | 1, which deals every group's workgroups over all XCDs.
+int resident_slots(int cus, int NW, bool spread)
+{
+    const int slots = cus / NW;
+    return spread ? slots - 1             // room for the padding group of the odd modulus
+                  : slots - slots % 8;    // blockIdx modulus is a multiple of 8 (XCD alignment)
+}
+
+// Groups / rows per group for a [B, Hd] problem on a device with `cus` compute units; false if it does not fit.
 bool plan_gru(int B, int Hd, int cus, int max_rows, bool spread, GruPlan *pl)
 {
     if (Hd > 512) return false;
     pl->KP = Hd <= 64 ? 4 : (Hd <= 128 ? 8 : (Hd <= 256 ? 16 : 32));
     pl->HP = 16 * pl->KP;
     pl->NW = (Hd + kUnits - 1) / kUnits;
-    int slots = cus / pl->NW;          // groups that can be co-resident, one workgroup per CU (two per CU measured
-                                       // slower: the waiting workgroup's polls slow its neighbour and the L2)
-    if (spread) slots -= 1;            // room for the padding group of the odd modulus
-    else slots -= slots % 8;           // blockIdx modulus is a multiple of 8 (XCD alignment)
+    const int slots = resident_slots(cus, pl->NW, spread);
     if (slots < (spread ? 1 : 8)) return false;
     pl->NG = B < slots ? B : slots;
     pl->BL = (B + pl->NG - 1) / pl->NG;
@@ -968,57 +980,34 @@ hipError_t check_resident(K kernel, int threads, size_t lds, unsigned grid, int 
     return hipSuccess;
 }
 
-template <int KP, int RT, int NRS>
-hipError_t launch_fwd(const GruParams &p, size_t lds, hipStream_t s)
+// One persistent launch of NGpad * NW workgroups: the big-LDS opt-in and the residency check (each cached per kernel instantiation
+// and device), then the launch.  `lds` is what this plan needs, `lds_max` the most any plan of the instantiation needs.
+template <auto Kernel>
+hipError_t launch_persistent(const GruParams &p, int threads, size_t lds, size_t lds_max, hipStream_t s)
 {
     static bool attr[64] = {};
     static int resident[64] = {};
-    hipError_t e = ddsp_allow_big_lds((const void *)gru_fwd_kernel<KP, RT, NRS>, attr);
-    if (e != hipSuccess) return e;
-    e = check_resident(gru_fwd_kernel<KP, RT, NRS>, 256 * NRS, sizeof(float) * ((size_t)kMaxRows * 16 * KP + 4),
-                       (unsigned)(p.NGpad * p.NW), resident);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gru_fwd_kernel<KP, RT, NRS>), dim3((unsigned)(p.NGpad * p.NW)), dim3(256 * NRS), lds, s, p);
-    return hipGetLastError();
-}
-
-template <int KP, int RT, int NRS>
-hipError_t launch_bwd(const GruParams &p, size_t lds, hipStream_t s)
-{
-    static bool attr[64] = {};
-    static int resident[64] = {};
-    hipError_t e = ddsp_allow_big_lds((const void *)gru_bwd_kernel<KP, RT, NRS>, attr);
-    if (e != hipSuccess) return e;
-    e = check_resident(gru_bwd_kernel<KP, RT, NRS>, 256 * NRS, sizeof(float) * ((size_t)kMaxRowsBwd * 3 * 16 * KP + 4),
-                       (unsigned)(p.NGpad * p.NW), resident);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gru_bwd_kernel<KP, RT, NRS>), dim3((unsigned)(p.NGpad * p.NW)), dim3(256 * NRS), lds, s, p);
-    return hipGetLastError();
-}
-
-template <int KP>
-hipError_t launch_mfma(const GruParams &p, bool backward, hipStream_t s)
-{
-    constexpr int HS = 16 * KP + 8;     // row stride of the bf16 image in LDS
-    static bool attr[2][64] = {};
-    static int resident[2][64] = {};
-    const size_t lds = backward ? sizeof(__bf16) * (size_t)kMfmaRows * 3 * HS + sizeof(float) * (4 * 256 + 4)
-                                : sizeof(__bf16) * (size_t)kMfmaRows * HS + sizeof(float) * 4;
     const unsigned grid = (unsigned)(p.NGpad * p.NW);
-    if (backward) {
-        hipError_t e = ddsp_allow_big_lds((const void *)gru_bwd_mfma_kernel<KP>, attr[1]);
-        if (e != hipSuccess) return e;
-        e = check_resident(gru_bwd_mfma_kernel<KP>, 256, lds, grid, resident[1]);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gru_bwd_mfma_kernel<KP>), dim3(grid), dim3(256), lds, s, p);
-    } else {
-        hipError_t e = ddsp_allow_big_lds((const void *)gru_fwd_mfma_kernel<KP>, attr[0]);
-        if (e != hipSuccess) return e;
-        e = check_resident(gru_fwd_mfma_kernel<KP>, 256, lds, grid, resident[0]);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gru_fwd_mfma_kernel<KP>), dim3(grid), dim3(256), lds, s, p);
-    }
+    hipError_t e = ddsp_allow_big_lds((const void *)Kernel, attr);
+    if (e != hipSuccess) return e;
+    e = check_resident(Kernel, threads, lds_max, grid, resident);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3((unsigned)threads), lds, s, p);
     return hipGetLastError();
+}
+
+template <int KP, int RT, int NRS>
+hipError_t launch_fwd(const GruParams &p, hipStream_t s)
+{
+    const int BLpad = GruLds<KP>::padded_rows(p.BL, RT);
+    return launch_persistent<gru_fwd_kernel<KP, RT, NRS>>(p, 256 * NRS, GruLds<KP>::bytes(BLpad, 1), GruLds<KP>::bytes(kMaxRows, 1), s);
+}
+
+template <int KP, int RT, int NRS>
+hipError_t launch_bwd(const GruParams &p, hipStream_t s)
+{
+    const int BLpad = GruLds<KP>::padded_rows(p.BL, RT);
+    return launch_persistent<gru_bwd_kernel<KP, RT, NRS>>(p, 256 * NRS, GruLds<KP>::bytes(BLpad, 3), GruLds<KP>::bytes(kMaxRowsBwd, 3), s);
 }
 
 // Shapes of a workgroup, chosen by same-box A/B (tools/ab_gru.sh): rows per register tile RT and row sets NRS (256 threads
@@ -1026,11 +1015,18 @@ hipError_t launch_mfma(const GruParams &p, bool backward, hipStream_t s)
 // cycles, so the forward's 384 FMAs + reductions of a 4-row tile (1.45 us of a 2.4 us step by in-kernel timers) run faster
 // as two 2-row tiles on two wavefronts per SIMD; the backward prefers one set with a 4-row tile up to 4 rows per group.
 template <int KP>
-hipError_t launch_gru(const GruParams &p, bool backward, int RT, int NRS, size_t lds, hipStream_t s)
+hipError_t launch_gru(const GruParams &p, bool backward, int RT, int NRS, hipStream_t s)
 {
-    if (!backward) return NRS == 1 ? launch_fwd<KP, 2, 1>(p, lds, s) : launch_fwd<KP, 2, 2>(p, lds, s);
-    if (RT == 4) return launch_bwd<KP, 4, 1>(p, lds, s);
-    return NRS == 1 ? launch_bwd<KP, 2, 1>(p, lds, s) : launch_bwd<KP, 2, 2>(p, lds, s);
+    if (!backward) return NRS == 1 ? launch_fwd<KP, 2, 1>(p, s) : launch_fwd<KP, 2, 2>(p, s);
+    if (RT == 4) return launch_bwd<KP, 4, 1>(p, s);
+    return NRS == 1 ? launch_bwd<KP, 2, 1>(p, s) : launch_bwd<KP, 2, 2>(p, s);
+}
+
+template <int KP>
+hipError_t launch_mfma(const GruParams &p, bool backward, hipStream_t s)
+{
+    const size_t lds = GruLds<KP>::mfma_bytes(backward);
+    return backward ? launch_persistent<gru_bwd_mfma_kernel<KP>>(p, 256, lds, lds, s) : launch_persistent<gru_fwd_mfma_kernel<KP>>(p, 256, lds, lds, s);
 }
 
 int run_gru(GruParams &p, void *scratch, bool backward, hipStream_t s)
@@ -1088,13 +1084,11 @@ int run_gru(GruParams &p, void *scratch, bool backward, hipStream_t s)
     } else {
         const int RT = (backward && pl.BL > 2 && pl.BL <= 4) ? 4 : 2;
         const int NRS = (pl.BL <= 2 || RT == 4) ? 1 : 2;
-        const int BLpad = (pl.BL + RT - 1) & ~(RT - 1);
-        const size_t lds = sizeof(float) * ((size_t)BLpad * payloads * pl.HP + 4);
         switch (pl.KP) {
-            case 4: e = launch_gru<4>(p, backward, RT, NRS, lds, s); break;
-            case 8: e = launch_gru<8>(p, backward, RT, NRS, lds, s); break;
-            case 16: e = launch_gru<16>(p, backward, RT, NRS, lds, s); break;
-            default: e = launch_gru<32>(p, backward, RT, NRS, lds, s); break;
+            case 4: e = launch_gru<4>(p, backward, RT, NRS, s); break;
+            case 8: e = launch_gru<8>(p, backward, RT, NRS, s); break;
+            case 16: e = launch_gru<16>(p, backward, RT, NRS, s); break;
+            default: e = launch_gru<32>(p, backward, RT, NRS, s); break;
         }
     }
     if (e == hipErrorCooperativeLaunchTooLarge) return DDSP_ERANGE;   // the grid cannot be resident at once on this device
@@ -1103,6 +1097,34 @@ int run_gru(GruParams &p, void *scratch, bool backward, hipStream_t s)
         gate.armed = e == hipSuccess;
     }
     return (int)e;
+}
+
+// The entry points' argument checks and GruParams, once per direction (`lowp` / `io_type`: the bf16 variants).
+int run_forward(const float *gi, const float *w_hh, const float *b_hh, const float *h0, float *y, float *hT, float *gates, float *hn,
+                void *scratch, int B, int T, int Hd, int lowp, void *stream)
+{
+    if (B == 0) return 0;
+    if (!gi || !w_hh || !y || !hT || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
+    if ((gates == nullptr) != (hn == nullptr)) return DDSP_EINVAL;
+    GruParams p = {};
+    p.gi = gi; p.w_hh = w_hh; p.b_hh = b_hh; p.h0 = h0; p.y = y; p.hT = hT; p.gates = gates; p.hn = hn;
+    p.B = B; p.T = T; p.Hd = Hd; p.lowp = lowp;
+    return run_gru(p, scratch, false, (hipStream_t)stream);
+}
+
+int run_backward(const float *dy, const float *dhT, const float *w_hh, const float *h0, const float *y, const float *gates, const float *hn,
+                 void *d_gi, void *d_gh, float *dh0, void *scratch, int B, int T, int Hd, int lowp, int io_type, void *stream)
+{
+    if (B == 0) return 0;
+    if (!dy || !w_hh || !y || !gates || !hn || !d_gi || !d_gh || !dh0 || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
+    if (io_type != 0 && io_type != DDSP_IO_BF16) return DDSP_EINVAL;
+    GruParams p = {};
+    p.io16 = io_type == DDSP_IO_BF16;
+    p.dy = dy; p.dhT = dhT; p.w_hh = w_hh; p.h0 = h0; p.y = const_cast<float *>(y);
+    p.gates = const_cast<float *>(gates); p.hn = const_cast<float *>(hn);
+    p.d_gi = (float *)d_gi; p.d_gh = (float *)d_gh; p.dh0 = dh0;
+    p.B = B; p.T = T; p.Hd = Hd; p.lowp = lowp;
+    return run_gru(p, scratch, true, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1120,8 +1142,7 @@ extern "C" int ddsp_gru_max_batch(int Hd, int backward)
     if (device_cus(&cus)) return 0;
     GruPlan pl;
     if (!plan_gru(1, Hd, cus, 1, false, &pl)) return 0;
-    int slots = cus / pl.NW;
-    slots -= slots % 8;
+    const int slots = resident_slots(cus, pl.NW, false);
     if (backward & 2) return (slots - 1) * kMfmaRows;           // bit 1: the bf16 matrix-core variants (<= 16 rows per group)
     return (slots - 1) * ((backward & 1) ? kMaxRowsBwd : kMaxRows);   // also valid in the spread test mode
 }
@@ -1129,55 +1150,27 @@ extern "C" int ddsp_gru_max_batch(int Hd, int backward)
 extern "C" int ddsp_gru_forward(const float *gi, const float *w_hh, const float *b_hh, const float *h0, float *y, float *hT,
                                 float *gates, float *hn, void *scratch, int B, int T, int Hd, void *stream)
 {
-    if (B == 0) return 0;
-    if (!gi || !w_hh || !y || !hT || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
-    if ((gates == nullptr) != (hn == nullptr)) return DDSP_EINVAL;
-    GruParams p = {};
-    p.gi = gi; p.w_hh = w_hh; p.b_hh = b_hh; p.h0 = h0; p.y = y; p.hT = hT; p.gates = gates; p.hn = hn;
-    p.B = B; p.T = T; p.Hd = Hd;
-    return run_gru(p, scratch, false, (hipStream_t)stream);
+    return run_forward(gi, w_hh, b_hh, h0, y, hT, gates, hn, scratch, B, T, Hd, 0, stream);
 }
 
 extern "C" int ddsp_gru_backward(const float *dy, const float *dhT, const float *w_hh, const float *h0, const float *y,
                                  const float *gates, const float *hn, float *d_gi, float *d_gh, float *dh0, void *scratch,
                                  int B, int T, int Hd, void *stream)
 {
-    if (B == 0) return 0;
-    if (!dy || !w_hh || !y || !gates || !hn || !d_gi || !d_gh || !dh0 || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
-    GruParams p = {};
-    p.dy = dy; p.dhT = dhT; p.w_hh = w_hh; p.h0 = h0; p.y = const_cast<float *>(y);
-    p.gates = const_cast<float *>(gates); p.hn = const_cast<float *>(hn);
-    p.d_gi = d_gi; p.d_gh = d_gh; p.dh0 = dh0;
-    p.B = B; p.T = T; p.Hd = Hd;
-    return run_gru(p, scratch, true, (hipStream_t)stream);
+    return run_backward(dy, dhT, w_hh, h0, y, gates, hn, d_gi, d_gh, dh0, scratch, B, T, Hd, 0, 0, stream);
 }
 
 extern "C" int ddsp_gru_forward_bf16(const float *gi, const float *w_hh, const float *b_hh, const float *h0, float *y, float *hT,
                                      float *gates, float *hn, void *scratch, int B, int T, int Hd, void *stream)
 {
-    if (B == 0) return 0;
-    if (!gi || !w_hh || !y || !hT || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
-    if ((gates == nullptr) != (hn == nullptr)) return DDSP_EINVAL;
-    GruParams p = {};
-    p.gi = gi; p.w_hh = w_hh; p.b_hh = b_hh; p.h0 = h0; p.y = y; p.hT = hT; p.gates = gates; p.hn = hn;
-    p.B = B; p.T = T; p.Hd = Hd; p.lowp = 1;
-    return run_gru(p, scratch, false, (hipStream_t)stream);
+    return run_forward(gi, w_hh, b_hh, h0, y, hT, gates, hn, scratch, B, T, Hd, 1, stream);
 }
 
 extern "C" int ddsp_gru_backward_bf16(const float *dy, const float *dhT, const float *w_hh, const float *h0, const float *y,
                                       const float *gates, const float *hn, void *d_gi, void *d_gh, float *dh0, void *scratch,
                                       int B, int T, int Hd, int io_type, void *stream)
 {
-    if (B == 0) return 0;
-    if (!dy || !w_hh || !y || !gates || !hn || !d_gi || !d_gh || !dh0 || !scratch || B < 0 || T <= 0 || Hd <= 0) return DDSP_EINVAL;
-    if (io_type != 0 && io_type != DDSP_IO_BF16) return DDSP_EINVAL;
-    GruParams p = {};
-    p.io16 = io_type == DDSP_IO_BF16;
-    p.dy = dy; p.dhT = dhT; p.w_hh = w_hh; p.h0 = h0; p.y = const_cast<float *>(y);
-    p.gates = const_cast<float *>(gates); p.hn = const_cast<float *>(hn);
-    p.d_gi = (float *)d_gi; p.d_gh = (float *)d_gh; p.dh0 = dh0;
-    p.B = B; p.T = T; p.Hd = Hd; p.lowp = 1;
-    return run_gru(p, scratch, true, (hipStream_t)stream);
+    return run_backward(dy, dhT, w_hh, h0, y, gates, hn, d_gi, d_gh, dh0, scratch, B, T, Hd, 1, io_type, stream);
 }
 
 extern "C" int ddsp_gru_set_mode(int mode)

@@ -27,6 +27,30 @@ def test_gru_is_a_stock_gru_on_cpu():
     assert torch.equal(y0, y1) and torch.equal(h0, h1)
 
 
+# Which kernel instantiation a row reaches (csrc/ddsp_gru.hip: plan_gru, run_gru), on the 256 CUs of an MI355X.  KP = 4 / 8 / 16 / 32
+# for up to 64 / 128 / 256 / 512 hidden units; a group's units take NW = ceil(hd / 16) workgroups, so slots = (256 // NW) rounded
+# down to a multiple of 8 groups fit, and a batch of B rows gets BL = ceil(B / min(B, slots)) rows per group.
+#   fp32 forward   gru_fwd_kernel<KP, 2, NRS>:    NRS = 1 for BL <= 2, else 2
+#   fp32 backward  gru_bwd_kernel<KP, RT, NRS>:   <2, 1> for BL <= 2, <4, 1> for BL = 3..4, <2, 2> for BL >= 5
+#   bf16 forward   gru_fwd_mfma_kernel<KP> for BL >= 2 (one row per group takes the fp32 kernel); bf16 backward gru_bwd_mfma_kernel<KP> always
+#     hd    KP  NW  slots   (B -> BL) of the rows below
+#     12     4   1   256    2 -> 1, 3 -> 1
+#     64     4   4    64    4 -> 1, 70 -> 2, 200 -> 4, 330 -> 6
+#    100     8   7    32    5 -> 1, 40 -> 2, 100 -> 4, 160 -> 5
+#    128     8   8    32    200 -> 7
+#    200    16  13    16    9 -> 1, 20 -> 2, 50 -> 4, 80 -> 5, 250 -> 16 (fp32 forward), 15 + 1 (the others: slices of 240 + 10 rows)
+#    512    32  32     8    1 -> 1, 6 -> 1, 20 -> 3, 32 -> 4, 40 -> 5, 100 -> 13, 150 -> 19 (forward), 14 + 5 (backward: slices of 112 + 38 rows)
+# Between them the rows reach all 28 instantiations: 4 KP x {forward <2,1>, <2,2>; backward <2,1>, <4,1>, <2,2>; bf16 forward; bf16 backward}.
+_ROWS_4_TO_6_PER_GROUP = [
+    (200, 6, 8, 64, True),       # 4 rows per group: forward <4,2,2>, backward <4,4,1>
+    (330, 7, 8, 64, False),      # 6: backward <4,2,2>
+    (100, 8, 8, 100, False),     # 4: forward <8,2,2>, backward <8,4,1>
+    (160, 6, 8, 100, True),      # 5: backward <8,2,2>
+    (50, 7, 8, 200, True),       # 4: forward <16,2,2>, backward <16,4,1>
+    (80, 8, 8, 200, False),      # 5: backward <16,2,2>
+]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,n_in,hd,with_h0", [
     (3, 7, 5, 12, False),        # the fixtures' controller width
@@ -37,7 +61,7 @@ def test_gru_is_a_stock_gru_on_cpu():
     (32, 50, 64, 512, False),    # training shape (BASELINE.json configs[4] widths), 4 rows per group
     (40, 11, 16, 512, True),     # 5 rows per group: two register tiles
     (1, 32, 1024, 512, True),    # live callback: one row, carried state
-])
+] + _ROWS_4_TO_6_PER_GROUP)
 def test_gru_forward_matches_torch_cpu(B, T, n_in, hd, with_h0):
     ref, mine = _pair(n_in, hd, B * 1000 + hd)
     mine = mine.cuda()
@@ -87,7 +111,7 @@ def test_gru_state_carry_equals_one_long_call():
     (32, 40, 64, 512, True),
     (150, 5, 8, 512, False),     # more rows than one backward launch takes: split into slices
     (20, 6, 8, 512, True),       # 3 rows per group (partial register tile)
-])
+] + _ROWS_4_TO_6_PER_GROUP)
 def test_gru_backward_matches_torch_cpu_autograd(B, T, n_in, hd, with_h0):
     ref, mine = _pair(n_in, hd, B + hd)
     mine = mine.cuda()
@@ -307,7 +331,8 @@ def test_gru_stacked_layers_match_torch_cpu():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,hd,with_h0", [(4, 30, 64, True), (32, 60, 512, False), (9, 17, 200, True), (40, 12, 512, True), (1, 32, 512, True),
-                                            (200, 6, 128, False), (100, 8, 512, True), (250, 5, 200, False)])   # > 4 rows per group: matrix-core forward
+                                            (200, 6, 128, False), (100, 8, 512, True), (250, 5, 200, False),   # > 4 rows per group: matrix-core forward
+                                            (70, 7, 64, False), (40, 8, 100, True), (20, 6, 200, True)])      # 2 rows per group: forward <4>, <8>, <16>
 def test_gru_bf16_matrix_core_variant_tracks_fp32(B, T, hd, with_h0):
     """The autocast variants (ddsp_gru_*_bf16: bf16 MFMA products, fp32 everything else) against the fp32 kernels on the same
     inputs: equal up to bf16 rounding of h and W in the products (|dh| ~ 1e-3), gradients with cosine >= 0.999; status 0."""
