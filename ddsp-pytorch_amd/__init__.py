@@ -16,6 +16,7 @@ from .graphed import GraphedSynth, GraphedLiveDecoder, GraphedTrainStep  # noqa:
 from .gru import GRU, gru_forward, gru_backward, gru_status  # noqa: F401
 from .decoder import Controller, Decoder  # noqa: F401
 from .encoder import Crepe, F0Encoder, LoudnessEncoder, Encoder  # noqa: F401
+from .encoder import pitch_argmax, pitch_centered, pitch_weighted, pitch_viterbi  # noqa: F401
 from .autoencoder import AutoEncoder  # noqa: F401
 from .dataset import AudioData, PLHDataset, load_audio, example_geometry  # noqa: F401
 from .spectral import griffinlim  # noqa: F401

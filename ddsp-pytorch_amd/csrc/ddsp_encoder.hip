@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "ddsp_hip.h"
+#include "ddsp_internal.h"
 
 namespace {
 
@@ -145,14 +146,6 @@ __global__ void __launch_bounds__(256) crepe_epilogue_kernel(const float *__rest
         const float v1 = __fmaf_rn((relu_nan(src[1] + bc) - m) * inv, g, bt);
         out[e] = max_nan(v0, v1);
     }
-}
-
-// (value, bin) that torch.argmax keeps of two candidates: the first NaN, else the larger value, ties to the lower bin
-__device__ __forceinline__ bool takes_over(float va, int ia, float vb, int ib)
-{
-    const bool na = va != va, nb = vb != vb;
-    if (na || nb) return na && nb ? ia < ib : na;
-    return va > vb || (va == vb && ia < ib);
 }
 
 // one wavefront per frame: lane l owns bins l, l + 64, ...; probabilities are written as they are computed

@@ -50,3 +50,11 @@ __device__ __forceinline__ I reflect_index(I i, I L)
     if (i >= L) i = 2 * (L - 1) - i;
     return i;
 }
+
+// (value, bin) that torch.argmax keeps of two candidates: the first NaN, else the larger value, ties to the lower bin
+__device__ __forceinline__ bool takes_over(float va, int ia, float vb, int ib)
+{
+    const bool na = va != va, nb = vb != vb;
+    if (na || nb) return na && nb ? ia < ib : na;
+    return va > vb || (va == vb && ia < ib);
+}

@@ -2,13 +2,16 @@
 
   Crepe            the CREPE pitch network ('tiny' / 'full'); parameter and buffer names as crepe/crepe.py:12-91, so that a
                    CREPE `.pth` state dict loads with strict=True
-  F0Encoder        resample to 16 kHz -> normalise -> frame by 1024 -> CREPE -> argmax pitch (encoder.py:13-88, 120-128)
+  F0Encoder        resample to 16 kHz -> normalise -> frame by 1024 -> CREPE -> pitch (encoder.py:13-128): the argmax bin by
+                   default, or the nine-bin weighted average around the argmax ('weighted') or around a Viterbi path ('viterbi')
+  pitch_argmax, pitch_centered, pitch_weighted, pitch_viterbi   the decoders themselves, over probabilities [B, T, 360]
   LoudnessEncoder  A-weighted loudness of the un-windowed STFT (encoder.py:131-156)
   Encoder          both, as the dict {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177)
 
-On CUDA tensors the work runs on hand-written HIP (csrc/ddsp_encoder.hip, csrc/ddsp_loudness.hip; include/ddsp_hip.h) around
-the library work it keeps: CREPE's convolutions on MIOpen (F.conv1d on a [N, C, L] view of the (k, 1) weights) and its
-classifier on rocBLAS.  CPU tensors run the reference's arithmetic as stock torch ops (the restatement the fixtures pin).
+On CUDA tensors the work runs on hand-written HIP (csrc/ddsp_encoder.hip, csrc/ddsp_pitch.hip, csrc/ddsp_loudness.hip;
+include/ddsp_hip.h) around the library work it keeps: CREPE's convolutions on MIOpen (F.conv1d on a [N, C, L] view of the
+(k, 1) weights) and its classifier on rocBLAS.  CPU tensors run the reference's arithmetic as stock torch ops (the
+restatement the fixtures pin).
 
 Two pieces restate libraries the reference imports and this package does not have; their parity with those libraries
 cannot be pinned here:
@@ -33,6 +36,10 @@ import torch.nn.functional as F
 from . import _lib
 
 PITCH_BINS = 360
+PITCH_DECODERS = ('argmax', 'weighted', 'viterbi')
+CENTS_OF_BIN_0 = 1997.3794084376191
+CENTERED_HALF_WIDTH = 4                  # pitch_centered averages bins c - 4 .. c + 4
+VITERBI_BAND = 11                        # a Viterbi path moves at most 11 bins (220 cents) per frame
 CREPE_RATE = 16000
 CREPE_WINDOW = 1024
 _BN_EPS = 0.0010000000474974513          # the MMdnn-converted CREPE's BatchNorm epsilon
@@ -187,6 +194,178 @@ def pitch_tables():
     return 10 * 2 ** (cents / 1200), bins / 359.
 
 
+# ------------------------------------------------------------------------------------------------------------ pitch decoders
+# Definitions: DESIGN.md section 10.  CUDA fp32 tensors run csrc/ddsp_pitch.hip; CPU tensors run the same definitions as stock
+# torch / numpy ops (the Viterbi recurrence in fp64).
+
+def _cents_map(bins):
+    return bins * 20 + CENTS_OF_BIN_0
+
+
+def _freq_map(cents):
+    return 10 * 2 ** (cents / 1200)
+
+
+def viterbi_log_transition() -> torch.Tensor:
+    """log A as the kernel reads it: [360, 23] fp32 indexed by target bin j and k - j + 11, A[k][j] = max(12 - |k - j|, 0) / S_k
+    with S_k the row sum (144 in the interior, less within 11 bins of an end); -inf where k is outside 0 .. 359.  Built in
+    fp64 and rounded once."""
+    k = np.arange(PITCH_BINS)
+    A = np.maximum(VITERBI_BAND + 1 - np.abs(k[:, None] - k[None, :]), 0).astype(np.float64)
+    A /= A.sum(axis=1, keepdims=True)
+    table = np.full((PITCH_BINS, 2 * VITERBI_BAND + 1), -np.inf)
+    for d in range(2 * VITERBI_BAND + 1):
+        src = k + d - VITERBI_BAND
+        ok = (src >= 0) & (src < PITCH_BINS)
+        table[k[ok], d] = np.log(A[src[ok], k[ok]])
+    return torch.from_numpy(table.astype(np.float32))
+
+
+_DEVICE_TABLES = {}
+
+
+def _tables_on(device, build):
+    """The host tables `build()` returns, copied to `device` once (a copy per call would also keep a caller out of a graph)."""
+    key = (build.__name__, str(device))
+    if key not in _DEVICE_TABLES:
+        made = build()
+        _DEVICE_TABLES[key] = tuple(t.to(device) for t in made) if isinstance(made, tuple) else made.to(device)
+    return _DEVICE_TABLES[key]
+
+
+def _decoder_input(probabilities: torch.Tensor, what: str) -> torch.Tensor:
+    if probabilities.dim() != 3 or probabilities.shape[-1] != PITCH_BINS:
+        raise ValueError(f"{what}: probabilities must be [B, T, {PITCH_BINS}], got {tuple(probabilities.shape)}")
+    _refuse_grad(probabilities, what)
+    if probabilities.is_cuda:
+        return probabilities.detach().contiguous().float()
+    return probabilities.detach()
+
+
+def _centered_device(center, p: torch.Tensor):
+    """ddsp_pitch_centered: center None = the kernel's own argmax.  -> (freq, harmonicity, normalized_cents, bins int32 [B, T])"""
+    B, T = p.shape[:2]
+    out = torch.empty((3, B, T, 1), device=p.device, dtype=torch.float32)
+    bins = torch.empty((B, T), device=p.device, dtype=torch.int32)
+    if center is not None:
+        center = center.to(device=p.device, dtype=torch.int32).reshape(B, T).contiguous()
+    with torch.cuda.device(p.device):
+        rc = _lib.lib().ddsp_pitch_centered(p.data_ptr(), center.data_ptr() if center is not None else None, out[0].data_ptr(),
+                                            out[1].data_ptr(), out[2].data_ptr(), bins.data_ptr(), B * T,
+                                            torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_pitch_centered")
+    return out[0], out[1], out[2], bins
+
+
+def pitch_argmax(probabilities: torch.Tensor):
+    """encoder.py:120-128: -> (freq, harmonicity, normalized_cents) of each frame's argmax bin, each [B, T, 1]."""
+    p = _decoder_input(probabilities, "pitch_argmax")
+    if p.is_cuda:
+        _, harmonicity, _, bins = _centered_device(None, p)
+        f0_table, cents_table = _tables_on(p.device, pitch_tables)
+        bins = bins.long().unsqueeze(-1)
+        return f0_table[bins], harmonicity, cents_table[bins]
+    bins = p.argmax(dim=-1, keepdim=True)
+    return _freq_map(_cents_map(bins)), p.gather(-1, bins), bins / 359.
+
+
+def pitch_centered(center: torch.Tensor, probabilities: torch.Tensor):
+    """The weighted average of the bins center - 4 .. center + 4 (those inside 0 .. 359), every probability with its own
+    bin's cents: -> (freq, harmonicity, normalized_cents), each [B, T, 1]; center [B, T, 1] integer bins.  The reference's
+    method of this name (encoder.py:95-118) pairs the nine probabilities with a rotated list of cents; this is its evident
+    intent."""
+    p = _decoder_input(probabilities, "pitch_centered")
+    B, T = p.shape[:2]
+    if tuple(center.shape) != (B, T, 1) or center.dtype.is_floating_point:
+        raise ValueError(f"pitch_centered: center must be integer bins [B, T, 1] = {(B, T, 1)}, got {center.dtype} {tuple(center.shape)}")
+    if p.is_cuda:
+        return _centered_device(center, p)[:3]
+    center = center.long().clamp(0, PITCH_BINS - 1)
+    p = p.float()
+    idx = center + torch.arange(-CENTERED_HALF_WIDTH, CENTERED_HALF_WIDTH + 1)
+    w = p.gather(-1, idx.clamp(0, PITCH_BINS - 1))
+    w = torch.where((idx >= 0) & (idx < PITCH_BINS), w, torch.zeros((), dtype=w.dtype))
+    num = torch.zeros((B, T, 1), dtype=torch.float32)
+    den = torch.zeros((B, T, 1), dtype=torch.float32)
+    for i in range(2 * CENTERED_HALF_WIDTH + 1):             # ascending offsets, as the kernel sums them
+        num = num + float(i - CENTERED_HALF_WIDTH) * w[..., i:i + 1]
+        den = den + w[..., i:i + 1]
+    offset = (20 * (num / den)).double()                     # the fp32 quantity; the rest in fp64, rounded once (as the kernel)
+    base = (center * 20).double()
+    cents = (base + CENTS_OF_BIN_0) + offset
+    return _freq_map(cents).float(), p.gather(-1, center), ((base + offset) / (20. * (PITCH_BINS - 1))).float()
+
+
+def pitch_weighted(probabilities: torch.Tensor):
+    """encoder.py:91-93: pitch_centered around each frame's own argmax."""
+    p = _decoder_input(probabilities, "pitch_weighted")
+    if p.is_cuda:
+        return _centered_device(None, p)[:3]
+    return pitch_centered(p.argmax(dim=-1, keepdim=True), p)
+
+
+def _viterbi_host(p: np.ndarray, state):
+    """The recurrence of ddsp_pitch_viterbi in fp64 numpy: p [B, T, 360] -> (bins int64 [B, T], last scores [B, 360])."""
+    B, T, _ = p.shape
+    log_a = viterbi_log_transition().numpy().astype(np.float64)
+    e = np.log(np.fmax(p.astype(np.float64), np.float64(np.float32(1e-30))))       # fmax drops a NaN
+
+    def step(v):
+        padded = np.full((B, PITCH_BINS + 2 * VITERBI_BAND), -np.inf)
+        padded[:, VITERBI_BAND:VITERBI_BAND + PITCH_BINS] = v
+        cand = np.stack([padded[:, d:d + PITCH_BINS] for d in range(2 * VITERBI_BAND + 1)], axis=-1) + log_a
+        arg = cand.argmax(axis=-1)                                                    # first maximum: the lower predecessor
+        return np.take_along_axis(cand, arg[..., None], axis=-1)[..., 0], arg - VITERBI_BAND
+
+    back = np.zeros((B, T, PITCH_BINS), dtype=np.int64)
+    v = e[:, 0] if state is None else step(np.asarray(state, dtype=np.float64))[0] + e[:, 0]
+    for t in range(1, T):
+        best, back[:, t] = step(v)
+        v = best + e[:, t]
+    bins = np.empty((B, T), dtype=np.int64)
+    s = v.argmax(axis=-1)                                                             # first maximum: the lower final state
+    bins[:, T - 1] = s
+    rows = np.arange(B)
+    for t in range(T - 1, 0, -1):
+        s = s + back[rows, t, s]
+        bins[:, t - 1] = s
+    return bins, v - v.max(axis=-1, keepdims=True)
+
+
+def pitch_viterbi(probabilities: torch.Tensor, state=None, return_state: bool = False):
+    """The bins [B, T, 1] (int64) of the path maximising sum_t log max(p_t[s_t], 1e-30) + sum_{t >= 1} log A[s_{t-1}][s_t]
+    under the triangular +-11-bin transition of `viterbi_log_transition`; ties go to the lower predecessor and to the lower
+    final state, and a NaN frame is uninformative.  `state` [B, 360] fp32 (the scores a previous call returned) replaces
+    the uniform prior, so a block-wise caller can carry the recurrence across calls; with a state, or return_state=True,
+    the result is (bins, state).  Scores are defined up to one constant per row."""
+    p = _decoder_input(probabilities, "pitch_viterbi")
+    B, T = p.shape[:2]
+    if T < 1:
+        raise ValueError("pitch_viterbi: needs at least one frame")
+    if state is not None and tuple(state.shape) != (B, PITCH_BINS):
+        raise ValueError(f"pitch_viterbi: state must be [B, {PITCH_BINS}] = {(B, PITCH_BINS)}, got {tuple(state.shape)}")
+    want_state = return_state or state is not None
+    if p.is_cuda:
+        L = _lib.lib()
+        bins = torch.empty((B, T), device=p.device, dtype=torch.int32)
+        if state is not None:
+            state = state.to(device=p.device, dtype=torch.float32).contiguous()
+        out = torch.empty((B, PITCH_BINS), device=p.device, dtype=torch.float32) if want_state else None
+        nbytes = L.ddsp_pitch_viterbi_workspace_bytes(B, T)
+        work = torch.empty(nbytes, device=p.device, dtype=torch.uint8) if nbytes else None
+        with torch.cuda.device(p.device):
+            rc = L.ddsp_pitch_viterbi(p.data_ptr(), _tables_on(p.device, viterbi_log_transition).data_ptr(),
+                                      state.data_ptr() if state is not None else None, out.data_ptr() if want_state else None,
+                                      bins.data_ptr(), work.data_ptr() if nbytes else None, B, T,
+                                      torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_pitch_viterbi")
+        bins = bins.long().unsqueeze(-1)
+        return (bins, out) if want_state else bins
+    path, last = _viterbi_host(p.float().numpy(), None if state is None else state.detach().cpu().numpy())
+    bins = torch.from_numpy(path).unsqueeze(-1)
+    return (bins, torch.from_numpy(last.astype(np.float32))) if want_state else bins
+
+
 def _load_crepe_weights(weights):
     if isinstance(weights, (str, os.PathLike)):
         return torch.load(weights, map_location="cpu", weights_only=True)
@@ -199,10 +378,20 @@ class F0Encoder(nn.Module):
 
     The reference loads crepe/pretrained/{capacity}.pth from its own tree; this package ships no weights, so they come from
     `weights` (a path to a CREPE state dict or the dict itself), else from `conf.crepe_weights`.  With neither it raises
-    rather than run untrained weights."""
+    rather than run untrained weights.
 
-    def __init__(self, conf, weights=None):
+    `decoder` (else conf.pitch_decoder, else 'argmax') chooses how the probabilities become a pitch: 'argmax' (the
+    reference's forward), 'weighted' (pitch_weighted) or 'viterbi' (pitch_centered around the bins of pitch_viterbi)."""
+
+    def __init__(self, conf, weights=None, decoder=None):
         super().__init__()
+        if decoder is None:
+            decoder = getattr(conf, 'pitch_decoder', 'argmax')
+        if decoder not in PITCH_DECODERS:
+            raise ValueError(f"pitch decoder {decoder!r}: expected one of {PITCH_DECODERS}")
+        self.decoder = decoder
+        self.min_cents = self.cents_map(0)
+        self.max_cents = self.cents_map(PITCH_BINS - 1)
         self.hop_length = conf.hop_length
         self.window_size = conf.n_fft
         self.rs = Resample(conf.sample_rate, CREPE_RATE)
@@ -219,6 +408,35 @@ class F0Encoder(nn.Module):
         f0_table, cents_table = pitch_tables()
         self.register_buffer("f0_table", f0_table, persistent=False)
         self.register_buffer("cents_table", cents_table, persistent=False)
+
+    @staticmethod
+    def cents_map(bins):
+        return _cents_map(bins)
+
+    def normalize_cents(self, cents):
+        return (cents - self.min_cents) / (self.max_cents - self.min_cents)
+
+    @staticmethod
+    def freq_map(cents):
+        return _freq_map(cents)
+
+    def pitch_argmax(self, probabilities):
+        return pitch_argmax(probabilities)
+
+    def pitch_centered(self, center, probabilities):
+        return pitch_centered(center, probabilities)
+
+    def pitch_weighted(self, probabilities):
+        return pitch_weighted(probabilities)
+
+    def pitch_viterbi(self, probabilities, state=None):
+        return pitch_viterbi(probabilities, state)
+
+    def decode(self, probabilities: torch.Tensor):
+        """probabilities [B, T, 360] -> (freq, harmonicity, normalized_cents) by this encoder's decoder."""
+        if self.decoder == 'viterbi':
+            return pitch_centered(pitch_viterbi(probabilities), probabilities)
+        return pitch_weighted(probabilities) if self.decoder == 'weighted' else pitch_argmax(probabilities)
 
     def resampled_hop(self, orig_len: int, resampled_len: int) -> int:
         """encoder.py:66-69 in Python arithmetic; refuses inputs shorter than one frame."""
@@ -242,6 +460,9 @@ class F0Encoder(nn.Module):
             x = x.unfold(1, CREPE_WINDOW, hop)
             B, T = x.shape[:2]
             probabilities = self.model(x.reshape(-1, CREPE_WINDOW)).reshape(B, T, PITCH_BINS)
+            if self.decoder != 'argmax':
+                freq, harmonicity, normalized_cents = self.decode(probabilities)
+                return freq, harmonicity, probabilities, normalized_cents
             bins = probabilities.argmax(dim=-1, keepdim=True)
             freq = 10 * 2 ** ((bins * 20 + 1997.3794084376191) / 1200)
             return freq, probabilities.gather(-1, bins), probabilities, bins / 359.
@@ -266,6 +487,9 @@ class F0Encoder(nn.Module):
                                      self.cents_table.data_ptr(), probs.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
                                      out[2].data_ptr(), N, stream)
             _lib.check(rc, "ddsp_pitch_decode")
+            if self.decoder != 'argmax':
+                freq, harmonicity, normalized_cents = self.decode(probs)
+                return freq, harmonicity, probs, normalized_cents
         return out[0], out[1], probs, out[2]
 
 

@@ -378,6 +378,32 @@ int ddsp_pitch_decode(const float *logits, const float *bias, const float *f0_ta
                       float *harmonicity, float *cents, long N, void *stream);
 
 /*
+ * Pitch decoders over the probabilities ddsp_pitch_decode wrote.  All fp32, dense row-major; bins are int32.
+ *
+ * ddsp_pitch_centered  probs [N, 360], center [N] (bins in 0 .. 359; NULL: the frame's own torch argmax, first NaN wins, ties to
+ *                    the lower bin) -> with w_i = probs[c + i] for i = -4 .. 4 inside 0 .. 359, else 0:
+ *                      cents = (20 c + 1997.3794084376191) + 20 (sum_i i w_i) / (sum_i w_i)   (both sums in ascending i)
+ *                      f0 = 10 * 2^(cents / 1200), harmonicity = probs[c], normalized_cents = (20 c + offset) / 7180,
+ *                    every probability with its own bin's cents (the reference's pitch_centered pairs them rotated,
+ *                    encoder.py:95-118).  NaN probabilities give NaN outputs.  bins_out [N] (may be NULL) receives c.
+ * ddsp_pitch_viterbi probs [B, T, 360] -> bins [B, T], the path maximising
+ *                      sum_t e_t[s_t] + sum_{t >= 1} log_trans[s_t][s_{t-1} - s_t + 11],   e_t[j] = log(max(probs[t][j], 1e-30))
+ *                    (the max drops a NaN), over paths that move at most 11 bins per frame; ties go to the lower predecessor
+ *                    and to the lower final state.  log_trans [360, 23], indexed by target bin j and k - j + 11, is the log of
+ *                    the caller's transition matrix, -inf where k is outside 0 .. 359.  state_in [B, 360] (NULL: a uniform
+ *                    prior) holds scores v of the frame before the first: v_0[j] = e_0[j] + max_k (state_in[k] + log A[k][j]);
+ *                    state_out [B, 360] (may be NULL) receives the last frame's scores, which are defined up to one
+ *                    constant per row (the kernel re-centres them as it goes).  One launch, no allocation, no host
+ *                    synchronisation.  Back-pointers stay in LDS while T <= 446; longer rows need `workspace` of
+ *                    ddsp_pitch_viterbi_workspace_bytes(B, T) bytes (0 while they fit; 4-byte aligned).  Rows are independent.
+ */
+int ddsp_pitch_centered(const float *probs, const int *center, float *f0, float *harmonicity, float *normalized_cents, int *bins_out,
+                        long N, void *stream);
+size_t ddsp_pitch_viterbi_workspace_bytes(long B, long T);
+int ddsp_pitch_viterbi(const float *probs, const float *log_trans, const float *state_in, float *state_out, int *bins, void *workspace,
+                       long B, long T, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
