@@ -54,6 +54,7 @@ namespace {
 #ifndef DDSP_TURN_EVERY
 #define DDSP_TURN_EVERY 8    // synth walk: samples between two looks at the clock (divides 32)
 #endif
+constexpr int kTotalsTurnEvery = 16;   // totals walk: the same (a multiple of 4 that divides 32)
 constexpr int kRow = 256 + 4;          // staging row: one float per thread of the workgroup, padded
 constexpr float kReuseMaxInc = 4.8f;   // quotient reuse: r = P - q*2pi32 stays exact while |r| < 8, i.e. increments < 8 - pi
 
@@ -396,19 +397,19 @@ __device__ __forceinline__ void walk_totals(const OscParams &p, double (&acc)[K]
     float lam, dlam;
     segment_lambda(p, n_beg, clamp0, lam, dlam);
     float mal = 1.0f - lam;
-    for (int nb = n_beg; nb < n_end; nb += 16) {
+    static_assert(kTotalsTurnEvery % 4 == 0 && 32 % kTotalsTurnEvery == 0, "pieces are multiples of 32 samples");
+    for (int nb = n_beg; nb < n_end; nb += kTotalsTurnEvery) {
     take_turn(slot, p.nres, p.turn_shift);
-    for (int n = nb; n < nb + 16; ++n) {
-        const float w1 = lam, w0 = mal;
-        lam += dlam;
-        mal -= dlam;
+    for (int n = nb; n < nb + kTotalsTurnEvery; n += 4) {   // four samples unrolled: one block, no copy of the weights
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
         float v[K];
         DDSP_STAGE_END();
 #pragma unroll
-        for (int m = 0; m < K; ++m) v[m] = w1 * x1[m];
+        for (int m = 0; m < K; ++m) v[m] = lam * x1[m];
         DDSP_STAGE_END();
 #pragma unroll
-        for (int m = 0; m < K; ++m) v[m] = __fmaf_rn(w0, x0[m], v[m]);
+        for (int m = 0; m < K; ++m) v[m] = __fmaf_rn(mal, x0[m], v[m]);
         DDSP_STAGE_END();
         double d[K];
 #pragma unroll
@@ -417,6 +418,9 @@ __device__ __forceinline__ void walk_totals(const OscParams &p, double (&acc)[K]
 #pragma unroll
         for (int m = 0; m < K; ++m) acc[m] += d[m];
         DDSP_STAGE_END();
+        lam += dlam;   // (in place, after their last use: no copies)
+        mal -= dlam;
+    }
     }
     }
 }
@@ -448,9 +452,9 @@ __global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(
     }
     int hmax = 0;       // highest harmonic number of this lane with a non-zero amplitude (NaN counts) at any row the chunk interpolates from
 
-    // row r of this lane's batch row: increments (:26-35) and masked, normalised amplitudes (:31-33) of EVERY slot; stored by the
-    // chunk in which the row first becomes the NEWER row of a segment (every row exactly once).  The root slots' increments
-    // come back in w.
+    // row r of this lane's batch row: increments (:26-35) of the ROOT slots -- which come back in w -- and masked, normalised
+    // amplitudes (:31-33) of every slot; stored by the chunk in which the row first becomes the NEWER row of a segment (every
+    // row exactly once).
     auto make_row = [&](int r, float (&w)[KR]) {
         const float fb = p.f0[rowbase + r];
         const unsigned crow = ((unsigned)k.b * p.T + r) * p.H;
@@ -470,17 +474,26 @@ __global__ void __launch_bounds__(256, K <= 13 ? 3 : 1) osc_chunk_totals_kernel(
         const float rs = 1.0f / s;                                 // 0 * inf = NaN for an all-masked frame (:33)
         const int seg_start = max(r * p.R - (p.R >> 1), 0);
         const bool own = k.active && seg_start >= i_beg && seg_start < k.i_end;
+        float amp[K];
 #pragma unroll
         for (int m = 0; m < K; ++m) {
             const int h = hs[m];
             const bool ok = h < p.H;
-            const float wv = ok ? frame_increment(h, fb, p.sr) : 0.0f;
-            if (m < KR) w[m < KR ? m : 0] = wv;
-            const float amp = ok ? a0[m] * rs : 0.0f;
-            if (amp != 0.0f) hmax = max(hmax, h + 1);
-            if (ok && own) {
-                p.w[crow + h] = wv;
-                p.amp[crow + h] = amp;
+            if (m < KR) {   // (a derived slot's increment has no reader; the division is unconditional and a select zeroes padding)
+                const float wv = frame_increment(h, fb, p.sr);
+                w[m < KR ? m : 0] = ok ? wv : 0.0f;
+            }
+            amp[m] = ok ? a0[m] * rs : 0.0f;
+            if (amp[m] != 0.0f) hmax = max(hmax, h + 1);
+        }
+        if (own) {   // one predicate for the whole row; a padded slot writes nothing
+#pragma unroll
+            for (int m = 0; m < K; ++m) {
+                const int h = hs[m];
+                if (h < p.H) {
+                    if (m < KR) p.w[crow + h] = w[m < KR ? m : 0];
+                    p.amp[crow + h] = amp[m];
+                }
             }
         }
     };
