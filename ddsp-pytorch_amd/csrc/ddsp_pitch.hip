@@ -3,6 +3,9 @@
 //                          probability with its own bin's cents), the centre given or the frame's own torch argmax
 //   pitch_viterbi_kernel   the maximum-score path over frames under a triangular +-11-bin transition: T dependent steps
 //                          of a 360 x 23 max-plus and the backtrack, in one launch
+// and what follows a decoder:
+//   pitch_voicing_kernel   periodicity median and hysteresis, loudness gate, median-filtered voiced pitch, unvoiced gaps
+//                          kept, held or interpolated: one wavefront per row, one launch
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -223,6 +226,216 @@ pitch_viterbi_kernel(const float *__restrict__ probs, const float *__restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ voicing
+// ddsp_pitch_voicing: what follows a pitch decoder.  One wavefront per row, three sweeps over tiles
+// of 64 frames with a wave-uniform carry from tile to tile:
+//   A  forward   periodicity median, hysteresis (a scan over the maps set / clear / keep), gate -> m
+//   B  forward   pitch median among the gated frames of the window -> the chosen frame u*, and the last voiced frame so far
+//   C  backward  the next voiced frame, then every frame's outputs
+// Between the sweeps a row keeps m (one byte per frame between zero margins of four, so that a window needs no bounds
+// test), u* and the previous voiced frame (one int each) in LDS, or in the caller's workspace for rows beyond kVoiceLdsFrames.
+
+constexpr int kVoiceHalf = 4;                   // the widest window reaches four frames either side
+constexpr int kVoiceSlots = 2 * kVoiceHalf + 1;
+constexpr int kVoiceLdsFrames = 4096;           // 9 bytes per frame: 36 KiB of LDS at most
+constexpr int kNoFrame = 0x7fffffff;            // "no voiced frame after this one", and the index of a masked median entry
+constexpr int kNoneBefore = -2;                 // "no voiced frame before this one"; -1 is the carried state's virtual frame
+enum { kKeep = 0, kSet = 1, kClear = 2 };
+
+struct VoiceKey {
+    float v;
+    int i;
+};
+
+__device__ __forceinline__ void key_order(VoiceKey &a, VoiceKey &b)
+{
+    const bool swap = b.v < a.v || (b.v == a.v && b.i < a.i);
+    const VoiceKey lo = swap ? b : a, hi = swap ? a : b;
+    a = lo;
+    b = hi;
+}
+
+// Element (count - 1) div 2 of the nine keys in ascending (value, index) order; the 9 - count masked entries are
+// (+inf, kNoFrame) and sort last.  A 25-exchange network; count >= 1 wherever the result is used.
+__device__ __forceinline__ VoiceKey lower_median(VoiceKey (&s)[kVoiceSlots], int count)
+{
+    key_order(s[0], s[3]); key_order(s[1], s[7]); key_order(s[2], s[5]); key_order(s[4], s[8]);
+    key_order(s[0], s[7]); key_order(s[2], s[4]); key_order(s[3], s[8]); key_order(s[5], s[6]);
+    key_order(s[0], s[2]); key_order(s[1], s[3]); key_order(s[4], s[5]); key_order(s[7], s[8]);
+    key_order(s[1], s[4]); key_order(s[3], s[6]); key_order(s[5], s[7]);
+    key_order(s[0], s[1]); key_order(s[2], s[4]); key_order(s[3], s[5]); key_order(s[6], s[8]);
+    key_order(s[2], s[3]); key_order(s[4], s[5]); key_order(s[6], s[7]);
+    key_order(s[1], s[2]); key_order(s[3], s[4]); key_order(s[5], s[6]);
+    const int r = (count - 1) >> 1;
+    VoiceKey k = s[0];
+#pragma unroll
+    for (int i = 1; i <= kVoiceHalf; ++i)
+        if (r == i) k = s[i];
+    return k;
+}
+
+// a row's intermediates: two ints per frame, then the m bytes with their margins, rounded up to whole ints
+__host__ __device__ __forceinline__ long voicing_row_bytes(long T) { return 8 * T + ((T + 2 * kVoiceHalf + 3) & ~3l); }
+
+template <bool kLds>
+__global__ void __launch_bounds__(64)
+pitch_voicing_kernel(const float *__restrict__ f0, const float *__restrict__ ncents, const float *__restrict__ period,
+                     const float *__restrict__ loud, const float *__restrict__ state_in, float *__restrict__ f0_out,
+                     float *__restrict__ n_out, unsigned char *__restrict__ voiced_out, float *__restrict__ period_out,
+                     float *__restrict__ state_out, unsigned char *__restrict__ workspace, int T, int half_p, int half_f,
+                     float upper, float lower, float silence, int fill)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char voice_lds[];
+    const int lane = threadIdx.x;
+    const long row = blockIdx.x;
+    unsigned char *store = kLds ? voice_lds : workspace + row * voicing_row_bytes(T);
+    int *sel = (int *)store;                    // u* of a voiced frame, -1 for an unvoiced one
+    int *prv = sel + T;                         // the last voiced frame at or before this one
+    unsigned char *mm = store + 8l * T;         // m[t] at mm[t + 4]
+    const float *p = period + row * T, *n = ncents + row * T, *f = f0 + row * T;
+    const float *ld = loud ? loud + row * T : nullptr;
+    const bool carried = state_in != nullptr;
+    const float last_n = carried ? state_in[row * 3 + 1] : NAN;
+    const float last_f = carried ? state_in[row * 3 + 2] : NAN;
+
+    if (lane < 2 * kVoiceHalf) mm[lane < kVoiceHalf ? lane : T + lane] = 0;
+
+    // A
+    int v_carry = carried && state_in[row * 3] != 0.0f;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool in = t < T;
+        VoiceKey s[kVoiceSlots];
+        int count = 0;
+#pragma unroll
+        for (int j = 0; j < kVoiceSlots; ++j) {
+            const int d = j - kVoiceHalf, u = t + d;
+            const bool ok = in && u >= 0 && u < T && (d < 0 ? -d : d) <= half_p;
+            float q = p[ok ? u : 0];
+            q = q != q ? 0.0f : q;
+            s[j].v = ok ? q : INFINITY;
+            s[j].i = ok ? u : kNoFrame;
+            count += ok;
+        }
+        const float ps = lower_median(s, count).v;
+        int x = !in ? kKeep : (ps >= upper ? kSet : (ps < lower ? kClear : kKeep));
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {      // inclusive scan: second == keep ? first : second
+            const int first = __shfl_up(x, o);
+            if (lane >= o && x == kKeep) x = first;
+        }
+        const int v = x == kKeep ? v_carry : (x == kSet);
+        v_carry = __shfl(v, 63);
+        if (in) {
+            const float nt = n[t];
+            const bool m = v && fabsf(nt) < INFINITY && (!ld || ld[t] >= silence);   // a NaN compares false in both tests
+            mm[t + kVoiceHalf] = m;
+            voiced_out[row * T + t] = m;
+            if (period_out) period_out[row * T + t] = ps;
+        }
+    }
+    __syncthreads();
+
+    // B
+    int a_carry = (carried && last_n == last_n) ? -1 : kNoneBefore;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool in = t < T;
+        const bool m = in && mm[t + kVoiceHalf];
+        VoiceKey s[kVoiceSlots];
+        int count = 0;
+#pragma unroll
+        for (int j = 0; j < kVoiceSlots; ++j) {
+            const int d = j - kVoiceHalf, u = t + d;
+            const bool ok = m && (d < 0 ? -d : d) <= half_f && mm[u + kVoiceHalf];     // the zero margins bound u
+            const float nu = n[ok ? u : 0];
+            s[j].v = ok ? nu : INFINITY;
+            s[j].i = ok ? u : kNoFrame;
+            count += ok;
+        }
+        const VoiceKey k = lower_median(s, count);
+        int a = m ? t : kNoneBefore;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int before = __shfl_up(a, o);
+            if (lane >= o) a = max(a, before);
+        }
+        a = max(a, a_carry);
+        a_carry = __shfl(a, 63);
+        if (in) {
+            sel[t] = m ? k.i : -1;
+            prv[t] = a;
+        }
+    }
+    __syncthreads();
+
+    if (state_out && lane == 0) {
+        float sn = NAN, sf = NAN;
+        if (a_carry >= 0) {
+            const int u = sel[a_carry];
+            sn = n[u];
+            sf = f[u];
+        } else if (a_carry == -1) {
+            sn = last_n;
+            sf = last_f;
+        }
+        state_out[row * 3] = v_carry ? 1.0f : 0.0f;
+        state_out[row * 3 + 1] = sn;
+        state_out[row * 3 + 2] = sf;
+    }
+
+    // C
+    int b_carry = kNoFrame;
+    for (int t0 = ((T - 1) >> 6) << 6; t0 >= 0; t0 -= 64) {
+        const int t = t0 + lane;
+        const bool in = t < T;
+        const int own = in ? sel[t] : -1;
+        int b = own >= 0 ? t : kNoFrame;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int after = __shfl_down(b, o);
+            if (lane + o < 64) b = min(b, after);
+        }
+        b = min(b, b_carry);
+        b_carry = __shfl(b, 0);
+        if (!in) continue;
+        float nn, ff;
+        if (own >= 0) {
+            nn = n[own];
+            ff = f[own];
+        } else {
+            const int a = prv[t];
+            const bool has_a = a != kNoneBefore, has_b = b != kNoFrame;
+            nn = n[t];
+            ff = f[t];
+            if (fill != DDSP_VOICING_FILL_NONE && (has_a || has_b)) {
+                float na = last_n, fa = last_f, nb = 0.0f, fb = 0.0f;
+                if (a >= 0) {
+                    const int u = sel[a];
+                    na = n[u];
+                    fa = f[u];
+                }
+                if (has_b) {
+                    const int u = sel[b];
+                    nb = n[u];
+                    fb = f[u];
+                }
+                if (fill == DDSP_VOICING_FILL_INTERPOLATE && has_a && has_b) {
+                    const float w = (float)(t - a) / (float)(b - a);
+                    const float step = (nb - na) * w;                        // three roundings: no contraction in this build
+                    nn = na + step;
+                    ff = (float)(10.0 * exp2((7180.0 * (double)nn + 1997.3794084376191) / 1200.0));
+                } else {
+                    nn = has_a ? na : nb;
+                    ff = has_a ? fa : fb;
+                }
+            }
+        }
+        n_out[row * T + t] = nn;
+        f0_out[row * T + t] = ff;
+    }
+}
+
 }  // namespace
 
 extern "C" int ddsp_pitch_centered(const float *probs, const int *center, float *f0, float *harmonicity, float *normalized_cents,
@@ -259,6 +472,38 @@ extern "C" int ddsp_pitch_viterbi(const float *probs, const float *log_trans, co
         if (!workspace) return DDSP_EINVAL;
         hipLaunchKernelGGL(pitch_viterbi_kernel<false>, dim3((unsigned)B), dim3(kThreads), (size_t)(kScoreBytes + kChunk * kBins), s, probs, log_trans,
                            state_in, state_out, bins, (signed char *)workspace, (int)T);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t ddsp_pitch_voicing_workspace_bytes(long B, long T)
+{
+    if (B <= 0 || T <= kVoiceLdsFrames) return 0;
+    return (size_t)B * (size_t)voicing_row_bytes(T);
+}
+
+extern "C" int ddsp_pitch_voicing(const float *f0, const float *normalized, const float *periodicity, const float *loudness,
+                                  const float *state_in, float *f0_out, float *normalized_out, uint8_t *voiced_out,
+                                  float *periodicity_out, float *state_out, void *workspace, long B, long T, int period_window,
+                                  int pitch_window, float upper, float lower, float silence, int fill, void *stream)
+{
+    if (B == 0) return 0;
+    if (!f0 || !normalized || !periodicity || !f0_out || !normalized_out || !voiced_out || B < 0 || T <= 0) return DDSP_EINVAL;
+    const auto window = [](int w) { return w >= 1 && w <= kVoiceSlots && (w & 1); };
+    if (!window(period_window) || !window(pitch_window) || upper < lower) return DDSP_EINVAL;
+    if (fill != DDSP_VOICING_FILL_NONE && fill != DDSP_VOICING_FILL_HOLD && fill != DDSP_VOICING_FILL_INTERPOLATE) return DDSP_EINVAL;
+    if (T >= (1l << 24) || B > 2147483647l / T) return DDSP_ERANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const int hp = (period_window - 1) / 2, hf = (pitch_window - 1) / 2;
+    if (T <= kVoiceLdsFrames) {
+        hipLaunchKernelGGL(pitch_voicing_kernel<true>, dim3((unsigned)B), dim3(64), (size_t)voicing_row_bytes(T), s,
+                           f0, normalized, periodicity, loudness, state_in, f0_out, normalized_out, voiced_out, periodicity_out,
+                           state_out, (unsigned char *)nullptr, (int)T, hp, hf, upper, lower, silence, fill);
+    } else {
+        if (!workspace) return DDSP_EINVAL;
+        hipLaunchKernelGGL(pitch_voicing_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, f0, normalized, periodicity, loudness,
+                           state_in, f0_out, normalized_out, voiced_out, periodicity_out, state_out, (unsigned char *)workspace,
+                           (int)T, hp, hf, upper, lower, silence, fill);
     }
     return (int)hipGetLastError();
 }

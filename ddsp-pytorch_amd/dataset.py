@@ -252,7 +252,10 @@ class PLHDataset(Dataset):
     {f0, harmonicity, loudness, probabilities, normalized_cents, audio}, cached in data_dir/plh_dataset.pth.
 
     `weights`: CREPE weights (a path or state dict), else conf.crepe_weights (as F0Encoder takes them).  `encode_batch`: examples
-    per encoder call (default conf.batch_size, the reference's DataLoader batch)."""
+    per encoder call (default conf.batch_size, the reference's DataLoader batch).
+
+    With conf.pitch_voicing set, `f0` and `normalized_cents` are the gated ones (Encoder's `voicing`); `voiced` is not
+    stored.  The cache file records neither that setting nor conf.pitch_decoder: pass `clear` after changing either."""
 
     def __init__(self, conf, clear=False, weights=None, device=None, encode_batch=None):
         self.device = _device(device)

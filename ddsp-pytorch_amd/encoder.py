@@ -5,6 +5,8 @@
   F0Encoder        resample to 16 kHz -> normalise -> frame by 1024 -> CREPE -> pitch (encoder.py:13-128): the argmax bin by
                    default, or the nine-bin weighted average around the argmax ('weighted') or around a Viterbi path ('viterbi')
   pitch_argmax, pitch_centered, pitch_weighted, pitch_viterbi   the decoders themselves, over probabilities [B, T, 360]
+  pitch_voicing    what follows a decoder: periodicity smoothing and hysteresis, loudness gate, median-filtered voiced pitch,
+                   unvoiced gaps held or interpolated (one launch; `Encoder(voicing=...)` applies it, off by default)
   LoudnessEncoder  A-weighted loudness of the un-windowed STFT (encoder.py:131-156)
   Encoder          both, as the dict {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177)
 
@@ -366,6 +368,177 @@ def pitch_viterbi(probabilities: torch.Tensor, state=None, return_state: bool = 
     return (bins, torch.from_numpy(last.astype(np.float32))) if want_state else bins
 
 
+# ------------------------------------------------------------------------------------------------------------------ voicing
+# Definition: DESIGN.md section 10b (include/ddsp_hip.h: ddsp_pitch_voicing).  CUDA tensors take one launch of
+# csrc/ddsp_pitch.hip; CPU tensors run the same definition in numpy.
+
+VOICING_WINDOWS = (1, 3, 5, 7, 9)
+VOICING_FILLS = ('none', 'hold', 'interpolate')                   # DDSP_VOICING_FILL_*
+VOICING_OPTIONS = ('period_window', 'pitch_window', 'upper', 'lower', 'silence', 'fill')
+
+
+def _lower_median_column(values: np.ndarray, valid: np.ndarray) -> np.ndarray:
+    """values, valid [..., K] with the columns in frame order -> the column of each row's lower median: element
+    (count - 1) div 2 of the valid entries sorted by value, then by column.  Rows without a valid entry give column 0."""
+    K = values.shape[-1]
+    column = np.broadcast_to(np.arange(K), values.shape)
+    order = np.lexsort((column, ~valid, np.where(valid, values, np.inf)), axis=-1)     # the last key is the primary one
+    rank = np.maximum(valid.sum(axis=-1) - 1, 0) // 2
+    return np.take_along_axis(order, rank[..., None], axis=-1)[..., 0]
+
+
+def _voicing_host(f0, n, p, loud, state, period_window, pitch_window, upper, lower, silence, fill):
+    """ddsp_pitch_voicing on fp32 numpy rows [B, T] (loud, state may be None; upper, lower, silence np.float32)
+    -> (f0, voiced bool, normalized, periodicity, state [B, 3])."""
+    B, T = p.shape
+    frames = np.arange(T)
+    offsets = np.arange(-4, 5)
+    window = frames[:, None] + offsets                                         # [T, 9] frame of every window slot
+    inside = (window >= 0) & (window < T)
+    at = np.clip(window, 0, T - 1)
+    # 1. periodicity
+    q = np.where(np.isnan(p), np.float32(0), p)
+    valid = np.broadcast_to(inside & (np.abs(offsets) <= (period_window - 1) // 2), (B, T, 9))
+    pick = _lower_median_column(q[:, at], valid)
+    ps = np.take_along_axis(q[:, at], pick[..., None], axis=-1)[..., 0]
+    # 2. hysteresis
+    v = np.zeros((B, T), dtype=bool)
+    now = np.zeros(B, dtype=bool) if state is None else state[:, 0] != 0
+    for t in range(T):
+        now = np.where(ps[:, t] >= upper, True, np.where(ps[:, t] < lower, False, now))
+        v[:, t] = now
+    # 3. gate
+    m = v & np.isfinite(n)
+    if loud is not None:
+        with np.errstate(invalid="ignore"):
+            m &= loud >= silence
+    # 4. voiced pitch: the chosen frame carries both values
+    valid = m[:, at] & inside & (np.abs(offsets) <= (pitch_window - 1) // 2) & m[:, :, None]
+    pick = _lower_median_column(n[:, at], valid)
+    chosen = np.where(m, np.take_along_axis(np.broadcast_to(at, (B, T, 9)), pick[..., None], axis=-1)[..., 0], frames)
+    sn = np.take_along_axis(n, chosen, axis=1)
+    sf = np.take_along_axis(f0, chosen, axis=1)
+    # 5. unvoiced frames.  Column 0 of the extended rows is the state's virtual frame at t = -1.
+    virtual = np.zeros(B, dtype=bool) if state is None else ~np.isnan(state[:, 1])
+    nan = np.full((B, 1), np.nan, dtype=np.float32)
+    en = np.concatenate([nan if state is None else state[:, 1:2], sn], axis=1)
+    ef = np.concatenate([nan if state is None else state[:, 2:3], sf], axis=1)
+    em = np.concatenate([virtual[:, None], m], axis=1)
+    slots = np.arange(T + 1)
+    a = np.maximum.accumulate(np.where(em, slots, -1), axis=1)[:, 1:]           # extended column of the voiced frame before, -1: none
+    b = np.minimum.accumulate(np.where(m, frames, T)[:, ::-1], axis=1)[:, ::-1]  # frame of the voiced one after, T: none
+    has_a, has_b = a >= 0, b < T
+    na, fa = np.take_along_axis(en, np.maximum(a, 0), axis=1), np.take_along_axis(ef, np.maximum(a, 0), axis=1)
+    nb, fb = np.take_along_axis(sn, np.minimum(b, T - 1), axis=1), np.take_along_axis(sf, np.minimum(b, T - 1), axis=1)
+    out_n, out_f = sn.copy(), sf.copy()
+    if fill != 'none':
+        held = ~m & (has_a | has_b)
+        out_n[held] = np.where(has_a, na, nb)[held]
+        out_f[held] = np.where(has_a, fa, fb)[held]
+    if fill == 'interpolate':
+        both = ~m & has_a & has_b
+        with np.errstate(all="ignore"):
+            w = (frames + 1 - a).astype(np.float32) / (b + 1 - a).astype(np.float32)   # a counts from the virtual frame
+            step = (nb - na) * w                                                       # fp32 arrays: every operation rounds
+            out_n[both] = (na + step)[both]
+        cents = 7180.0 * out_n[both].astype(np.float64) + CENTS_OF_BIN_0
+        out_f[both] = np.array([10.0 * 2.0 ** (c / 1200.0) for c in cents.tolist()], dtype=np.float64).astype(np.float32)
+    # 6. state
+    last = a[:, -1]
+    some = last >= 0
+    state_out = np.stack([v[:, -1].astype(np.float32),
+                          np.where(some, np.take_along_axis(en, np.maximum(last, 0)[:, None], axis=1)[:, 0], np.float32(np.nan)),
+                          np.where(some, np.take_along_axis(ef, np.maximum(last, 0)[:, None], axis=1)[:, 0], np.float32(np.nan))], axis=1)
+    return out_f, m, out_n, ps, state_out.astype(np.float32)
+
+
+def pitch_voicing(freq: torch.Tensor, harmonicity: torch.Tensor, normalized_cents: torch.Tensor, loudness=None, *,
+                  period_window: int = 3, pitch_window: int = 3, upper: float = 0.31, lower: float = 0.19, silence=None,
+                  fill: str = 'hold', state=None, return_state: bool = False):
+    """What a CREPE front end does after decoding, on a decoder's outputs [B, T, 1]: the periodicity (`harmonicity`) is
+    median-filtered over `period_window` frames and thresholded with hysteresis (voiced from `upper` up, unvoiced below
+    `lower`, unchanged in between), frames quieter than `silence` (in LoudnessEncoder's units; None, or no `loudness`: no
+    loudness gate) or without a finite pitch are unvoiced as well, a voiced frame takes the decoded (freq, normalized_cents)
+    pair of the lower median, by normalized cents, of the voiced frames within `pitch_window`, and an unvoiced frame keeps
+    its decoded pitch ('none'), takes the nearest voiced frame's before it, else after it ('hold'), or moves linearly in
+    normalized cents between the two ('interpolate', as 'hold' with one side only).  DESIGN.md section 10b has the
+    definition to the bit.
+
+    -> (freq, voiced bool, normalized_cents, periodicity), each [B, T, 1]; with a `state` [B, 3] (what a previous call on the
+    rows' earlier frames returned: the hysteresis flag and the last voiced pair) or return_state=True, the state is a
+    fifth element.  The default thresholds are the conventional hysteresis pair for CREPE periodicity; they are not tuned
+    here.  Windows are 1, 3, 5, 7 or 9 frames."""
+    what = "pitch_voicing"
+    shape = tuple(harmonicity.shape)
+    if len(shape) != 3 or shape[-1] != 1 or shape[1] < 1:
+        raise ValueError(f"{what}: harmonicity must be [B, T, 1] with T >= 1, got {shape}")
+    B, T = shape[:2]
+    for name, x in (("freq", freq), ("normalized_cents", normalized_cents), ("loudness", loudness)):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError(f"{what}: {name} must be [B, T, 1] = {shape} as harmonicity, got {tuple(x.shape)}")
+    if state is not None and tuple(state.shape) != (B, 3):
+        raise ValueError(f"{what}: state must be [B, 3] = {(B, 3)}, got {tuple(state.shape)}")
+    if period_window not in VOICING_WINDOWS or pitch_window not in VOICING_WINDOWS:
+        raise ValueError(f"{what}: windows must be among {VOICING_WINDOWS}, got {period_window!r} and {pitch_window!r}")
+    if fill not in VOICING_FILLS:
+        raise ValueError(f"{what}: fill {fill!r}: expected one of {VOICING_FILLS}")
+    upper, lower = np.float32(upper), np.float32(lower)
+    if not upper >= lower:
+        raise ValueError(f"{what}: upper ({upper}) must not be below lower ({lower})")
+    inputs = [freq, harmonicity, normalized_cents] + ([loudness] if loudness is not None else [])
+    for x in inputs:
+        _refuse_grad(x, what)
+        if x.device != harmonicity.device:
+            raise ValueError(f"{what}: the inputs are on different devices")
+    if loudness is None or silence is None:
+        loudness, silence = None, np.float32(0)
+    silence = np.float32(silence)
+    want_state = return_state or state is not None
+    if harmonicity.is_cuda:
+        dev = harmonicity.device
+        f, p, n = (x.detach().contiguous().float() for x in (freq, harmonicity, normalized_cents))
+        ld = loudness.detach().contiguous().float() if loudness is not None else None
+        if state is not None:
+            state = state.detach().to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        out = torch.empty((3, B, T, 1), device=dev, dtype=torch.float32)
+        voiced = torch.empty((B, T, 1), device=dev, dtype=torch.uint8)
+        state_out = torch.empty((B, 3), device=dev, dtype=torch.float32) if want_state else None
+        nbytes = L.ddsp_pitch_voicing_workspace_bytes(B, T)
+        work = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+        with torch.cuda.device(dev):
+            rc = L.ddsp_pitch_voicing(f.data_ptr(), n.data_ptr(), p.data_ptr(), ld.data_ptr() if ld is not None else None,
+                                      state.data_ptr() if state is not None else None, out[0].data_ptr(), out[1].data_ptr(),
+                                      voiced.data_ptr(), out[2].data_ptr(), state_out.data_ptr() if want_state else None,
+                                      work.data_ptr() if nbytes else None, B, T, period_window, pitch_window, float(upper),
+                                      float(lower), float(silence), VOICING_FILLS.index(fill),
+                                      torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_pitch_voicing")
+        result = (out[0], voiced.view(torch.bool), out[1], out[2])
+        return result + (state_out,) if want_state else result
+    rows = [x.detach().float().numpy().reshape(B, T) for x in (freq, normalized_cents, harmonicity)]
+    ld = loudness.detach().float().numpy().reshape(B, T) if loudness is not None else None
+    st = state.detach().float().cpu().numpy() if state is not None else None
+    f, m, n, ps, state_out = _voicing_host(rows[0], rows[1], rows[2], ld, st, period_window, pitch_window, upper, lower, silence, fill)
+    result = tuple(torch.from_numpy(np.ascontiguousarray(x)).unsqueeze(-1) for x in (f, m, n, ps))
+    return result + (torch.from_numpy(state_out),) if want_state else result
+
+
+def voicing_options(voicing) -> dict | None:
+    """Encoder's `voicing` argument as keyword arguments of pitch_voicing: None / False -> None (off), True -> the defaults,
+    a dict -> itself (its keys among VOICING_OPTIONS)."""
+    if voicing is None or voicing is False:
+        return None
+    if voicing is True:
+        return {}
+    if not isinstance(voicing, dict):
+        raise ValueError(f"voicing must be None, a bool or a dict of pitch_voicing's keyword arguments, got {type(voicing).__name__}")
+    unknown = sorted(set(voicing) - set(VOICING_OPTIONS))
+    if unknown:
+        raise ValueError(f"voicing: unknown keys {unknown}; expected some of {VOICING_OPTIONS}")
+    return dict(voicing)
+
+
 def _load_crepe_weights(weights):
     if isinstance(weights, (str, os.PathLike)):
         return torch.load(weights, map_location="cpu", weights_only=True)
@@ -540,15 +713,24 @@ class LoudnessEncoder(nn.Module):
 
 
 class Encoder(nn.Module):
-    """audio [B, L] -> {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177)."""
+    """audio [B, L] -> {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177).
 
-    def __init__(self, conf, weights=None):
+    `voicing` (else conf.pitch_voicing, else off): True, or a dict of pitch_voicing's keyword arguments (VOICING_OPTIONS),
+    runs pitch_voicing on the decoded pitch with this encoder's own loudness: `f0` and `normalized_cents` are replaced and
+    `voiced` (bool [B, T, 1]) is added; `harmonicity` and `probabilities` stay as decoded.  Off, the dict is the reference's."""
+
+    def __init__(self, conf, weights=None, voicing=None):
         super().__init__()
         self.conf = conf
         self.f0_encoder = F0Encoder(conf, weights)
         self.loudness_encoder = LoudnessEncoder(conf)
+        self.voicing = voicing_options(getattr(conf, 'pitch_voicing', None) if voicing is None else voicing)
 
     def forward(self, x: torch.Tensor) -> dict:
         f0, harmonicity, probabilities, normalized_cents = self.f0_encoder(x)
         loudness = self.loudness_encoder(x)
-        return dict(f0=f0, harmonicity=harmonicity, loudness=loudness, probabilities=probabilities, normalized_cents=normalized_cents)
+        out = dict(f0=f0, harmonicity=harmonicity, loudness=loudness, probabilities=probabilities, normalized_cents=normalized_cents)
+        if self.voicing is not None:
+            out['f0'], out['voiced'], out['normalized_cents'], _ = pitch_voicing(f0, harmonicity, normalized_cents, loudness,
+                                                                                 **self.voicing)
+        return out

@@ -404,6 +404,41 @@ int ddsp_pitch_viterbi(const float *probs, const float *log_trans, const float *
                        long B, long T, void *stream);
 
 /*
+ * Voicing: what follows a pitch decoder.  Per row of T frames, all fp32, dense [B, T]:
+ *   f0, normalized   a decoder's frequency and normalised-cents outputs (one pair per frame)
+ *   periodicity      its harmonicity
+ *   loudness         LoudnessEncoder's units, or NULL: no loudness gate
+ *   state_in         [B, 3] = {flag, last_n, last_f0} of the rows' previous blocks, or NULL
+ * "Lower median" of (value, frame) pairs: element (count - 1) div 2 in ascending order of value, then of frame.
+ *   1. ps[t] = lower median of periodicity[u] (a NaN read as 0) over |u - t| <= (period_window - 1) / 2 inside the row
+ *   2. v[t] = true if ps[t] >= upper, false if ps[t] < lower, else v[t - 1]; v[-1] = (flag != 0), false without a state
+ *   3. m[t] = v[t] and normalized[t] finite and (no loudness or loudness[t] >= silence; a NaN compares false)
+ *   4. for m[t]: u* = the frame of the lower median, by normalized, of the frames |u - t| <= (pitch_window - 1) / 2 with m[u];
+ *      the outputs are normalized[u*] and f0[u*], a decoded pair bit for bit
+ *   5. for other frames, with a / b the nearest frame with m before / after t (a state whose last_n is not NaN is a frame
+ *      at t = -1 with the values last_n, last_f0):
+ *        DDSP_VOICING_FILL_NONE         the decoded normalized[t], f0[t]
+ *        DDSP_VOICING_FILL_HOLD         the outputs of a, else those of b, else the decoded values
+ *        DDSP_VOICING_FILL_INTERPOLATE  with both: w = fl32(t - a) / fl32(b - a), n = n_a + fl32(fl32(n_b - n_a) * w),
+ *                                       f0 = fl32(10 * 2^((7180 n + 1997.3794084376191) / 1200)) evaluated in fp64; else as HOLD
+ * Outputs: f0_out, normalized_out [B, T]; voiced_out [B, T] bytes = m; periodicity_out [B, T] = ps (may be NULL);
+ * state_out [B, 3] (may be NULL) = {v[T - 1], the outputs of the last frame with m, the state's included, else NaN}.
+ * No output may alias an input or another output.  The windows are 1, 3, 5, 7 or 9; upper >= lower; anything else, an
+ * unknown fill or a missing required pointer is DDSP_EINVAL.  T >= 2^24 (frame distances are formed in fp32) or
+ * B T >= 2^31 is DDSP_ERANGE.  One launch, one wavefront per row, no atomics, no allocation, no host synchronisation.  A
+ * row's intermediates stay in LDS while T <= 4096; longer rows need `workspace` of ddsp_pitch_voicing_workspace_bytes(B, T)
+ * bytes (0 while they fit; 4-byte aligned).  Rows are independent.
+ */
+#define DDSP_VOICING_FILL_NONE 0
+#define DDSP_VOICING_FILL_HOLD 1
+#define DDSP_VOICING_FILL_INTERPOLATE 2
+size_t ddsp_pitch_voicing_workspace_bytes(long B, long T);
+int ddsp_pitch_voicing(const float *f0, const float *normalized, const float *periodicity, const float *loudness,
+                       const float *state_in, float *f0_out, float *normalized_out, uint8_t *voiced_out, float *periodicity_out,
+                       float *state_out, void *workspace, long B, long T, int period_window, int pitch_window, float upper,
+                       float lower, float silence, int fill, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
