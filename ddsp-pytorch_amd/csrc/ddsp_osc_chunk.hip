@@ -23,7 +23,8 @@
 //
 //   * Only some of a lane's K slots -- KR ROOT slots -- walk the increment / fp64 accumulate chain.  The other KD = K - KR are
 //     DERIVED: the unwrapped fp32 phase of harmonic 2^t * r is bit for bit 2^t times that of harmonic r, so a
-//     derived slot multiplies the rounded phase of a root slot of its lane by 2^t.  Which harmonic sits in which slot is the
+//     derived slot takes the rounded phase of a root slot of its lane times 2^t, with t a compile-time property of the slot: the
+//     fast walk folds 2^t into the modulo's constants and never forms the product.  Which harmonic sits in which slot is the
 //     slot plan (ddsp_osc_plan.h), computed on the host and handed over in the kernel arguments; KR = K is the all-roots mapping.
 //
 // Launches: osc_chunk_totals_kernel (rows w / amp, chunk totals of the root slots, highest audible harmonic per row and chunk),
@@ -117,16 +118,22 @@ __device__ __forceinline__ const PlanTable *plan_table()
     return reinterpret_cast<const PlanTable *>((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(ChunkArgs, t));
 }
 
-// derived_parent(K, .) as a table, so that an unrolled loop's index folds to a register name
+// derived_parent(K, .) and 2^derived_shift(K, .) as tables, so that an unrolled loop's index folds to a register name and to
+// a constant
 template <int K>
 struct ParentTable {
     int v[kPlanMaxK];
-    constexpr ParentTable() : v()
+    float f[kPlanMaxK];
+    constexpr ParentTable() : v(), f()
     {
-        for (int d = 0; d < kPlanMaxK; ++d) v[d] = derived_parent(K, d);
+        for (int d = 0; d < kPlanMaxK; ++d) {
+            v[d] = derived_parent(K, d);
+            f[d] = (float)(1 << derived_shift(K, d));
+        }
     }
 };
 #define DDSP_PARENT(K, d) (par.v[d])   // with `constexpr ParentTable<K> par` in scope
+#define DDSP_FACTOR(K, d) (par.f[d])   // 2^t of derived slot d, a compile-time constant (ddsp_osc_plan.h: derived_shift)
 
 // slots [0, KR) are roots, [KR, K) derived (derived slot d = slot KR + d reads root slot DDSP_PARENT(K, d))
 template <int K, int KR>
@@ -172,20 +179,26 @@ __device__ __forceinline__ void segment_rows(int s, int T, int &r0, int &r1)
 
 // ---- production walk: samples [n_beg, n_end) of the current segment, the lane's first KLR root slots and KLD derived ones ----
 // (the derived slots those roots feed: class_derived).  Stages 1-5 -- increment, fp64 accumulate, rounding -- run over the roots,
-// one multiply by 2^t forms each derived phase, every later stage runs over all KL = KLR + KLD slots.
+// every later stage over all KL = KLR + KLD slots.  A derived slot's phase, 2^t times its root's, is never formed: t is a
+// compile-time property of the slot (derived_shift), so the modulo runs on the ROOT's phase with constants that carry the
+// factor -- quotient fma(P, 2^t/2pi32, magic) - magic (the same real product, rounded once: the same bits), remainder
+// fma(-q, 2pi32/2^t, P) (the old remainder times 2^-t: a power of two commutes with the rounding), revolutions r * (2^t/2pi)
+// (the old product) -- DESIGN.md §4a.
 // NS samples per iteration (a stage then covers NS*KL independent instructions); QKEEP: the modulo's quotient is
 // computed on even samples and reused on the odd ones (increments < kReuseMaxInc, checked by the caller).
 // Every lane parks its partial sum in LDS; after each 32nd sample the G lanes of a row group each sum the partials of
 // 32/G samples, apply the loudness and store: one whole 128-byte line per row.
 template <int K, int KR, int KLR, int NS, int QMODE>
-__device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR> &st, const float (&fac)[K - KR + 1], float *ystage,
-                                           float *yrow, int j, bool active, int i_abs, int n_beg, int n_end, bool clamp0, float L0,
-                                           float L1, int slot)
+__device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR> &st, float *ystage, float *yrow, int j, bool active,
+                                           int i_abs, int n_beg, int n_end, bool clamp0, float L0, float L1, int slot)
 {
     constexpr int KLD = KR < K ? class_derived(K, KLR) : 0;   // the derived slots the walked roots feed
     constexpr int KL = KLR + KLD;                             // v[.][m]: m < KLR root slot m, else derived slot m - KLR
 #define DDSP_SLOT(m) ((m) < KLR ? (m) : KR + ((m) - KLR))
     constexpr ParentTable<K> par;
+    // slot m of the walk takes its phase from root slot DDSP_SRC(m) (itself, or a derived slot's parent) times DDSP_FAC(m)
+#define DDSP_SRC(m) ((m) < KLR ? (m) : DDSP_PARENT(K, (m) - KLR))
+#define DDSP_FAC(m) ((m) < KLR ? 1.0f : DDSP_FACTOR(K, (m) - KLR))
     const int G = 1 << p.logG, per = 32 >> p.logG;
     float lam, dlam;
     segment_lambda(p, n_beg, clamp0, lam, dlam);
@@ -209,7 +222,7 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
             w1[e] = w1[e - 1] + dlam;
             w0[e] = w0[e - 1] - dlam;
         }
-        float v[NS][KL];
+        float v[NS][KLR], r[NS][KL];
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
@@ -240,14 +253,8 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
 #pragma unroll
             for (int m = 0; m < KLR; ++m) v[e][m] = (float)d[e][m];                       // ... rounded to fp32 per sample
         DDSP_STAGE_END();
-        if (KLD > 0) {   // derived slots: the root's rounded phase times 2^t, exact
-#pragma unroll
-            for (int e = 0; e < NS; ++e)
-#pragma unroll
-                for (int m = KLR; m < KL; ++m) v[e][m] = fac[m - KLR] * v[e][DDSP_PARENT(K, m - KLR)];
-            DDSP_STAGE_END();
-        }
-        // P - q*2pi32 is exact in fp32 for q = rint(P/2pi32) < 2^21; nearest multiple instead of floor
+        // P - q*2pi32 is exact in fp32 for q = rint(P/2pi32) < 2^21; nearest multiple instead of floor.  The
+        // constants of a derived slot carry its 2^t (powers of two: each product below is exact at compile time)
         float q[NS][KL];
         const bool fresh = QMODE != 1 || (n & 1) == 0;   // wave-uniform
         if (fresh) {
@@ -255,7 +262,7 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
 #pragma unroll
             for (int e = 0; e < NQ; ++e)
 #pragma unroll
-                for (int m = 0; m < KL; ++m) q[e][m] = __fmaf_rn(v[e][m], kInvTwoPi32, kRoundMagic);
+                for (int m = 0; m < KL; ++m) q[e][m] = __fmaf_rn(v[e][DDSP_SRC(m)], DDSP_FAC(m) * kInvTwoPi32, kRoundMagic);
             DDSP_STAGE_END();
 #pragma unroll
             for (int e = 0; e < NQ; ++e)
@@ -277,17 +284,17 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = __fmaf_rn(-q[e][m], kTwoPi32, v[e][m]);  // :42
+            for (int m = 0; m < KL; ++m) r[e][m] = __fmaf_rn(-q[e][m], kTwoPi32 / DDSP_FAC(m), v[e][DDSP_SRC(m)]);  // :42 (times 2^-t)
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = v[e][m] * kRevPerRad;
+            for (int m = 0; m < KL; ++m) r[e][m] = r[e][m] * (DDSP_FAC(m) * kRevPerRad);
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
 #pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = __builtin_amdgcn_sinf(v[e][m]);         // v_sin_f32 (revolutions)
+            for (int m = 0; m < KL; ++m) r[e][m] = __builtin_amdgcn_sinf(r[e][m]);         // v_sin_f32 (revolutions)
         DDSP_STAGE_END();
 #pragma unroll
         for (int e = 0; e < NS; ++e)
@@ -301,7 +308,7 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
             s1[e] = 0.0f;
 #pragma unroll
             for (int m = 0; m < KL; ++m) {
-                if (m & 1) s1[e] = __fmaf_rn(q[e][m], v[e][m], s1[e]); else s0[e] = __fmaf_rn(q[e][m], v[e][m], s0[e]);  // :48-49
+                if (m & 1) s1[e] = __fmaf_rn(q[e][m], r[e][m], s1[e]); else s0[e] = __fmaf_rn(q[e][m], r[e][m], s0[e]);  // :48-49
             }
         }
         DDSP_STAGE_END();
@@ -355,12 +362,14 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
         }
     }
 #undef DDSP_SLOT
+#undef DDSP_SRC
+#undef DDSP_FAC
 }
 
 // Reference-exact walk of the same samples: libm fmodf modulo, per-sample cross-lane sum, direct stores.
 template <int K, int KR>
-__device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<K, KR> &st, const float (&fac)[K - KR + 1], float *yrow,
-                                                 int j, bool active, int i_abs, int n_beg, int n_end, bool clamp0, float L0, float L1)
+__device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<K, KR> &st, float *yrow, int j, bool active, int i_abs,
+                                                 int n_beg, int n_end, bool clamp0, float L0, float L1)
 {
     constexpr ParentTable<K> par;
     float lam, dlam;
@@ -377,7 +386,7 @@ __device__ __forceinline__ void walk_synth_exact(const OscParams &p, ChunkState<
             ph[m] = (float)st.acc[m];
         }
 #pragma unroll
-        for (int m = KR; m < K; ++m) ph[m] = fac[m - KR] * ph[DDSP_PARENT(K, m - KR)];
+        for (int m = KR; m < K; ++m) ph[m] = DDSP_FACTOR(K, m - KR) * ph[DDSP_PARENT(K, m - KR)];
 #pragma unroll
         for (int m = 0; m < K; ++m) {
             const float r = remainder_two_pi(ph[m]);   // :42, exact
@@ -661,11 +670,14 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
     constexpr int KE = class_prefix(KR, 3), KQ = class_prefix(KR, 2), KH = class_prefix(KR, 1), KT = class_prefix(KR, 0);
     const int ntasks = p.RB * p.NC;
     const PlanTable *tab = plan_table();
-    const int jj = (threadIdx.x & 63) & ((1 << p.logG) - 1);
-    float fac[KD + 1];                  // derived slot d: 2^t
+    // bit d: derived slot d of this lane holds a harmonic.  A padded one walks with its slot's 2^t like any other (amplitude 0, a
+    // finite sine) but must not decide the walk: its scaled increment and phase stay out of `big` and `bad` below
+    unsigned filled = 0;
+    {
+        const int jj = (threadIdx.x & 63) & ((1 << p.logG) - 1);
 #pragma unroll
-    for (int d = 0; d < KD; ++d) fac[d] = (float)(1u << tab->shift[jj * K + KR + d]);
-    fac[KD] = 1.0f;
+        for (int d = 0; d < KD; ++d) filled |= (tab->h[jj * K + KR + d] < p.H ? 1u : 0u) << d;
+    }
     int wt = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (EXACT && *p.redo_flag == 0) return;
     for (; wt < ntasks; wt += gridDim.x * 4) {
@@ -762,22 +774,23 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
                 big = big || !(st.x0[m] < kReuseMaxInc) || !(st.x1[m] < kReuseMaxInc);
             }
 #pragma unroll
-            for (int d = 0; d < KD; ++d)   // (a positive factor leaves the sign / NaN check as it is)
-                big = big || !(fac[d] * st.x0[DDSP_PARENT(K, d)] < kReuseMaxInc) || !(fac[d] * st.x1[DDSP_PARENT(K, d)] < kReuseMaxInc);
+            for (int d = 0; d < KD; ++d)   // (a positive factor leaves the sign / NaN check as it is; x * 2^t < c <=> x < c / 2^t)
+                big = big || ((filled >> d & 1u) && (!(st.x0[DDSP_PARENT(K, d)] < kReuseMaxInc / DDSP_FACTOR(K, d)) ||
+                                                     !(st.x1[DDSP_PARENT(K, d)] < kReuseMaxInc / DDSP_FACTOR(K, d))));
             if (exact) {
-                walk_synth_exact<K, KR>(p, st, fac, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1);
+                walk_synth_exact<K, KR>(p, st, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1);
             } else if (mlive <= p.cls_max[3] && KE < KQ) {
-                walk_synth<K, KR, KE, 4, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KE, 4, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else if (mlive <= p.cls_max[2] && KQ < KH) {
-                walk_synth<K, KR, KQ, 4, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KQ, 4, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else if (mlive <= p.cls_max[1] && KH < KT) {
-                walk_synth<K, KR, KH, 2, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KH, 2, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else if (mlive <= p.cls_max[0] && KT < KR) {
-                walk_synth<K, KR, KT, 1, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KT, 1, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else if (!__any(big)) {
-                walk_synth<K, KR, KR, 1, 1>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KR, 1, 1>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             } else {
-                walk_synth<K, KR, KR, 1, 0>(p, st, fac, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
+                walk_synth<K, KR, KR, 1, 0>(p, st, ystage, yrow, k.j, k.active, k.i, k.n, n_end, clamp0, L0, L1, slot);
             }
             k.i += n_end - k.n;
             if (k.i >= k.i_end) break;
@@ -794,7 +807,8 @@ __global__ void __launch_bounds__(256, (!EXACT && K <= 13) ? 3 : 1) osc_chunk_sy
             for (int m = 0; m < KR; ++m) bad = bad || !(st.acc[m] < (double)kFastPhaseLimit);
             // (the fast modulo's range holds for a derived slot when it holds for 2^t times its root's phase)
 #pragma unroll
-            for (int d = 0; d < KD; ++d) bad = bad || !((double)fac[d] * st.acc[DDSP_PARENT(K, d)] < (double)kFastPhaseLimit);
+            for (int d = 0; d < KD; ++d)
+                bad = bad || ((filled >> d & 1u) && !(st.acc[DDSP_PARENT(K, d)] < (double)kFastPhaseLimit / (double)DDSP_FACTOR(K, d)));
             const bool redo = __any(bad);
             if (DDSP_CHUNK_INLINE_REPAIR && redo) { exact = true; continue; }
             if ((threadIdx.x & 63) == 0) {

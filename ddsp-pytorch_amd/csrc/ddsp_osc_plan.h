@@ -3,9 +3,9 @@
 //
 // The unwrapped fp32 phase of harmonic 2^t * r is bit for bit 2^t times the phase of harmonic r (every rounding on the way
 // commutes with a power of two: DESIGN.md §4a), so only some slots -- ROOTS -- walk the increment / fp64 accumulate chain;
-// a DERIVED slot multiplies the rounded phase of a root slot of the same lane by 2^t.  Registers cannot be indexed per
-// lane, so WHICH root a derived slot reads is fixed at compile time per K (slot_children below: root slot i feeds
-// slot_children(K, i) derived slots); the planner's job is to cut the odd families o, 2o, 4o, ... into pieces
+// a DERIVED slot takes the rounded phase of a root slot of the same lane times 2^t.  Registers cannot be indexed per
+// lane, so WHICH root a derived slot reads, and with which t, is fixed at compile time per K (slot_children below: root slot i
+// feeds slot_children(K, i) derived slots, the r-th of them with t = r + 1: derived_shift); the planner's job is to cut the odd families o, 2o, 4o, ... into pieces
 // {r, r * 2^t1, r * 2^t2, ...} that fill G lanes of that one shape.  Where it cannot, the launch keeps the all-roots
 // mapping (harmonic = lane + slot * G).
 #pragma once
@@ -72,6 +72,11 @@ constexpr int derived_rank(int K, int d)
         }
     return 0;
 }
+// A FILLED derived slot d holds 2^t times its root's harmonic number with t = derived_shift(K, d): plan_slots cuts every odd
+// family into contiguous runs {r, 2r, 4r, ...} and gives child number c of a run to the root slot's child of rank c, so t is a
+// property of the slot, the same in every lane (tests/test_osc_plan_shift_host.py holds this for every K, G and H = 1..400).  The
+// kernels take the factor from here, at compile time; PlanTable::shift records the same t per lane (0 in a padded slot).
+constexpr int derived_shift(int K, int d) { return derived_rank(K, d) + 1; }
 // Silent-harmonic classes: class q = 0..3 walks the first class_prefix(KR, q) root slots (3/4, 1/2, 1/4, 1/8 of them) and the
 // derived slots they feed, class_derived(K, that many); a wavefront whose highest audible harmonic number is <= cls_max[q]
 // may take it.
