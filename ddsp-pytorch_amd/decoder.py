@@ -32,9 +32,6 @@ def _dense_stack(n_in: int, width: int, depth: int) -> nn.Module:
     return stack
 
 
-_LN_IO = {torch.bfloat16: 1, torch.float16: 2}
-
-
 def _ln_forward(x, g, b, eps, slope):
     """x [.., D] contiguous (fp32 / bf16 / fp16), g / b fp32 -> (y like x, mean, rstd): include/ddsp_hip.h ddsp_ln_lrelu_forward*."""
     D = x.shape[-1]
@@ -50,7 +47,7 @@ def _ln_forward(x, g, b, eps, slope):
                                          rows, D, float(eps), float(slope), stream)
         else:
             rc = L.ddsp_ln_lrelu_forward_16(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            rows, D, float(eps), float(slope), _LN_IO[x.dtype], stream)
+                                            rows, D, float(eps), float(slope), dense._IO[x.dtype], stream)
     _lib.check(rc, "ddsp_ln_lrelu_forward")
     return y, mean, rstd
 
@@ -72,7 +69,7 @@ def _ln_backward(gy, x, y, g, mean, rstd, slope, want_xsum):
         if x.dtype == torch.float32:
             rc = L.ddsp_ln_lrelu_backward(*args, stream)
         else:
-            rc = L.ddsp_ln_lrelu_backward_16(*args, _LN_IO[x.dtype], stream)
+            rc = L.ddsp_ln_lrelu_backward_16(*args, dense._IO[x.dtype], stream)
     _lib.check(rc, "ddsp_ln_lrelu_backward")
     return gx, out[0], out[1], xsum
 
@@ -143,12 +140,10 @@ class _FirstBlock(torch.autograd.Function):
     instead of being written and read back, and the backward sums the Linear's weight / bias gradients beside the LayerNorm's
     -- the input carries no gradient (the caller checks).  Output in the autocast dtype when autocast is on, fp32 otherwise."""
 
-    _IO = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, eps, slope):
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-        if dt not in _FirstBlock._IO:
+        if dt not in dense._IO:
             dt = torch.float32
         D = weight.shape[0]
         xs = x.detach().reshape(-1).contiguous().float()
@@ -161,7 +156,7 @@ class _FirstBlock(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().ddsp_outer_ln_lrelu_forward(xs.data_ptr(), w.data_ptr(), c.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(),
                                                               mean.data_ptr(), rstd.data_ptr(), rows, D, float(eps), float(slope),
-                                                              _FirstBlock._IO[dt], torch.cuda.current_stream().cuda_stream),
+                                                              dense._IO[dt], torch.cuda.current_stream().cuda_stream),
                        "ddsp_outer_ln_lrelu_forward")
         ctx.save_for_backward(xs, w, c, y, g, mean, rstd)
         ctx.slope = float(slope)
@@ -181,7 +176,7 @@ class _FirstBlock(torch.autograd.Function):
             _lib.check(L.ddsp_outer_ln_lrelu_backward(gy.data_ptr(), xs.data_ptr(), w.data_ptr(), c.data_ptr(), y.data_ptr(), g.data_ptr(),
                                                       mean.data_ptr(), rstd.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
                                                       out[2].data_ptr(), out[3].data_ptr(), scratch.data_ptr(), rows, D, ctx.slope,
-                                                      _FirstBlock._IO[y.dtype], torch.cuda.current_stream().cuda_stream),
+                                                      dense._IO[y.dtype], torch.cuda.current_stream().cuda_stream),
                        "ddsp_outer_ln_lrelu_backward")
         wshape, wdt, cdt, gdt, bdt = ctx.param_meta
         return None, out[0].view(wshape).to(wdt), out[1].to(cdt), out[2].to(gdt), out[3].to(bdt), None, None
@@ -265,12 +260,10 @@ class _Heads(torch.autograd.Function):
     instead of three GEMMs (one of them 1 wide) and three sigmoid passes forward, and nine GEMMs / reductions backward.  The
     parameters stay three separate tensors (checkpoint compatibility): their gradients are row slices of one weight gradient."""
 
-    _IO = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
     @staticmethod
     def forward(ctx, z, w0, b0, w1, b1, w2, b2):
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else z.dtype
-        if dt not in _Heads._IO:
+        if dt not in dense._IO:
             dt = torch.float32
         zc = z.to(dt).contiguous()
         W = torch.cat([dense._cast(w, dt) for w in (w0, w1, w2)], 0)
@@ -282,7 +275,7 @@ class _Heads(torch.autograd.Function):
         outs = [torch.empty(z.shape[:-1] + (n,), device=z.device, dtype=torch.float32) for n in ns]
         with torch.cuda.device(z.device):
             _lib.check(_lib.lib().ddsp_heads_sigmoid_forward(h.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), rows,
-                                                             ns[0], ns[1], ns[2], _Heads._IO[dt], torch.cuda.current_stream().cuda_stream),
+                                                             ns[0], ns[1], ns[2], dense._IO[dt], torch.cuda.current_stream().cuda_stream),
                        "ddsp_heads_sigmoid_forward")
         ctx.save_for_backward(zc, W, h)
         ctx.ns, ctx.in_dtype, ctx.param_dtypes = ns, z.dtype, (w0.dtype, b0.dtype)
@@ -297,7 +290,7 @@ class _Heads(torch.autograd.Function):
         gh = torch.empty_like(h)
         with torch.cuda.device(h.device):
             _lib.check(_lib.lib().ddsp_heads_sigmoid_backward(h.data_ptr(), gs[0].data_ptr(), gs[1].data_ptr(), gs[2].data_ptr(), gh.data_ptr(), rows,
-                                                              ns[0], ns[1], ns[2], _Heads._IO[h.dtype], torch.cuda.current_stream().cuda_stream),
+                                                              ns[0], ns[1], ns[2], dense._IO[h.dtype], torch.cuda.current_stream().cuda_stream),
                        "ddsp_heads_sigmoid_backward")
         wdt, bdt = ctx.param_dtypes
         gz = gw = gb = None
@@ -339,7 +332,7 @@ class Controller(nn.Module):
             # cat widening both stacks to fp32 and the next Linear narrowing all three again (the Linear computes in 16 bit anyway)
             z = z.to(z_pitch.dtype)
         z = _run_stack(self.mlp_gru, torch.cat((z, z_pitch, z_loud), dim=-1))
-        if FUSED_HEADS and z.is_cuda and z.dtype in _Heads._IO:
+        if FUSED_HEADS and z.is_cuda and z.dtype in dense._IO:
             c, a, H = _Heads.apply(z, self.dense_harmonic.weight, self.dense_harmonic.bias, self.dense_loudness.weight,
                                    self.dense_loudness.bias, self.dense_filter.weight, self.dense_filter.bias)
         else:

@@ -339,7 +339,7 @@ def test_fused_scaled_sigmoid_matches_torch_formulation():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("D", [256, 512, 1024])
+@pytest.mark.parametrize("D", [256, 512, 768, 1024])
 def test_fused_layernorm_leakyrelu_matches_torch_layers(D):
     from ddsp_pytorch_amd.decoder import _dense_stack, _run_stack
     torch.manual_seed(D)
@@ -412,6 +412,112 @@ def test_first_block_of_the_f0_and_loudness_stacks_matches_torch_layers(D, amp):
     for k in gp_ref:
         scale = float(gp_ref[k].abs().max()) + 1e-9
         assert float((gp[k] - gp_ref[k]).abs().max()) <= 2.0 * float((gp_sep[k] - gp_ref[k]).abs().max()) + unit * scale, k
+
+
+# Row counts at which the LayerNorm kernels take another path (four rows per workgroup, one wavefront each): 1 and 3 leave wavefronts
+# without a row, whose zero slabs are still summed; 277 rows are 70 workgroups, so the finish runs its four-way unrolled loop (64
+# slabs) and its tail; 4101 rows are 1024 workgroups (the backward's cap) plus rows 4096-4100 as second turns of its row loop.
+_LN_ROWS = (1, 3, 277, 4101)
+_LN_EPS, _LN_SLOPE = 1e-5, 0.01
+
+
+def _ln_lrelu_fp64(pre, leaves, gy):
+    """The torch formulation in fp64 on a pre-activation `pre` [rows, D] built from `leaves` = (..., gamma, beta), all fp64:
+    -> y, mean, rstd, [gradient of each leaf]."""
+    import torch.nn.functional as F
+    y = F.leaky_relu(F.layer_norm(pre, pre.shape[-1:], leaves[-2], leaves[-1], _LN_EPS), _LN_SLOPE)
+    grads = torch.autograd.grad(y, leaves, gy.double())
+    return y.detach(), pre.detach().mean(-1), (pre.detach().var(-1, unbiased=False) + _LN_EPS).rsqrt(), list(grads)
+
+
+def _check_ln_outputs(got, ref, dtype, where):
+    """got / ref: (y, mean, rstd, gx or None, [parameter gradients]).  fp32: y to 1e-5 absolute (inputs are O(1)); 16-bit: y within one
+    rounding to the type, gx within two (its input gy was rounded as well); every fp32 gradient to 1e-4 of the reference's largest
+    value.  mean / rstd are fp32 sums of D O(1) values in every case: 1e-5 absolute / relative covers their ~log2(D) roundings."""
+    y, mean, rstd, gx, grads = got
+    y_ref, mean_ref, rstd_ref, gx_ref, grads_ref = ref
+    ulp = {torch.float32: None, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype]
+    assert y.dtype == dtype and mean.dtype == rstd.dtype == torch.float32
+    err = float((y.double() - y_ref).abs().max())
+    assert err <= (1e-5 if ulp is None else ulp * float(y_ref.abs().max())), (where, "y", err)
+    assert float((mean.double() - mean_ref).abs().max()) <= 1e-5, (where, "mean")
+    assert float((rstd.double() / rstd_ref - 1.0).abs().max()) <= 1e-5, (where, "rstd")
+    if gx_ref is not None:
+        assert gx.dtype == dtype
+        err = float((gx.double() - gx_ref).abs().max())
+        assert err <= (1e-4 if ulp is None else 2 * ulp) * float(gx_ref.abs().max()), (where, "gx", err)
+    for k, (g, g_ref) in enumerate(zip(grads, grads_ref)):
+        assert g.dtype == torch.float32
+        err = float((g.double() - g_ref).abs().max())
+        assert err <= 1e-4 * float(g_ref.abs().max()), (where, "parameter gradient", k, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("D", [256, 768, 1024])
+def test_fused_layernorm_passes_match_fp64_at_every_row_count(D, dtype):
+    """decoder._ln_forward / _ln_backward (with the column sums of gx) called directly, against the torch formulation in fp64 on the
+    same (already rounded) inputs, at the row counts of _LN_ROWS; each call twice, bitwise equal."""
+    from ddsp_pytorch_amd.decoder import _ln_backward, _ln_forward
+    torch.manual_seed(100 + D)
+    gamma = torch.empty(D, device="cuda").uniform_(0.5, 1.5)
+    beta = torch.empty(D, device="cuda").uniform_(-0.3, 0.3)
+    x_all = torch.randn(_LN_ROWS[-1], D, device="cuda").to(dtype)
+    gy_all = torch.randn(_LN_ROWS[-1], D, device="cuda").to(dtype)
+    for rows in _LN_ROWS:
+        x, gy = x_all[:rows].contiguous(), gy_all[:rows].contiguous()
+
+        def run():
+            y, mean, rstd = _ln_forward(x, gamma, beta, _LN_EPS, _LN_SLOPE)
+            gx, dg, db, xsum = _ln_backward(gy, x, y, gamma, mean, rstd, _LN_SLOPE, True)
+            return y, mean, rstd, gx, [dg, db, xsum]
+
+        got, again = run(), run()
+        for a, b in zip(got[:4] + tuple(got[4]), again[:4] + tuple(again[4])):
+            assert torch.equal(a, b), (rows, "two calls differ")
+        leaves = [t.double().requires_grad_() for t in (x, gamma, beta)]
+        y_ref, mean_ref, rstd_ref, (gx_ref, dg_ref, db_ref) = _ln_lrelu_fp64(leaves[0], leaves, gy)
+        _check_ln_outputs(got, (y_ref, mean_ref, rstd_ref, gx_ref, [dg_ref, db_ref, gx_ref.sum(0)]), dtype, rows)
+    if D == 256 and dtype == torch.float32:
+        # forward only: 16389 rows are 4096 workgroups (the forward's cap) plus rows 16384-16388 as second turns of its row loop
+        x = torch.randn(16389, D, device="cuda")
+        got, again = _ln_forward(x, gamma, beta, _LN_EPS, _LN_SLOPE), _ln_forward(x, gamma, beta, _LN_EPS, _LN_SLOPE)
+        assert all(torch.equal(a, b) for a, b in zip(got, again))
+        leaves = [t.double().requires_grad_() for t in (x, gamma, beta)]
+        y_ref, mean_ref, rstd_ref, _ = _ln_lrelu_fp64(leaves[0], leaves, torch.zeros_like(x))
+        _check_ln_outputs(got + (None, []), (y_ref, mean_ref, rstd_ref, None, []), dtype, 16389)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("D", [256, 512])
+def test_first_block_passes_match_fp64_at_every_row_count(D, dtype):
+    """decoder._FirstBlock (output in `dtype`: the autocast type, or fp32 without autocast) against the torch formulation in fp64 of
+    Linear(1 -> D) -> LayerNorm -> LeakyReLU on the same inputs, at the row counts of _LN_ROWS; each call twice, bitwise equal."""
+    from ddsp_pytorch_amd.decoder import _FirstBlock
+    torch.manual_seed(200 + D)
+    params = [torch.empty(D, 1, device="cuda").uniform_(-1.0, 1.0), torch.empty(D, device="cuda").uniform_(-1.0, 1.0),     # Linear(1, D)'s range
+              torch.empty(D, device="cuda").uniform_(0.5, 1.5), torch.empty(D, device="cuda").uniform_(-0.3, 0.3)]
+    xs_all = torch.rand(_LN_ROWS[-1], 1, device="cuda") * 2 - 1
+    gy_all = torch.randn(_LN_ROWS[-1], D, device="cuda").to(dtype)
+    for rows in _LN_ROWS:
+        xs, gy = xs_all[:rows].contiguous(), gy_all[:rows].contiguous()
+
+        def run():
+            leaves = [p.clone().requires_grad_() for p in params]
+            with torch.autocast("cuda", dtype=dtype, enabled=dtype != torch.float32):
+                y = _FirstBlock.apply(xs, *leaves, _LN_EPS, _LN_SLOPE)
+            mean, rstd = y.grad_fn.saved_tensors[-2:]
+            y.backward(gy)
+            return y.detach(), mean, rstd, None, [p.grad for p in leaves]
+
+        got, again = run(), run()
+        for a, b in zip(got[:3] + tuple(got[4]), again[:3] + tuple(again[4])):
+            assert torch.equal(a, b), (rows, "two calls differ")
+        leaves = [p.double().requires_grad_() for p in params]
+        pre = xs.double() * leaves[0].view(1, D) + leaves[1]
+        y_ref, mean_ref, rstd_ref, grads_ref = _ln_lrelu_fp64(pre, leaves, gy)
+        _check_ln_outputs(got, (y_ref, mean_ref, rstd_ref, None, grads_ref), dtype, rows)
 
 
 @pytest.mark.gpu

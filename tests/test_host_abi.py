@@ -118,6 +118,46 @@ def test_argument_validation_without_gpu_abi5():
     assert L.ddsp_reverb_impulse(None, None, None, None, None, 16, 16, None) == -1
 
 
+def test_layernorm_entry_points_validate_in_a_fixed_order():
+    """The six LayerNorm + LeakyReLU entries answer, in this order: an invalid io_type; then (forward) empty rows, null pointers,
+    a width the kernels are not built for -- (backward) the width, the gradient outputs an empty shard still zeroes, null pointers."""
+    L = ddsp._lib.lib()
+    EINVAL, ERANGE = -1, -2
+    N = None
+    ln_fwd = lambda rows, D: L.ddsp_ln_lrelu_forward(N, N, N, N, N, N, rows, D, 1e-5, 0.01, N)                       # noqa: E731
+    ln_bwd = lambda rows, D: L.ddsp_ln_lrelu_backward(N, N, N, N, N, N, N, N, N, N, N, rows, D, 0.01, N)              # noqa: E731
+    ln_fwd16 = lambda rows, D, io: L.ddsp_ln_lrelu_forward_16(N, N, N, N, N, N, rows, D, 1e-5, 0.01, io, N)          # noqa: E731
+    ln_bwd16 = lambda rows, D, io: L.ddsp_ln_lrelu_backward_16(N, N, N, N, N, N, N, N, N, N, N, rows, D, 0.01, io, N)  # noqa: E731
+    out_fwd = lambda rows, D, io: L.ddsp_outer_ln_lrelu_forward(N, N, N, N, N, N, N, N, rows, D, 1e-5, 0.01, io, N)  # noqa: E731
+    out_bwd = lambda rows, D, io: L.ddsp_outer_ln_lrelu_backward(N, N, N, N, N, N, N, N, N, N, N, N, N, rows, D, 0.01, io, N)  # noqa: E731
+    # an invalid io_type, with empty rows (which the forwards would otherwise answer with 0): the `_16` entries have no fp32 form
+    for io in (0, 3, -1):
+        assert ln_fwd16(0, 512, io) == EINVAL and ln_bwd16(0, 512, io) == EINVAL, io
+    for io in (3, -1):
+        assert out_fwd(0, 512, io) == EINVAL and out_bwd(0, 512, io) == EINVAL, io
+    # empty rows with a bad width: the forward returns before it looks at D, the backward looks at D first
+    for D in (0, 300, 1280):
+        assert ln_fwd(0, D) == 0 and ln_fwd16(0, D, 1) == 0 and ln_fwd16(0, D, 2) == 0, D
+        assert ln_bwd(0, D) == ERANGE and ln_bwd16(0, D, 1) == ERANGE and ln_bwd16(0, D, 2) == ERANGE, D
+    for D in (0, 768, 1024):                               # (the first block: 256 or 512 only)
+        assert all(out_fwd(0, D, io) == 0 and out_bwd(0, D, io) == ERANGE for io in (0, 1, 2)), D
+    # a null grad_gamma with empty rows: an empty shard still writes its zero parameter gradients
+    assert ln_bwd(0, 768) == EINVAL and ln_bwd16(0, 1024, 1) == EINVAL and ln_bwd16(0, 256, 2) == EINVAL
+    assert all(out_bwd(0, D, io) == EINVAL for D in (256, 512) for io in (0, 1, 2))
+    # a bad width with null pointers: the forward reports the pointers, the backward the width
+    assert ln_fwd(4, 300) == EINVAL and ln_fwd16(4, 300, 1) == EINVAL and out_fwd(4, 768, 0) == EINVAL and out_fwd(4, 768, 2) == EINVAL
+    assert ln_bwd(4, 300) == ERANGE and ln_bwd16(4, 300, 2) == ERANGE and out_bwd(4, 768, 0) == ERANGE and out_bwd(4, 768, 1) == ERANGE
+    # negative rows, good width
+    assert ln_fwd(-1, 512) == EINVAL and ln_bwd(-1, 512) == EINVAL and out_fwd(-1, 512, 0) == EINVAL and out_bwd(-1, 512, 0) == EINVAL
+    # the heads and column-sum entries take all three types, and answer empty input before the type
+    assert L.ddsp_heads_sigmoid_forward(N, N, N, N, 0, 1, 1, 1, 7, N) == 0 and L.ddsp_heads_sigmoid_backward(N, N, N, N, N, 0, 1, 1, 1, 7, N) == 0
+    word = ctypes.c_uint64(0)                      # (a valid address; nothing is read from it)
+    p = ctypes.addressof(word)
+    assert L.ddsp_heads_sigmoid_forward(p, p, p, p, 1, 1, 1, 1, 7, N) == EINVAL
+    assert L.ddsp_heads_sigmoid_backward(p, p, p, p, p, 1, 1, 1, 1, 7, N) == EINVAL
+    assert L.ddsp_colsum(p, p, p, 8, 4, 7, N) == EINVAL and L.ddsp_colsum(N, N, N, 8, 0, 7, N) == 0
+
+
 def test_module_boundary_matches_reference_contract():
     osc = ddsp.OscillatorBank(Conf(60, 16000, 128))
     sd = osc.state_dict()
