@@ -7,7 +7,9 @@
                              encoder, then Decoder.forward_live -> (audio as numpy, hidden)
 
 State-dict keys are the reference's (`encoder.f0_encoder.model.*`, `encoder.loudness_encoder.a_weight`, `decoder.*`).  CREPE
-weights come from `weights` or `conf.crepe_weights` (see encoder.F0Encoder); `voicing` is handed to `Encoder`.  The decoder's synthesis runs on the device only.
+weights come from `weights` or `conf.crepe_weights` (see encoder.F0Encoder); `voicing` and `tracker` are handed to `Encoder`.
+With tracker 'yin' (the argument, else `conf.pitch_tracker`) no weights are needed and the state dict has no
+`encoder.f0_encoder.model.*` keys; decoder checkpoints load as before.  The decoder's synthesis runs on the device only.
 """
 from __future__ import annotations
 
@@ -21,9 +23,9 @@ from .encoder import Encoder
 
 
 class AutoEncoder(nn.Module):
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None):
         super().__init__()
-        self.encoder = Encoder(conf, weights, voicing=voicing)
+        self.encoder = Encoder(conf, weights, voicing=voicing, tracker=tracker)
         self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed)
         self.padding = conf.n_fft - conf.hop_length
         self.hop_length = conf.hop_length

@@ -255,7 +255,8 @@ class PLHDataset(Dataset):
     per encoder call (default conf.batch_size, the reference's DataLoader batch).
 
     With conf.pitch_voicing set, `f0` and `normalized_cents` are the gated ones (Encoder's `voicing`); `voiced` is not
-    stored.  The cache file records neither that setting nor conf.pitch_decoder: pass `clear` after changing either."""
+    stored.  With conf.pitch_tracker = 'yin' the pitch features come from pitch_salience_yin and no weights are needed.  The
+    cache file records none of these settings, nor conf.pitch_decoder: pass `clear` after changing one."""
 
     def __init__(self, conf, clear=False, weights=None, device=None, encode_batch=None):
         self.device = _device(device)

@@ -5,12 +5,14 @@
   F0Encoder        resample to 16 kHz -> normalise -> frame by 1024 -> CREPE -> pitch (encoder.py:13-128): the argmax bin by
                    default, or the nine-bin weighted average around the argmax ('weighted') or around a Viterbi path ('viterbi')
   pitch_argmax, pitch_centered, pitch_weighted, pitch_viterbi   the decoders themselves, over probabilities [B, T, 360]
+  pitch_salience_yin   a salience [B, T, 360] without a network: the YIN difference function of CREPE's own frames,
+                   cumulative-mean normalised and read at each bin's lag (one launch; `F0Encoder(tracker='yin')` decodes it)
   pitch_voicing    what follows a decoder: periodicity smoothing and hysteresis, loudness gate, median-filtered voiced pitch,
                    unvoiced gaps held or interpolated (one launch; `Encoder(voicing=...)` applies it, off by default)
   LoudnessEncoder  A-weighted loudness of the un-windowed STFT (encoder.py:131-156)
   Encoder          both, as the dict {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177)
 
-On CUDA tensors the work runs on hand-written HIP (csrc/ddsp_encoder.hip, csrc/ddsp_pitch.hip, csrc/ddsp_loudness.hip;
+On CUDA tensors the work runs on hand-written HIP (csrc/ddsp_encoder.hip, csrc/ddsp_pitch.hip, csrc/ddsp_yin.hip, csrc/ddsp_loudness.hip;
 include/ddsp_hip.h) around the library work it keeps: CREPE's convolutions on MIOpen (F.conv1d on a [N, C, L] view of the
 (k, 1) weights) and its classifier on rocBLAS.  CPU tensors run the reference's arithmetic as stock torch ops (the
 restatement the fixtures pin).
@@ -27,6 +29,7 @@ input that requires grad is refused rather than silently detached.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -39,11 +42,14 @@ from . import _lib
 
 PITCH_BINS = 360
 PITCH_DECODERS = ('argmax', 'weighted', 'viterbi')
+PITCH_TRACKERS = ('crepe', 'yin')
 CENTS_OF_BIN_0 = 1997.3794084376191
 CENTERED_HALF_WIDTH = 4                  # pitch_centered averages bins c - 4 .. c + 4
 VITERBI_BAND = 11                        # a Viterbi path moves at most 11 bins (220 cents) per frame
 CREPE_RATE = 16000
 CREPE_WINDOW = 1024
+YIN_LAGS = 512                           # the difference function: lags 0 .. 511, 512 terms each
+YIN_OCTAVE_COST = 0.05
 _BN_EPS = 0.0010000000474974513          # the MMdnn-converted CREPE's BatchNorm epsilon
 _LOWPASS_WIDTH = 6
 _ROLLOFF = 0.99
@@ -368,6 +374,79 @@ def pitch_viterbi(probabilities: torch.Tensor, state=None, return_state: bool = 
     return (bins, torch.from_numpy(last.astype(np.float32))) if want_state else bins
 
 
+# -------------------------------------------------------------------------------------------------------------- YIN salience
+# Definition: DESIGN.md section 10c (include/ddsp_hip.h: ddsp_yin_salience).  CUDA tensors take one launch of
+# csrc/ddsp_yin.hip; CPU tensors run the same arithmetic as fp32 torch ops.
+
+def yin_bin_table(octave_cost: float = YIN_OCTAVE_COST) -> torch.Tensor:
+    """The per-bin constants ddsp_yin_salience reads, [360, 4] fp32 = {i_b, w_b, cost_b, 0}: integer part and fraction of the
+    bin's lag tau_b = 16000 / f_b (f_b from pitch_tables) and cost_b = octave_cost * log2(tau_b / tau_359); built in fp64 and
+    rounded once."""
+    tau = CREPE_RATE / pitch_tables()[0].numpy().astype(np.float64)
+    whole = np.floor(tau)
+    table = np.zeros((PITCH_BINS, 4))
+    table[:, 0], table[:, 1], table[:, 2] = whole, tau - whole, float(octave_cost) * np.log2(tau / tau[-1])
+    assert whole.min() >= 1 and whole.max() + 2 < YIN_LAGS
+    return torch.from_numpy(table.astype(np.float32))
+
+
+def _yin_table_on(device, octave_cost: float) -> torch.Tensor:
+    key = ('yin_bin_table', str(device), float(octave_cost))
+    if key not in _DEVICE_TABLES:
+        _DEVICE_TABLES[key] = yin_bin_table(octave_cost).to(device)
+    return _DEVICE_TABLES[key]
+
+
+def _yin_salience_host(y: torch.Tensor, hop: int, table: torch.Tensor) -> torch.Tensor:
+    """ddsp_yin_salience as torch ops on y [B, Lr] fp32 (torch's own summation orders)."""
+    x = y.unfold(1, CREPE_WINDOW, hop)                                            # [B, T, 1024]
+    head = x[..., :YIN_LAGS]
+    d = torch.stack([((head - x[..., tau:tau + YIN_LAGS]) ** 2).sum(-1) for tau in range(YIN_LAGS)], dim=-1)
+    c = torch.cumsum(d[..., 1:], dim=-1)
+    lags = torch.arange(1, YIN_LAGS, dtype=torch.float32)
+    one = torch.ones((), dtype=torch.float32)
+    dp = torch.cat([torch.ones_like(d[..., :1]), torch.where(c > 0, (d[..., 1:] * lags) / c, one)], dim=-1)
+    i = table[:, 0].long().clamp(1, YIN_LAGS - 3)
+    u, cost = table[:, 1], table[:, 2]
+    p0, p1, p2, p3 = dp[..., i - 1], dp[..., i], dp[..., i + 1], dp[..., i + 2]
+    k3 = 3 * (p1 - p2) + (p3 - p0)
+    k2 = 4 * p2 + (-5 * p1 + (2 * p0 - p3))
+    v = (0.5 * u) * (u * (u * k3 + k2) + (p2 - p0)) + p1
+    s = (1 - v) - cost
+    s = torch.where(torch.isfinite(s), s.clamp(0, 1), torch.zeros((), dtype=torch.float32))
+    dead = ~torch.isfinite(x).all(dim=-1, keepdim=True)                           # a frame with a sample that is not finite
+    return torch.where(dead, torch.zeros((), dtype=torch.float32), s)
+
+
+def pitch_salience_yin(audio16k: torch.Tensor, hop: int, octave_cost: float = YIN_OCTAVE_COST) -> torch.Tensor:
+    """A pitch salience [B, T, 360] on CREPE's bin grid without CREPE: audio16k [B, Lr] at 16 kHz (what `Resample` returns),
+    frames of 1024 samples every `hop` (CREPE's own, not normalised), T = 1 + (Lr - 1024) // hop.  Per frame the YIN
+    difference function d(tau) = sum_{j < 512} (x[j] - x[j + tau])^2 over tau = 0 .. 511, its cumulative-mean normalisation
+    d', and per bin the Catmull-Rom value of d' at the bin's lag 16000 / f_b: salience = clip(1 - d' - octave_cost *
+    log2(lag_b / lag_359), 0, 1).  `octave_cost` breaks the tie between a period and its multiples towards the period.  A
+    frame with a sample that is not finite, a silent and a constant frame are 0 in every bin.  The decoders (pitch_argmax,
+    pitch_weighted, pitch_viterbi + pitch_centered) and pitch_voicing read it as they read CREPE's probabilities; the peak
+    value is the periodicity.  DESIGN.md section 10c has the definition and its limits."""
+    what = "pitch_salience_yin"
+    if audio16k.dim() != 2:
+        raise ValueError(f"{what}: audio must be [B, Lr], got {tuple(audio16k.shape)}")
+    _refuse_grad(audio16k, what)
+    B, Lr = audio16k.shape
+    hop = int(hop)
+    if Lr < CREPE_WINDOW or hop < 1:
+        raise ValueError(f"{what}: needs at least {CREPE_WINDOW} samples and a positive hop, got {Lr} samples and hop {hop}")
+    T = 1 + (Lr - CREPE_WINDOW) // hop
+    if audio16k.is_cuda:
+        y = audio16k.detach().contiguous().float()
+        probs = torch.empty((B, T, PITCH_BINS), device=y.device, dtype=torch.float32)
+        with torch.cuda.device(y.device):
+            rc = _lib.lib().ddsp_yin_salience(y.data_ptr(), _yin_table_on(y.device, octave_cost).data_ptr(), probs.data_ptr(),
+                                              B, Lr, hop, T, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_yin_salience")
+        return probs
+    return _yin_salience_host(audio16k.detach().float(), hop, yin_bin_table(octave_cost))
+
+
 # ------------------------------------------------------------------------------------------------------------------ voicing
 # Definition: DESIGN.md section 10b (include/ddsp_hip.h: ddsp_pitch_voicing).  CUDA tensors take one launch of
 # csrc/ddsp_pitch.hip; CPU tensors run the same definition in numpy.
@@ -554,10 +633,22 @@ class F0Encoder(nn.Module):
     rather than run untrained weights.
 
     `decoder` (else conf.pitch_decoder, else 'argmax') chooses how the probabilities become a pitch: 'argmax' (the
-    reference's forward), 'weighted' (pitch_weighted) or 'viterbi' (pitch_centered around the bins of pitch_viterbi)."""
+    reference's forward), 'weighted' (pitch_weighted) or 'viterbi' (pitch_centered around the bins of pitch_viterbi).
 
-    def __init__(self, conf, weights=None, decoder=None):
+    `tracker` (else conf.pitch_tracker, else 'crepe') chooses where the probabilities come from: 'crepe', or 'yin'
+    (pitch_salience_yin on the same resampled audio and hop: no weights, no `model` submodule and so no `model.*` state-dict
+    keys; `probabilities` is the YIN salience and `harmonicity` its value at the decoded bin).  Unlike CREPE's sigmoid, the
+    salience can be 0 in every bin (silence, a constant, some noise frames): 'argmax' then returns bin 0 with harmonicity 0,
+    'weighted' and 'viterbi' return NaN as pitch_centered does for any all-zero row; pitch_voicing (`Encoder(voicing=...)`)
+    marks such frames unvoiced and fills them."""
+
+    def __init__(self, conf, weights=None, decoder=None, tracker=None):
         super().__init__()
+        if tracker is None:
+            tracker = getattr(conf, 'pitch_tracker', 'crepe')
+        if tracker not in PITCH_TRACKERS:
+            raise ValueError(f"pitch tracker {tracker!r}: expected one of {PITCH_TRACKERS}")
+        self.tracker = tracker
         if decoder is None:
             decoder = getattr(conf, 'pitch_decoder', 'argmax')
         if decoder not in PITCH_DECODERS:
@@ -568,16 +659,18 @@ class F0Encoder(nn.Module):
         self.hop_length = conf.hop_length
         self.window_size = conf.n_fft
         self.rs = Resample(conf.sample_rate, CREPE_RATE)
-        self.model = Crepe(conf.crepe_capacity)
-        if weights is None:
-            weights = getattr(conf, 'crepe_weights', None)
-        if weights is None:
-            raise ValueError("F0Encoder needs CREPE weights: pass weights=<path or state dict> or set conf.crepe_weights "
-                             f"(a '{conf.crepe_capacity}' CREPE state dict; this package ships none)")
-        self.model.load_state_dict(_load_crepe_weights(weights), strict=True)
-        self.model.eval()
-        for p in self.model.parameters():
-            p.requires_grad = False
+        self.octave_cost = YIN_OCTAVE_COST
+        if tracker == 'crepe':
+            self.model = Crepe(conf.crepe_capacity)
+            if weights is None:
+                weights = getattr(conf, 'crepe_weights', None)
+            if weights is None:
+                raise ValueError("F0Encoder needs CREPE weights: pass weights=<path or state dict> or set conf.crepe_weights "
+                                 f"(a '{conf.crepe_capacity}' CREPE state dict; this package ships none)")
+            self.model.load_state_dict(_load_crepe_weights(weights), strict=True)
+            self.model.eval()
+            for p in self.model.parameters():
+                p.requires_grad = False
         f0_table, cents_table = pitch_tables()
         self.register_buffer("f0_table", f0_table, persistent=False)
         self.register_buffer("cents_table", cents_table, persistent=False)
@@ -623,6 +716,8 @@ class F0Encoder(nn.Module):
     def forward(self, batch: torch.Tensor):
         _refuse_grad(batch, "F0Encoder")
         with torch.no_grad():
+            if self.tracker == 'yin':
+                return self._forward_yin(batch)
             if batch.is_cuda:
                 return self._forward_device(batch)
             orig_len = batch.shape[1]
@@ -639,6 +734,16 @@ class F0Encoder(nn.Module):
             bins = probabilities.argmax(dim=-1, keepdim=True)
             freq = 10 * 2 ** ((bins * 20 + 1997.3794084376191) / 1200)
             return freq, probabilities.gather(-1, bins), probabilities, bins / 359.
+
+    def _forward_yin(self, batch: torch.Tensor):
+        """Either device: resample, the YIN salience on CREPE's hop grid, this encoder's decoder."""
+        if batch.is_cuda:
+            batch = batch.contiguous().float()
+        with torch.cuda.device(batch.device) if batch.is_cuda else contextlib.nullcontext():
+            y = self.rs(batch)
+            probabilities = pitch_salience_yin(y, self.resampled_hop(batch.shape[1], y.shape[1]), self.octave_cost)
+            freq, harmonicity, normalized_cents = self.decode(probabilities)
+        return freq, harmonicity, probabilities, normalized_cents
 
     def _forward_device(self, batch: torch.Tensor):
         L = _lib.lib()
@@ -717,12 +822,14 @@ class Encoder(nn.Module):
 
     `voicing` (else conf.pitch_voicing, else off): True, or a dict of pitch_voicing's keyword arguments (VOICING_OPTIONS),
     runs pitch_voicing on the decoded pitch with this encoder's own loudness: `f0` and `normalized_cents` are replaced and
-    `voiced` (bool [B, T, 1]) is added; `harmonicity` and `probabilities` stay as decoded.  Off, the dict is the reference's."""
+    `voiced` (bool [B, T, 1]) is added; `harmonicity` and `probabilities` stay as decoded.  Off, the dict is the reference's.
 
-    def __init__(self, conf, weights=None, voicing=None):
+    `tracker` (else conf.pitch_tracker, else 'crepe') is F0Encoder's: 'yin' needs no weights."""
+
+    def __init__(self, conf, weights=None, voicing=None, tracker=None):
         super().__init__()
         self.conf = conf
-        self.f0_encoder = F0Encoder(conf, weights)
+        self.f0_encoder = F0Encoder(conf, weights, tracker=tracker)
         self.loudness_encoder = LoudnessEncoder(conf)
         self.voicing = voicing_options(getattr(conf, 'pitch_voicing', None) if voicing is None else voicing)
 

@@ -439,6 +439,26 @@ int ddsp_pitch_voicing(const float *f0, const float *normalized, const float *pe
                        float lower, float silence, int fill, void *stream);
 
 /*
+ * YIN salience on CREPE's bin grid: a second source of the [B, T, 360] array the pitch decoders read.
+ * y [B, Lr] fp32 at 16 kHz (what ddsp_resample returns) -> probs [B, T, 360]; frame t of row b is x = y[b, t hop .. t hop + 1024),
+ * CREPE's framing without its normalisation.  Per frame, all fp32:
+ *   d(tau)  = sum_{j = 0}^{511} (x[j] - x[j + tau])^2, tau = 0 .. 511, terms added in ascending j (each term one FMA on the
+ *             rounded difference)
+ *   c(tau)  = d(1) + ... + d(tau);  d'(0) = 1, d'(tau) = fl(d(tau) tau) / c(tau) where c(tau) > 0, else 1
+ *   bin b:  v = Catmull-Rom through d'(i_b - 1), d'(i_b), d'(i_b + 1), d'(i_b + 2) at w_b,
+ *           probs = clip(1 - v - cost_b, 0, 1), and 0 where that is not finite
+ * A frame that holds a sample which is not finite is 0 in every bin.
+ * bin_table [360, 4] fp32, 16-byte aligned, row b = {i_b, w_b, cost_b, unused}: the integer part (stored as a float; the kernel
+ * clamps it to 1 .. 509 so that no table can make it read outside d') and the fraction of the bin's lag 16000 / f_b, and the
+ * bin's octave cost, built by the caller in fp64 (encoder.yin_bin_table).
+ * (T - 1) hop + 1024 <= Lr, Lr >= 1024 and hop > 0, DDSP_EINVAL otherwise; B Lr or 360 B T beyond 2^60 is DDSP_ERANGE.  One
+ * launch, one wavefront per frame (grid-strided beyond 8192 frames), no atomics, no allocation, no host synchronisation;
+ * no alignment is assumed of y, its rows or its frames.  Every sum has one order: a frame's result is the same bits from run
+ * to run and whatever else is in the batch.
+ */
+int ddsp_yin_salience(const float *y, const float *bin_table, float *probs, long B, long Lr, int hop, long T, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
