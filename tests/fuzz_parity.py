@@ -6,10 +6,11 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward]   (`training`: the loss-side kernels against
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru]   (`training`: the loss-side kernels against
 fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
 backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
-fp64 reference of tests/noise_grad_reference.py)"""
+fp64 reference of tests/noise_grad_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
+reference of tests/gru_reference.py)"""
 import os
 import sys
 
@@ -25,6 +26,7 @@ from oracle import oracle  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import osc_grad_reference as R  # noqa: E402
 import noise_grad_reference as R_noise  # noqa: E402
+import gru_reference as R_gru  # noqa: E402
 
 
 def bits(a):
@@ -499,6 +501,120 @@ def sweep_noise_backward(cases: int, seed: int, verbose: bool = True):
     return bad, worst
 
 
+# ---- the GRU recurrence (csrc/ddsp_gru.hip) step by step against the fp64 reference of tests/gru_reference.py -------------------
+def gru_case(B, T, Hd, lowp, seed, h0=True, bias=True, dhT=True, io16=None, spread=False, keep=False):
+    """One forward (saving and not saving) and one backward of the raw launchers on the inputs of gru_reference.make_inputs, against
+    the teacher-forced fp64 reference with the rounding gru_reference.plan predicts for every batch row.  `io16` (default: with
+    every bf16 backward): the same backward with 16-bit d_gi / d_gh.  `spread`: under ddsp_gru_set_mode(1).
+    -> dict: plan_fwd / plan_bwd (lists of Slice), fwd / bwd ({tensor: Measure}), bad (messages: empty when every check of the
+    criterion holds -- bounds, non-vacuity, status words, hT == y[:, -1] and save=False == save=True bitwise, the io16 checks);
+    keep: + 'out', the device tensors (y, hT, gates, hn, d_gi, d_gh, dh0)."""
+    from ddsp_pytorch_amd import gru as gru_mod
+    L = ddsp._lib.lib()
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    x = R_gru.make_inputs(B, T, Hd, seed, h0, bias, dhT)
+    d = {k: (None if v is None else v.cuda()) for k, v in x.items()}
+    r = {"plan_fwd": R_gru.plan(B, Hd, cus, lowp, False, spread, T), "plan_bwd": R_gru.plan(B, Hd, cus, lowp, True, spread, T)}
+    bwd_mfma = all(s.mfma for s in r["plan_bwd"])
+    io16 = lowp if io16 is None else (io16 and lowp)
+    used = []
+    try:
+        if spread:
+            ddsp._lib.check(L.ddsp_gru_set_mode(1), "ddsp_gru_set_mode")
+        y, hT, gates, hn = gru_mod.gru_forward(d["gi"], d["w"], d["b"], d["h0"], save=True, scratch_out=used, lowp=lowp)
+        y2, hT2, g2, hn2 = gru_mod.gru_forward(d["gi"], d["w"], d["b"], d["h0"], save=False, scratch_out=used, lowp=lowp)
+        d_gi, d_gh, dh0 = gru_mod.gru_backward(d["dy"], d["dhT"], d["w"], d["h0"], y, gates, hn, scratch_out=used, lowp=lowp)
+        if io16:
+            h_gi, h_gh, h_dh0 = gru_mod.gru_backward(d["dy"], d["dhT"], d["w"], d["h0"], y, gates, hn, scratch_out=used, lowp=True, io16=True)
+        status = [gru_mod.gru_status(s) for s in used]
+    finally:
+        if spread:
+            L.ddsp_gru_set_mode(0)
+    bad = []
+    if any(status):
+        bad.append(f"status words {status}")
+    if g2 is not None or hn2 is not None:
+        bad.append("save=False returned saved tensors")
+    if not torch.equal(hT, y[:, -1]):
+        bad.append("hT != y[:, -1]")
+    if not (torch.equal(y, y2) and torch.equal(hT, hT2)):
+        bad.append("save=False differs from save=True")
+    c = lambda t: t.cpu()      # noqa: E731
+    yc, gc, hnc = c(y), c(gates), c(hn)
+    rows_f, rows_b = R_gru.rounded_rows(r["plan_fwd"]), R_gru.rounded_rows(r["plan_bwd"])
+    r["fwd"] = R_gru.forward_measures(x, yc, c(hT), gc, hnc, rows_f)
+    r["bwd"] = R_gru.backward_measures(x, yc, gc, hnc, c(d_gi), c(d_gh), c(dh0), rows_b)
+    bad += ["forward " + m for m in R_gru.failures(r["fwd"], T)] + ["backward " + m for m in R_gru.failures(r["bwd"], T)]
+    if io16:
+        if h_gi.dtype != torch.bfloat16 or h_gh.dtype != torch.bfloat16:
+            bad.append("io16 outputs are not bf16")
+        if not torch.equal(h_dh0, dh0):
+            bad.append("io16: dh0 differs from the fp32-output launch")
+        if bwd_mfma:
+            # one bf16 ulp of the reference teacher-forced from the 16-bit d_gh itself: half an ulp of the kernel's fp32 value (its
+            # rounding to bf16) + that value's own fp32 error, which the criterion bounds by MARGIN x e32 of the tensor's largest entry
+            args = (x["dy"], x["dhT"], x["w"], x["h0"], yc, gc, hnc, c(h_gh))
+            ref = R_gru.backward_steps(*args, torch.float64, rows_b)
+            ref32 = R_gru.backward_steps(*args, torch.float32, rows_b)
+            for name, got, want, w32 in zip(("d_gi", "d_gh"), (h_gi, h_gh), ref, ref32):
+                top = float(want.abs().max())
+                tol = R_gru.bf16_ulp(want) + R_gru.MARGIN * float((w32.double() - want).abs().max())
+                over = float(((c(got).double() - want).abs() - tol).max())
+                r["io16_" + name] = float(((c(got).double() - want).abs() / tol).max())       # <= 1 passes
+                if not over <= 0.0:
+                    bad.append(f"io16 {name}: {over:.3e} (of a largest entry {top:.3e}) beyond one bf16 ulp of the reference")
+            if not float((c(h_dh0).double() - ref[2]).abs().max()) <= R_gru.MARGIN * float((ref32[2].double() - ref[2]).abs().max()):
+                bad.append("io16 dh0 against the reference teacher-forced from the 16-bit d_gh")
+        else:   # T >= 65536: the fp32 backward ran and gru.py cast its outputs
+            if not (torch.equal(h_gi, d_gi.to(torch.bfloat16)) and torch.equal(h_gh, d_gh.to(torch.bfloat16))):
+                bad.append("io16 fallback: not the bf16 cast of the fp32 outputs")
+    r["bad"] = bad
+    r["ratio_fwd"], r["ratio_bwd"] = R_gru.worst_ratio(r["fwd"]), R_gru.worst_ratio(r["bwd"])
+    r["family_fwd"] = ("bf16" if any(s.mfma for s in r["plan_fwd"]) else "fp32") + " forward"
+    r["family_bwd"] = ("bf16" if bwd_mfma else "fp32") + " backward"
+    if keep:
+        r["out"] = (y, hT, gates, hn, d_gi, d_gh, dh0)
+    return r
+
+
+def gru_case_line(r):
+    return (f"{r['family_fwd']} {'+'.join(s.kernel for s in r['plan_fwd'])} BL {[s.BL for s in r['plan_fwd']]} last {[s.last for s in r['plan_fwd']]}: "
+            f"{r['ratio_fwd']:.2f} x e32 [{R_gru.describe(r['fwd'])}] | {r['family_bwd']} {'+'.join(s.kernel for s in r['plan_bwd'])} "
+            f"BL {[s.BL for s in r['plan_bwd']]}: {r['ratio_bwd']:.2f} x e32 [{R_gru.describe(r['bwd'])}]"
+            + "".join(f" | {k} {v:.2f} of (1 bf16 ulp + the fp32 bound)" for k, v in r.items() if k.startswith("io16_")))
+
+
+def sweep_gru(cases: int, seed: int, verbose: bool = True, counts: dict | None = None):
+    """Random shapes of the GRU recurrence against the fp64 reference: Hd in 1 .. 512 (the four KP classes equally often, so that a
+    short sweep reaches every instantiation's class), B in 1 .. 300, T in 1 .. 12, random lowp / h0 / bias / dhT / io16.  (T = 1
+    without h0 multiplies W_hh by zeros only -- no rounding to tell apart, the non-vacuity condition cannot hold: such a draw gets
+    an h0.)  `counts` receives {kernel instantiation: launches' cases}.  -> (failed, {family: worst error / e32})"""
+    rng = np.random.default_rng(seed)
+    worst = {}
+    counts = {} if counts is None else counts
+    bad = 0
+    for i in range(cases):
+        lo, hi = [(1, 64), (65, 128), (129, 256), (257, 512)][int(rng.integers(4))]
+        Hd = int(rng.integers(lo, hi + 1))
+        B = int(rng.integers(1, 301))
+        T = int(rng.integers(1, 13))
+        lowp, h0, bias, dhT, io16 = (bool(rng.random() < 0.5) for _ in range(5))
+        h0 = h0 or T == 1
+        r = gru_case(B, T, Hd, lowp, int(rng.integers(1 << 30)), h0=h0, bias=bias, dhT=dhT, io16=io16)
+        okay = not r["bad"]
+        bad += not okay
+        for s in r["plan_fwd"] + r["plan_bwd"]:
+            counts[s.kernel] = counts.get(s.kernel, 0) + 1
+        worst[r["family_fwd"]] = max(worst.get(r["family_fwd"], 0.0), r["ratio_fwd"])
+        worst[r["family_bwd"]] = max(worst.get(r["family_bwd"], 0.0), r["ratio_bwd"])
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} gru B{B} T{T} Hd{Hd} lowp {int(lowp)} h0 {int(h0)} bias {int(bias)} dhT {int(dhT)} io16 {int(io16)}: "
+                  f"{gru_case_line(r)}{'' if okay else ' ' + '; '.join(r['bad'])}", flush=True)
+    if verbose:
+        print("kernel instantiations reached: " + ", ".join(f"{k} x{v}" for k, v in sorted(counts.items())), flush=True)
+    return bad, worst
+
+
 def sweep_training_kernels(cases: int, seed: int, verbose: bool = True):
     """Random shapes of the loss-side kernels against torch on the CPU in fp64: ddsp_mss_scale (+ the overlap-add gather) for random
     batch / length / transform size / overlap, the framing pair around a library rfft, and the column sums.  -> failed cases"""
@@ -592,6 +708,13 @@ def main():
         bad, worst = sweep_noise_backward(cases, seed, verbose=False)
         print(f"noise backward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per form: "
               + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
+        sys.exit(1 if bad else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "gru":
+        counts = {}
+        bad, worst = sweep_gru(cases, seed, verbose=False, counts=counts)
+        print(f"GRU recurrence: cases {cases}, seed {seed}, failed {bad}; worst error / e32 per family: "
+              + ", ".join(f"{k} {v:.2f}" for k, v in sorted(worst.items())) + "; instantiations reached: "
+              + ", ".join(f"{k} x{v}" for k, v in sorted(counts.items())))
         sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "training":
         bad = sweep_training_kernels(cases, seed, verbose=False)

@@ -1,6 +1,7 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
 oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
-plus the chunked oscillator form, the loss-side kernels and the backward of the oscillator and of the filtered noise."""
+plus the chunked oscillator form, the loss-side kernels, the backward of the oscillator and of the filtered noise, and the GRU
+recurrence step by step against fp64."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,3 +41,14 @@ def test_random_shapes_of_the_noise_backward_match_fp64(seed):
     fuzz_parity.NOISE_BWD_TOL of each frame's yardstick: every kernel form, injected and in-kernel draws, forced modes, zero frames."""
     bad, worst = fuzz_parity.sweep_noise_backward(40, seed, verbose=False)
     assert bad == 0, (bad, worst)
+
+
+@pytest.mark.parametrize("seed", [707])
+def test_random_shapes_of_the_gru_recurrence_match_fp64_step_by_step(seed):
+    """40 random cases of the GRU recurrence's raw launchers against the teacher-forced fp64 reference (tests/gru_reference.py), every
+    tensor within 8 x the same formulas' fp32 error: fp32 and bf16 kernels, with and without h0 / bias / dhT, 16-bit gradient outputs.
+    The seed reaches both bf16 matrix-core kernels at all four KP."""
+    counts = {}
+    bad, worst = fuzz_parity.sweep_gru(40, seed, verbose=False, counts=counts)
+    assert bad == 0, (bad, worst)
+    assert {f"gru_{d}_mfma_kernel<{KP}>" for d in ("fwd", "bwd") for KP in (4, 8, 16, 32)} <= set(counts), counts

@@ -362,6 +362,16 @@ def test_gru_bf16_matrix_core_variant_tracks_fp32(B, T, hd, with_h0):
         cos = float((a * c).sum() / (a.norm() * c.norm() + 1e-30))
         assert cos >= 0.999, (name, cos)
         assert float((a - c).abs().max()) <= 5e-2 * float(a.abs().max()), name
+    # The bounds above state how far the two precisions lie apart.  Whether the bf16 kernels compute what they are meant to is a
+    # sharper question: every step against fp64 from the kernel's own previous output (tests/gru_reference.py), fp32 round-off only.
+    import gru_reference as R
+    host = lambda t: None if t is None else t.cpu()      # noqa: E731
+    x = dict(gi=host(gi), w=host(w), b=host(b), h0=host(h0), dy=host(dy), dhT=host(dhT))
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_f, rows_b = (R.rounded_rows(R.plan(B, hd, cus, True, backward, T=T)) for backward in (False, True))
+    fwd = R.forward_measures(x, *(host(t) for t in got), rows_f)
+    bwd = R.backward_measures(x, host(y), host(gates), host(hn), *(host(t) for t in gb), rows_b)
+    assert not R.failures(fwd, T) and not R.failures(bwd, T), (R.failures(fwd, T), R.failures(bwd, T))
 
 
 @pytest.mark.gpu
