@@ -939,22 +939,6 @@ bool plan_gru(int B, int Hd, int cus, int max_rows, bool spread, GruPlan *pl)
     return pl->BL <= max_rows;
 }
 
-int device_cus(int *cus)
-{
-    static int cached[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    if (!cached[dev & 63]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return (int)e;
-        cached[dev & 63] = n;
-    }
-    *cus = cached[dev & 63];
-    return 0;
-}
-
 size_t xchg_bytes(const GruPlan &pl, int payloads) { return (size_t)pl.NG * 2 * pl.BL * payloads * pl.HP * sizeof(unsigned long long); }
 
 // Co-residency guard, part 1: every workgroup of the grid spins on its peers, so the whole grid has to be resident at
@@ -967,7 +951,7 @@ hipError_t check_resident(K kernel, int threads, size_t lds, unsigned grid, int 
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    if (device_cus(&cus)) return hipErrorInvalidDevice;
+    if (ddsp_device_cus(&cus) != hipSuccess) return hipErrorInvalidDevice;
     int &per_cu = cache[dev & 63];
     if (per_cu == 0) {
         int n = 0;
@@ -1032,8 +1016,8 @@ hipError_t launch_mfma(const GruParams &p, bool backward, hipStream_t s)
 int run_gru(GruParams &p, void *scratch, bool backward, hipStream_t s)
 {
     int cus = 0;
-    const int rc = device_cus(&cus);
-    if (rc) return rc;
+    const hipError_t ce = ddsp_device_cus(&cus);
+    if (ce != hipSuccess) return (int)ce;
     GruPlan pl;
     const int mode = g_gru_mode.load(std::memory_order_relaxed);   // test hooks: one snapshot per launch
     const int max_rows = p.lowp ? kMfmaRows : (backward ? kMaxRowsBwd : kMaxRows);
@@ -1139,7 +1123,7 @@ extern "C" size_t ddsp_gru_scratch_bytes(int B, int Hd)
 extern "C" int ddsp_gru_max_batch(int Hd, int backward)
 {
     int cus = 0;
-    if (device_cus(&cus)) return 0;
+    if (ddsp_device_cus(&cus) != hipSuccess) return 0;
     GruPlan pl;
     if (!plan_gru(1, Hd, cus, 1, false, &pl)) return 0;
     const int slots = resident_slots(cus, pl.NW, false);

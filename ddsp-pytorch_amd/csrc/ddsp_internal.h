@@ -27,6 +27,24 @@ inline hipError_t ddsp_allow_big_lds(const void *fn, bool (&done)[64])
     return e;
 }
 
+// Compute units of the current device, asked once per device of this process.  No lock, as ddsp_allow_big_lds above: two threads
+// that race both store the same count.
+inline hipError_t ddsp_device_cus(int *cus)
+{
+    static int cached[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (!cached[dev & 63]) {
+        int n = 0;
+        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+        cached[dev & 63] = n;
+    }
+    *cus = cached[dev & 63];
+    return hipSuccess;
+}
+
 // scratch carving: offsets rounded up to 256 bytes
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 

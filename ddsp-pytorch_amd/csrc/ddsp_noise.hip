@@ -10,8 +10,9 @@
 // kernel was left-padded by R: that is exactly the first R samples of the linear convolution, the
 // tail is discarded and frames are concatenated with no overlap-add (:50-51).
 //
-// This first version evaluates the inverse real DFT and the truncated convolution directly in fp32
-// (F and R/2 multiply-adds per output); see DESIGN.md §5 for the planned in-LDS FFT form.
+// Here: the two entry points (validate -> plan, ddsp_noise_plan.h -> launch) and the direct kernels, which evaluate the inverse
+// real DFT and the truncated convolution in fp32 as written above (F and R/2 multiply-adds per output) and take every shape.  The
+// faster forms of particular shapes have their own sources (ddsp_noise_common.h lists them).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,7 +26,10 @@ using namespace ddsp_noise;
 
 namespace {
 
-std::atomic<int> g_force_generic{0};  // ddsp_noise_set_generic: tests exercise the one-frame-per-workgroup kernel (read once per launch)
+std::atomic<int> g_noise_mode{0};     // ddsp_noise_set_generic: the kMode* bits of ddsp_noise_plan.h (tests, A/B runs; read once per launch)
+static_assert(kPlanERange == DDSP_ERANGE, "the planner's status is the ABI's");
+
+inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr % 16) == 0; }
 
 __global__ void __launch_bounds__(256) noise_frame_kernel(NoiseParams p)
 {
@@ -511,56 +515,39 @@ __global__ void __launch_bounds__(kNT) noise_bwd_batched_kernel(NoiseBwdParams p
     }
 }
 
-size_t bwd_batched_lds_bytes(int F, int R, int lpf_log)
+// One launch of a direct kernel: the opt-in to more than 64 KiB of LDS (once per kernel and device), the profile slot (the forward's
+// launches have one), the launch.
+template <auto Kernel, int Threads, bool Profiled, typename Params>
+hipError_t launch_direct(const Params &p, long grid, size_t lds, hipStream_t s)
 {
-    const int S = 2 * (F - 1), FB = 64 >> lpf_log;
-    return sizeof(float) * (((S + 3) & ~3) + (size_t)FB * (R + 4) + (size_t)FB * (R + 12) + (size_t)(S / 2 + 1) * (FB + 4));
+    static bool attr_set[64] = {};
+    const hipError_t e = ddsp_allow_big_lds((const void *)Kernel, attr_set);
+    if (e != hipSuccess) return e;
+    const int slot = Profiled ? ddsp_prof::begin(ddsp_prof::NOISE, s) : 0;
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(Threads), lds, s, p);
+    if (Profiled) ddsp_prof::end(slot, s);
+    return hipGetLastError();
 }
 
-int pick_bwd_lpf_log(int F, int R)
+// The Batched / Frame kernel a forward plan names, on the frames p describes.
+hipError_t launch_noise_direct(NoiseForm form, const NoisePlan &pl, NoiseParams &p, hipStream_t s)
 {
-    for (int limit : {48 * 1024, 80 * 1024, 160 * 1024})
-        for (int l = 0; l <= 3; ++l)
-            if (bwd_batched_lds_bytes(F, R, l) <= (size_t)limit) return l;
-    return -1;
+    const long frames = (long)p.B * p.T;
+    if (form == NoiseForm::Frame) return launch_direct<noise_frame_kernel, 256, true>(p, frames, pl.lds_bytes, s);
+    using Launch = hipError_t (*)(const NoiseParams &, long, size_t, hipStream_t);
+    static const Launch by_lanes[4][2] = {       // [lpf_log][S is a power of two]
+        {launch_direct<noise_batched_kernel<0, false>, kNT, true>, launch_direct<noise_batched_kernel<0, true>, kNT, true>},
+        {launch_direct<noise_batched_kernel<1, false>, kNT, true>, launch_direct<noise_batched_kernel<1, true>, kNT, true>},
+        {launch_direct<noise_batched_kernel<2, false>, kNT, true>, launch_direct<noise_batched_kernel<2, true>, kNT, true>},
+        {launch_direct<noise_batched_kernel<3, false>, kNT, true>, launch_direct<noise_batched_kernel<3, true>, kNT, true>}};
+    p.lpf_log = pl.lpf_log;
+    const int fb = 64 >> pl.lpf_log;
+    return by_lanes[pl.lpf_log < 3 ? pl.lpf_log : 3][(p.S & (p.S - 1)) == 0](p, (frames + fb - 1) / fb, pl.lds_bytes, s);
 }
-
-size_t batched_lds_bytes(int F, int R, int lpf_log)
-{
-    const int S = 2 * (F - 1), FB = 64 >> lpf_log;
-    const size_t ua = (size_t)(FB + 4) * F, ub = (size_t)FB * (R + 12);
-    const size_t un = ua > ub ? ua : ub;
-    return sizeof(float) * (((S + 3) & ~3) + (size_t)FB * (R + 4) + un);
-}
-
-// Lanes per frame (log2) of the batched forward kernel: 64 frames per workgroup when the tile fits in ~half the
-// CU's LDS (two workgroups per CU), else 32 / 16 frames; -1 when even 16 frames do not fit (generic kernel then).
-int pick_lpf_log(int F, int R, int mode)
-{
-    if (mode >> 8) return (mode >> 8) - 1;  // tuning: ddsp_noise_set_generic((l + 1) << 8)
-    // measured (hop 128, F 65): 32 frames / 35 KB per workgroup (4 workgroups per CU) beats 64 frames / 70 KB by 14 %
-    for (int l = 0; l <= 3; ++l)
-        if (batched_lds_bytes(F, R, l) <= 40 * 1024) return l;
-    for (int l = 0; l <= 3; ++l)
-        if (batched_lds_bytes(F, R, l) <= 80 * 1024) return l;
-    for (int l = 0; l <= 3; ++l)
-        if (batched_lds_bytes(F, R, l) <= 160 * 1024) return l;
-    return -1;
-}
-
-// where the whole-batch matrix product pays for its extra launches (cosine operand + product; measured crossovers at 195 bands,
-// hop 512: forward between 2 752 and 5 504 frames, backward below 688): the real-time callback's 4 frames and the reference's
-// own training batch (16 x 172 frames) keep the cosine sums in the forward
-constexpr long kIrProductMinFramesFwd = 4096, kIrProductMinFramesBwd = 512;
 
 }  // namespace
 
-extern "C" size_t ddsp_noise_workspace_bytes(int B, int T, int F, int hop)
-{
-    if (B <= 0 || T <= 0 || F < 2 || hop <= 0) return 0;
-    const long frames = (long)B * T;
-    return (ir_product_shape(F, hop) && frames >= kIrProductMinFramesBwd) ? ir_workspace_bytes(frames, F) : 0;
-}
+extern "C" size_t ddsp_noise_workspace_bytes(int B, int T, int F, int hop) { return noise_workspace_bytes(B, T, F, hop); }
 
 extern "C" int ddsp_noise_forward_ws(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop, uint64_t seed,
                                      uint64_t offset, const uint64_t *counter_dev, int accumulate, void *workspace,
@@ -574,89 +561,44 @@ extern "C" int ddsp_noise_forward_ws(const float *Hmag, const float *uniform, fl
     p.B = B; p.T = T; p.F = F; p.R = hop; p.S = 2 * (F - 1);
     p.seed = seed; p.offset = offset; p.offset_dev = counter_dev; p.accumulate = accumulate; p.lpf_log = 0;
     p.zrows = nullptr; p.zs = 0;
-    if ((long)B * T >= (1L << 31)) return DDSP_ERANGE;
+    const long frames = (long)B * T;
+    if (frames >= (1L << 31)) return DDSP_ERANGE;
     hipStream_t s = (hipStream_t)stream;
-    const int mode = g_force_generic.load(std::memory_order_relaxed);
-    // 195 bands at hop 512 (the reference's default shape) with a workspace: the impulse responses of the whole batch as one
-    // matrix product (ddsp_noise_ir.hip), which the FFT form below then reads instead of summing cosines; mode bit 4 (tests, A/B) keeps the sums
-    if (workspace && !(mode & (3 | 16)) && ir_product_shape(F, hop) && (long)B * T >= kIrProductMinFramesFwd &&
-        workspace_bytes >= ir_workspace_bytes((long)B * T, F) && ((uintptr_t)workspace % 16) == 0) {
-        hipError_t ie = hipSuccess;
-        p.zrows = launch_noise_ir(Hmag, (long)B * T, F, workspace, s, &ie);
-        if (!p.zrows) return (int)ie;
-        p.zs = ir_row_stride(F);
-    }
-    // hop 512: the in-LDS FFT form (ddsp_noise_fft.hip); mode bit 1 (tests, A/B) keeps the direct forms, bit 2 takes the
-    // FFT form for hop 256 as well (correct there too, just not faster)
-    if (!(mode & 3)) {
-        hipError_t fe = hipSuccess;
-        if (launch_noise_fft(p, s, (mode & 4) != 0, &fe)) return (int)fe;
-    }
-    // hop 128 / 65 bands (the 16 kHz configurations): the wavefront-private form (ddsp_noise_wave.hip); mode bit 3 keeps the batched kernel
-    if (!(mode & (1 | 8))) {
-        hipError_t we = hipSuccess;
-        const long done = launch_noise_wave(p, s, &we);
-        if (done < 0) return (int)we;
-        if (done == (long)B * T) return 0;
-        if (done > 0) {                                       // a remainder of fewer than 16 frames: the kernels below, same counters
+    const NoiseFacts facts = {aligned16(y), aligned16(Hmag), uniform != nullptr, aligned16(uniform),
+                              workspace != nullptr, aligned16(workspace), workspace_bytes};
+    const NoisePlan pl = plan_noise_forward({B, T, F, hop}, g_noise_mode.load(std::memory_order_relaxed), facts);
+    if (pl.status) return pl.status;
+    switch (pl.form) {
+        case NoiseForm::Fft:
+            if (pl.ir_product) {
+                const hipError_t ie = launch_noise_ir(Hmag, frames, F, workspace, s);
+                if (ie != hipSuccess) return (int)ie;
+                p.zrows = ir_rows(workspace, F);
+                p.zs = ir_row_stride(F);
+            }
+            return (int)launch_noise_fft(p, s);
+        case NoiseForm::Wave: {
+            const hipError_t we = launch_noise_wave(p, pl.wave_frames, s);
+            if (we != hipSuccess || pl.rest == NoiseForm::None) return (int)we;
+            // a remainder of fewer than 16 frames: a direct kernel, same counters
+            const long done = pl.wave_frames;
             p.Hm += done * F;
             if (p.u) p.u += done * hop;
             p.y += done * hop;
             p.offset += (uint64_t)done * (uint64_t)((hop + 3) / 4);
-            B = 1;
-            T = (int)((long)p.B * p.T - done);
-            p.B = B;
-            p.T = T;
+            p.B = 1;
+            p.T = (int)(frames - done);
+            return (int)launch_noise_direct(pl.rest, pl, p, s);
         }
+        default:
+            return (int)launch_noise_direct(pl.form, pl, p, s);
     }
-    const int lpf_log = pick_lpf_log(F, hop, mode);
-    // (the batched kernel stores whole float4s: an output buffer that is not 16-byte aligned takes the generic kernel)
-    if (!(mode & 1) && hop % 8 == 0 && lpf_log >= 0 && ((uintptr_t)y % 16) == 0) {
-        const size_t blds = batched_lds_bytes(F, hop, lpf_log);
-        p.lpf_log = lpf_log;
-        const int fb = 64 >> lpf_log;
-        const long blocks = ((long)B * T + fb - 1) / fb;
-        const bool spow2 = (p.S & (p.S - 1)) == 0;
-        hipError_t le = hipSuccess;
-#define DDSP_NOISE_LAUNCH(L, P2)                                                                                       \
-        do {                                                                                                           \
-            static bool attr_set[64] = {};                                                                             \
-            le = ddsp_allow_big_lds((const void *)noise_batched_kernel<L, P2>, attr_set);                              \
-            if (le != hipSuccess) return (int)le;                                                                      \
-            const int slot = ddsp_prof::begin(ddsp_prof::NOISE, s);                                                    \
-            hipLaunchKernelGGL((noise_batched_kernel<L, P2>), dim3((unsigned)blocks), dim3(kNT), blds, s, p);          \
-            ddsp_prof::end(slot, s);                                                                                   \
-        } while (0)
-        switch (lpf_log * 2 + (spow2 ? 1 : 0)) {
-            case 0: DDSP_NOISE_LAUNCH(0, false); break;
-            case 1: DDSP_NOISE_LAUNCH(0, true); break;
-            case 2: DDSP_NOISE_LAUNCH(1, false); break;
-            case 3: DDSP_NOISE_LAUNCH(1, true); break;
-            case 4: DDSP_NOISE_LAUNCH(2, false); break;
-            case 5: DDSP_NOISE_LAUNCH(2, true); break;
-            case 6: DDSP_NOISE_LAUNCH(3, false); break;
-            default: DDSP_NOISE_LAUNCH(3, true); break;
-        }
-#undef DDSP_NOISE_LAUNCH
-        return (int)hipGetLastError();
-    }
-    const size_t lds = sizeof(float) * ((size_t)F + p.S + 2 * (size_t)hop);
-    if (lds > 160 * 1024) return DDSP_ERANGE;
-    {
-        static bool attr_set[64] = {};
-        const hipError_t ae = ddsp_allow_big_lds((const void *)noise_frame_kernel, attr_set);
-        if (ae != hipSuccess) return (int)ae;
-    }
-    const int slot = ddsp_prof::begin(ddsp_prof::NOISE, s);
-    hipLaunchKernelGGL(noise_frame_kernel, dim3((unsigned)((long)B * T)), dim3(256), lds, s, p);
-    ddsp_prof::end(slot, s);
-    return (int)hipGetLastError();
 }
 
 extern "C" int ddsp_noise_set_generic(int on)
 {
     if (on != 0 && !ddsp_hooks_on()) return DDSP_EPERM;
-    g_force_generic.store(on, std::memory_order_relaxed);
+    g_noise_mode.store(on, std::memory_order_relaxed);
     return 0;
 }
 
@@ -666,40 +608,22 @@ extern "C" int ddsp_noise_backward_ws(const float *grad_y, const float *uniform,
     if (uniform && counter_dev) return DDSP_EINVAL;
     if (B == 0) return 0;
     if (!grad_y || !grad_H || B < 0 || T <= 0 || F < 2 || hop <= 0) return DDSP_EINVAL;
-    if ((long)B * T >= (1L << 31)) return DDSP_ERANGE;
+    const long frames = (long)B * T;
+    if (frames >= (1L << 31)) return DDSP_ERANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const NoiseFacts facts = {aligned16(grad_y), true, uniform != nullptr, aligned16(uniform),
+                              workspace != nullptr, aligned16(workspace), workspace_bytes};
+    const NoisePlan pl = plan_noise_backward({B, T, F, hop}, g_noise_mode.load(std::memory_order_relaxed), facts);
+    if (pl.status) return pl.status;
+    if (pl.form == NoiseForm::Fft)
+        return (int)launch_noise_fft_backward(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, counter_dev,
+                                              pl.ir_product ? workspace : nullptr, s);
     NoiseBwdParams p;
     p.g = grad_y; p.u = uniform; p.gH = grad_H;
     p.B = B; p.T = T; p.F = F; p.R = hop; p.S = 2 * (F - 1);
+    p.lpf_log = pl.lpf_log;
     p.seed = seed; p.offset = offset; p.offset_dev = counter_dev;
-    hipStream_t s = (hipStream_t)stream;
-    if (!(g_force_generic.load(std::memory_order_relaxed) & 3)) {    // hop 512: correlation in the in-LDS FFT form (mode bits 0 / 1 keep the direct forms)
-        hipError_t fe = hipSuccess;
-        // (a workspace is used only by the shapes of ddsp_noise_workspace_bytes; mode bit 4 keeps the direct kernels there)
-        const bool ws_ok = workspace && !(g_force_generic.load(std::memory_order_relaxed) & 16) && ir_product_shape(F, hop) &&
-                           (long)B * T >= kIrProductMinFramesBwd && workspace_bytes >= ir_workspace_bytes((long)B * T, F) &&
-                           ((uintptr_t)workspace % 16) == 0;
-        if (launch_noise_fft_backward(grad_y, uniform, grad_H, B, T, F, hop, seed, offset, counter_dev, ws_ok ? workspace : nullptr, s, &fe))
-            return (int)fe;
-    }
-    const int lpf_log = pick_bwd_lpf_log(F, hop);
-    p.lpf_log = lpf_log < 0 ? 0 : lpf_log;
-    if (!(g_force_generic.load(std::memory_order_relaxed) & 1) && hop % 8 == 0 && lpf_log >= 0) {
-        const size_t blds = bwd_batched_lds_bytes(F, hop, lpf_log);
-        static bool attr_set[64] = {};
-        const hipError_t ae = ddsp_allow_big_lds((const void *)noise_bwd_batched_kernel, attr_set);
-        if (ae != hipSuccess) return (int)ae;
-        const int fb = 64 >> lpf_log;
-        const long blocks = ((long)B * T + fb - 1) / fb;
-        hipLaunchKernelGGL(noise_bwd_batched_kernel, dim3((unsigned)blocks), dim3(kNT), blds, s, p);
-        return (int)hipGetLastError();
-    }
-    const size_t lds = sizeof(float) * ((size_t)p.S + 2 * (size_t)hop + p.S / 2 + 1);
-    if (lds > 160 * 1024) return DDSP_ERANGE;
-    {
-        static bool attr_set[64] = {};
-        const hipError_t ae = ddsp_allow_big_lds((const void *)noise_bwd_frame_kernel, attr_set);
-        if (ae != hipSuccess) return (int)ae;
-    }
-    hipLaunchKernelGGL(noise_bwd_frame_kernel, dim3((unsigned)((long)B * T)), dim3(256), lds, s, p);
-    return (int)hipGetLastError();
+    const int fb = 64 >> pl.lpf_log;
+    if (pl.form == NoiseForm::Batched) return (int)launch_direct<noise_bwd_batched_kernel, kNT, false>(p, (frames + fb - 1) / fb, pl.lds_bytes, s);
+    return (int)launch_direct<noise_bwd_frame_kernel, 256, false>(p, frames, pl.lds_bytes, s);
 }

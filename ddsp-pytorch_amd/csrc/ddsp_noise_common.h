@@ -1,7 +1,14 @@
-// Shared by the filtered-noise kernels (ddsp_noise.hip: direct forms, ddsp_noise_fft.hip: in-LDS FFT form).
+// Shared by the four filtered-noise sources:
+//   ddsp_noise.hip       the two entry points (validate -> plan -> launch) and the direct kernels (batched, one frame per workgroup)
+//   ddsp_noise_fft.hip   in-LDS FFT form, forward and backward (hop 512; hop 256 on request)
+//   ddsp_noise_wave.hip  wavefront-private form (hop 128, 65 bands), forward
+//   ddsp_noise_ir.hip    impulse responses of the whole batch as one split-bf16 matrix product (195 bands at hop 512)
+// Which of them a call runs is decided by ddsp_noise_plan.h alone; the launch_* functions below launch what they are told.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ddsp_noise_plan.h"
 
 namespace ddsp_noise {
 
@@ -43,30 +50,38 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // exact and so is the subtraction (a multiple of 2^-23 in [-1, 1)): ONE fused multiply-add gives the very bits of (u * 2) - 1.
 __device__ __forceinline__ float philox_to_sample(uint32_t r) { return __fmaf_rn((float)(r >> 8), 1.0f / 8388608.0f, -1.0f); }
 
-// Launches the FFT form when the shape is one it is built for and faster at (hop 512, S <= hop; with force_fft also hop 256);
-// returns false (and launches nothing) otherwise.  *err receives the launch status.
-bool launch_noise_fft(const NoiseParams &p, hipStream_t s, bool force_fft, hipError_t *err);
+// Eight fp32 values as three bf16 terms each, hi + mid + lo == the value exactly: the operands of the split-bf16 matrix products
+// (ddsp_noise_wave.hip, ddsp_noise_ir.hip).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+struct Split { bf16x8 p[3]; };
+// x = hi + mid + lo with every term a bf16: both residuals are exact in fp32 (8 + 8 + 8 significand bits)
+__device__ __forceinline__ void split3(float x, Split &d, int j)
+{
+    const __bf16 hi = (__bf16)x;
+    const float r1 = x - (float)hi;
+    const __bf16 mid = (__bf16)r1;
+    const float r2 = r1 - (float)mid;
+    d.p[0][j] = hi; d.p[1][j] = mid; d.p[2][j] = (__bf16)r2;
+}
 
-// Backward of the noise path in the in-LDS FFT form (hop 512; 257 bands, or -- given a workspace of ir_workspace_bytes -- the
-// shapes of ir_product_shape, whose dH step is then one matrix product); returns false (and launches nothing) for other shapes.
-// *err receives the launch status.
-bool launch_noise_fft_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
-                               uint64_t offset, const uint64_t *offset_dev, void *workspace, hipStream_t s, hipError_t *err);
+// ---- the launchers: each launches the form the plan named and returns the launch status ------------------------------------------
+// FFT form, forward (hop 512, or hop 256; S <= hop; y and u 16-byte aligned); reads p.zrows instead of summing cosines when set.
+hipError_t launch_noise_fft(const NoiseParams &p, hipStream_t s);
 
-// Impulse responses as one split-bf16 matrix product for the whole batch (ddsp_noise_ir.hip): the shapes it is built for, the
-// workspace it needs (| cosine operand | z rows |), and the launch -> the z rows inside the workspace (nullptr: launch error in *err).
-bool ir_product_shape(int F, int hop);
-int ir_row_stride(int F);
-size_t ir_workspace_bytes(long frames, int F);
-const float *launch_noise_ir(const float *Hmag, long frames, int F, void *workspace, hipStream_t s, hipError_t *err);
-float *ir_rows(void *workspace, int F);
+// FFT form, backward (hop 512; grad_y and uniform 16-byte aligned).  workspace == nullptr: 257 bands, dH inside the kernel; else
+// (ir_workspace_bytes, the shapes of ir_product_shape) dz goes to the workspace and dH = dz C^T is one matrix product.
+hipError_t launch_noise_fft_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
+                                     uint64_t offset, const uint64_t *offset_dev, void *workspace, hipStream_t s);
+
+// Impulse responses as one split-bf16 matrix product for the whole batch (ddsp_noise_ir.hip), into the workspace
+// (| cosine operand | z rows |): the forward's pair of launches leaves the z rows at ir_rows(workspace, F).
+hipError_t launch_noise_ir(const float *Hmag, long frames, int F, void *workspace, hipStream_t s);
 hipError_t launch_ir_table(void *workspace, int F, int transpose, hipStream_t s);
 hipError_t launch_ir_product(const float *in, int in_stride, float *out, int out_stride, float *maxabs, long frames, int F, int transpose,
                              const void *workspace, hipStream_t s);
 
-// Launches the wavefront-private hop-128 / 65-band form (ddsp_noise_wave.hip) on the leading whole groups of 16 frames when the
-// shape is the one it is built for.  Returns the number of frames it took (0: not its shape, nothing launched; the caller runs
-// the remaining frames -- fewer than 16 -- through another kernel, with the Philox offset advanced), -1 on a launch error (*err).
-long launch_noise_wave(const NoiseParams &p, hipStream_t s, hipError_t *err);
+// Wavefront-private hop-128 / 65-band form on the first `frames` frames of p, a multiple of kWaveGroupFrames (y, Hm and u 16-byte
+// aligned); the entry point runs a remainder through another kernel, with the Philox offset advanced.
+hipError_t launch_noise_wave(const NoiseParams &p, long frames, hipStream_t s);
 
 }  // namespace ddsp_noise

@@ -613,16 +613,9 @@ hipError_t launch(const NoiseParams &p, hipStream_t s)
     const long nframes = (long)p.B * p.T;
     const long npairs = (nframes + 1) / 2;
     const size_t lds = sizeof(float2) * 2 * buf_elems<R1>() + (IRFFT ? 0 : sizeof(float) * (size_t)p.S);
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
+    int cus = 0;
+    const hipError_t e = ddsp_device_cus(&cus);
     if (e != hipSuccess) return e;
-    static int cached[64] = {};
-    if (!cached[dev & 63]) {
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        cached[dev & 63] = cus;
-    }
-    cus = cached[dev & 63];
     // wavefronts a CU holds of this kernel: registers allow 2 (R1 = 16: 160-224 VGPRs) or 4 (R1 = 8: <= 120) per SIMD, LDS 160 KiB / lds
     const long by_regs = R1 == 16 ? 8 : 16, by_lds = (160 * 1024) / (long)lds;
     long per_cu = by_lds < by_regs ? by_lds : by_regs;
@@ -643,64 +636,41 @@ hipError_t launch(const NoiseParams &p, hipStream_t s)
 
 namespace ddsp_noise {
 
-bool launch_noise_fft(const NoiseParams &p, hipStream_t s, bool force_fft, hipError_t *err)
+hipError_t launch_noise_fft(const NoiseParams &p, hipStream_t s)
 {
-    const int R = p.R, S = p.S;
-    if (S > R || (S & 1) || S < 4) return false;                 // hop < 2(F-1) crops the impulse response: direct kernels
-    if (((uintptr_t)p.y % 16) != 0 || (p.u && ((uintptr_t)p.u % 16) != 0)) return false;
-    if (R == 512) {
-        *err = (S == 512) ? launch<16, true>(p, s) : launch<16, false>(p, s);
-        return true;
-    }
-    // hop 256 (N = 512: launch<8, false>) works and is tested through this entry, but measures no faster than the direct
-    // batched kernel there (0.31-0.36 ms against 0.27-0.29 ms at batch 512 x 250 frames, F = 129): the direct form's 128
-    // multiply-adds per sample are already cheaper than three 512-point transforms.  Kept for the tests only (force_fft).
-    if (R == 256 && force_fft) {
-        *err = launch<8, false>(p, s);
-        return true;
-    }
-    return false;
+    if (p.R == 512) return (p.S == 512) ? launch<16, true>(p, s) : launch<16, false>(p, s);
+    // hop 256 (N = 512) works and is tested through this entry, but measures no faster than the direct batched kernel there
+    // (0.31-0.36 ms against 0.27-0.29 ms at batch 512 x 250 frames, F = 129): the direct form's 128 multiply-adds per sample are
+    // already cheaper than three 512-point transforms.  Planned only on request (ddsp_noise_plan.h: kModeFftAtHop256).
+    return launch<8, false>(p, s);
 }
 
-bool launch_noise_fft_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
-                               uint64_t offset, const uint64_t *offset_dev, void *workspace, hipStream_t s, hipError_t *err)
+hipError_t launch_noise_fft_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
+                                     uint64_t offset, const uint64_t *offset_dev, void *workspace, hipStream_t s)
 {
-    const int S = 2 * (F - 1);
-    const bool zout = workspace && ir_product_shape(F, hop);         // 195 bands: dz to the workspace, dH = dz C^T as one product
-    if (hop != 512 || (S != hop && !zout)) return false;             // other shapes: the direct kernels (see above)
-    if (((uintptr_t)grad_y % 16) != 0 || (uniform && ((uintptr_t)uniform % 16) != 0)) return false;
     NoiseFftBwdParams q;
-    q.g = grad_y; q.u = uniform; q.gH = grad_H; q.B = B; q.T = T; q.F = F; q.S = S;
+    q.g = grad_y; q.u = uniform; q.gH = grad_H; q.B = B; q.T = T; q.F = F; q.S = 2 * (F - 1);
     q.dz = nullptr; q.zs = 0;
     q.seed = seed; q.offset = offset; q.offset_dev = offset_dev;
     const long nframes = (long)B * T, npairs = (nframes + 1) / 2;
     const size_t lds = sizeof(float2) * 2 * buf_elems<16>();
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) { *err = e; return true; }
-    static int cached[64] = {};
-    if (!cached[dev & 63]) {
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) { *err = e; return true; }
-        cached[dev & 63] = cus;
-    }
-    cus = cached[dev & 63];
+    int cus = 0;
+    hipError_t e = ddsp_device_cus(&cus);
+    if (e != hipSuccess) return e;
     const long resident = (long)cus * 8;                             // 17 KB of LDS each: eight wavefronts per CU
     const long grid = npairs < resident ? npairs : resident;
-    if (zout) {
+    if (workspace) {                                                 // 195 bands: dz to the workspace, dH = dz C^T as one product
         q.dz = ir_rows(workspace, F);
         q.zs = ir_row_stride(F);
-        *err = launch_ir_table(workspace, F, 1, s);
-        if (*err != hipSuccess) return true;
+        e = launch_ir_table(workspace, F, 1, s);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(noise_fft_bwd_kernel<true>, dim3((unsigned)grid), dim3(64), lds, s, q, npairs);
-        *err = hipGetLastError();
-        if (*err != hipSuccess) return true;
-        *err = launch_ir_product(q.dz, q.zs, grad_H, F, nullptr, nframes, F, 1, workspace, s);
-        return true;
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        return launch_ir_product(q.dz, q.zs, grad_H, F, nullptr, nframes, F, 1, workspace, s);
     }
-    hipLaunchKernelGGL(noise_fft_bwd_kernel<false>, dim3((unsigned)grid), dim3(64), lds, s, q, npairs);
-    *err = hipGetLastError();
-    return true;
+    hipLaunchKernelGGL(noise_fft_bwd_kernel<false>, dim3((unsigned)grid), dim3(64), lds, s, q, npairs);   // 257 bands: dH inside the kernel
+    return hipGetLastError();
 }
 
 }  // namespace ddsp_noise

@@ -33,21 +33,8 @@ namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));      // a 16-byte load from a 4-byte-aligned address
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-struct Split { bf16x8 p[3]; };
-// x = hi + mid + lo with every term a bf16: both residuals are exact in fp32 (8 + 8 + 8 significand bits)
-__device__ __forceinline__ void split3(float x, Split &d, int j)
-{
-    const __bf16 hi = (__bf16)x;
-    const float r1 = x - (float)hi;
-    const __bf16 mid = (__bf16)r1;
-    const float r2 = r1 - (float)mid;
-    d.p[0][j] = hi; d.p[1][j] = mid; d.p[2][j] = (__bf16)r2;
-}
-
-constexpr int KT = 4;             // contraction steps of 32 per parity: S/4 + 1 <= 128
-constexpr int NT = 7;             // output tiles of 16 per parity:      S/4 + 1 in (96, 112]  <=>  F in [194, 225]
-constexpr int FR = 2 * KT * 3;    // fragments of one output tile: (parity, step, term)
+constexpr int KT = kIrKT, NT = kIrNT, FR = kIrFR;    // (ddsp_noise_plan.h: the workspace's size follows from them)
+static_assert(sizeof(bf16x8) * 64 == kIrFragmentBytes, "a fragment is one 16-byte word per lane");
 
 // Fragment (nt, parity, kt, term) of the cosine operand, B[i = 32 kt + 8 (lane >> 4) + j][o = 16 nt + (lane & 15)], j = 0..7 in one
 // 16-byte word per lane; i = contraction index, o = output index.  Forward (transpose == 0): i = k' (bin 2 k' + parity), o = tap n;
@@ -223,37 +210,9 @@ __global__ void __launch_bounds__(256, 2) noise_ir_kernel(IrParams p)
     }
 }
 
-int device_cus(hipError_t *err)
-{
-    int dev = 0, cus = 0;
-    *err = hipGetDevice(&dev);
-    if (*err != hipSuccess) return 0;
-    static int cached[64] = {};
-    if (!cached[dev & 63]) {
-        *err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (*err != hipSuccess) return 0;
-        cached[dev & 63] = cus;
-    }
-    return cached[dev & 63];
-}
-
 }  // namespace
 
 namespace ddsp_noise {
-
-bool ir_product_shape(int F, int hop)
-{
-    const int S = 2 * (F - 1), NQ = (F - 1) / 2 + 1;
-    return hop == 512 && S < hop && NQ > 16 * (NT - 1) && NQ <= 16 * NT;
-}
-
-int ir_row_stride(int F) { return 16 * ((F + 15) / 16) + 4; }           // z row: >= F columns + a 16-byte tail (max |H| in its first float)
-
-size_t ir_table_bytes(int) { return (size_t)NT * FR * 64 * sizeof(bf16x8); }
-
-size_t ir_workspace_bytes(long frames, int F) { return ir_table_bytes(F) + (size_t)frames * ir_row_stride(F) * sizeof(float); }
-
-float *ir_rows(void *workspace, int F) { return reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + ir_table_bytes(F)); }
 
 // The cosine operand into the head of the workspace (transpose: the backward's, bins on the output side).
 hipError_t launch_ir_table(void *workspace, int F, int transpose, hipStream_t s)
@@ -267,8 +226,8 @@ hipError_t launch_ir_table(void *workspace, int F, int transpose, hipStream_t s)
 hipError_t launch_ir_product(const float *in, int in_stride, float *out, int out_stride, float *maxabs, long frames, int F, int transpose,
                              const void *workspace, hipStream_t s)
 {
-    hipError_t err = hipSuccess;
-    const int cus = device_cus(&err);
+    int cus = 0;
+    const hipError_t err = ddsp_device_cus(&cus);
     if (err != hipSuccess) return err;
     IrParams p;
     p.in = in; p.table = reinterpret_cast<const bf16x8 *>(workspace); p.out = out; p.maxabs = maxabs; p.frames = frames;
@@ -285,16 +244,16 @@ hipError_t launch_ir_product(const float *in, int in_stride, float *out, int out
 }
 
 // Forward: z rows (x S) of every frame into the workspace, | table | z [frames][ir_row_stride] |, max |H| of a frame in column
-// ir_row_stride - 4 of its row.  Returns the z rows (nullptr on a launch error).
-const float *launch_noise_ir(const float *Hmag, long frames, int F, void *workspace, hipStream_t s, hipError_t *err)
+// ir_row_stride - 4 of its row.
+hipError_t launch_noise_ir(const float *Hmag, long frames, int F, void *workspace, hipStream_t s)
 {
     const int zs = ir_row_stride(F);
     float *z = ir_rows(workspace, F);
     const int slot = ddsp_prof::begin(ddsp_prof::NOISE_IR, s);
-    *err = launch_ir_table(workspace, F, 0, s);
-    if (*err == hipSuccess) *err = launch_ir_product(Hmag, F, z, zs, z + zs - 4, frames, F, 0, workspace, s);
+    hipError_t err = launch_ir_table(workspace, F, 0, s);
+    if (err == hipSuccess) err = launch_ir_product(Hmag, F, z, zs, z + zs - 4, frames, F, 0, workspace, s);
     ddsp_prof::end(slot, s);
-    return *err == hipSuccess ? z : nullptr;
+    return err;
 }
 
 }  // namespace ddsp_noise

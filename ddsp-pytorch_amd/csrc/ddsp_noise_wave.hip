@@ -30,7 +30,7 @@
 //     every lane (uniform trip count); the switch between a pass's two chunks is the only divergent instruction group.
 //   * output: the group's 16 x 128 results are contiguous in y; staged through LDS (over the noise tile) and stored as whole lines.
 //
-// Only whole groups: launch_noise_wave() hands a remainder of fewer than 16 frames to the batched kernel (same Philox counters).
+// Only whole groups: the entry point hands a remainder of fewer than 16 frames to the batched kernel (same Philox counters).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,21 +53,12 @@ struct Tile { v4f v[5]; };           // a group's 16 x 65 filter magnitudes, 260
 struct Lines { v4f v[8]; };          // a group's 16 x 128 outputs, 512 x 16 bytes over 64 lanes
 struct Pass { float v[16]; };        // a lane's two output chunks of one convolution pass
 struct Spectra { v4f e[2], o[2], h64; float z32; };
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-struct Split { bf16x8 p[3]; };       // eight fp32 values as three bf16 terms each, hi + mid + lo == the value exactly
-// x = hi + mid + lo with every term a bf16: both residuals are exact in fp32 (8 + 8 + 8 significand bits)
-__device__ __forceinline__ void split3(float x, Split &d, int j)
-{
-    const __bf16 hi = (__bf16)x;
-    const float r1 = x - (float)hi;
-    const __bf16 mid = (__bf16)r1;
-    const float r2 = r1 - (float)mid;
-    d.p[0][j] = hi; d.p[1][j] = mid; d.p[2][j] = (__bf16)r2;
-}
 
-constexpr int R = 128;            // hop = samples per frame
-constexpr int F = 65;             // bands; S = 2 (F - 1) = 128 = R: the impulse response fills the frame exactly
-constexpr int FG = 16;            // frames per group
+// the one shape this form is built for (ddsp_noise_plan.h plans it for no other)
+constexpr int R = kWaveHop;          // hop = samples per frame
+constexpr int F = kWaveBands;        // bands; S = 2 (F - 1) = 128 = R: the impulse response fills the frame exactly
+constexpr int FG = kWaveGroupFrames; // frames per group
+static_assert(R == 128 && F == 65 && FG == 16 && 2 * (F - 1) == R, "the kernel's register and LDS layouts are written for these");
 constexpr int KS = 132;           // kern / staging row stride (4 x 33)
 constexpr int XS = 140;           // noise row stride: 8 leading zeros + 128 samples + 4 (4 x 35)
 constexpr int kLdsFloats = FG * KS + FG * XS;
@@ -392,11 +383,9 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
 #endif
 }
 
-}  // namespace
-
-namespace {
 constexpr int kDefaultWavesPerCu = 4;
 std::atomic<int> g_residency{0};      // ddsp_noise_set_residency: wavefronts per CU of noise_wave_kernel (0: the default)
+
 }  // namespace
 
 // Production tuning knob (not a test hook): wavefronts per CU, 1..8, of the hop-128 noise kernel's persistent grid; 0 restores the
@@ -415,23 +404,12 @@ extern "C" int ddsp_noise_get_residency(void)
 
 namespace ddsp_noise {
 
-long launch_noise_wave(const NoiseParams &p, hipStream_t s, hipError_t *err)
+hipError_t launch_noise_wave(const NoiseParams &p, long frames, hipStream_t s)
 {
-    if (p.R != R || p.F != F || p.S != R) return 0;
-    if (((uintptr_t)p.y % 16) != 0 || ((uintptr_t)p.Hm % 16) != 0 || (p.u && ((uintptr_t)p.u % 16) != 0)) return 0;
-    const long nframes = (long)p.B * p.T;
-    const long ngroups = nframes / FG;                            // whole groups only
-    if (ngroups == 0) return 0;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) { *err = e; return -1; }
-    static int cached[64] = {};
-    if (!cached[dev & 63]) {
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) { *err = e; return -1; }
-        cached[dev & 63] = cus;
-    }
-    cus = cached[dev & 63];
+    const long ngroups = frames / FG;
+    int cus = 0;
+    const hipError_t e = ddsp_device_cus(&cus);
+    if (e != hipSuccess) return e;
     constexpr size_t lds = sizeof(float) * kLdsFloats;
     // FOUR wavefronts per CU by default (17.4 KB of LDS each), not the eight that fit two per SIMD: at eight, this kernel's FMA + LDS +
     // HBM activity makes the chip's power management drop the shader clock (2.41 -> ~2.1 GHz; it takes ~25 ms of load to come back), so
@@ -451,8 +429,7 @@ long launch_noise_wave(const NoiseParams &p, hipStream_t s, hipError_t *err)
     if (p.accumulate) hipLaunchKernelGGL(noise_wave_kernel<true>, dim3((unsigned)grid), dim3(64), lds, s, p, ngroups);
     else hipLaunchKernelGGL(noise_wave_kernel<false>, dim3((unsigned)grid), dim3(64), lds, s, p, ngroups);
     ddsp_prof::end(slot, s);
-    *err = hipGetLastError();
-    return *err == hipSuccess ? ngroups * FG : -1;
+    return hipGetLastError();
 }
 
 }  // namespace ddsp_noise

@@ -848,7 +848,7 @@ hipError_t synth_residency(Residency *out)
     std::lock_guard<std::mutex> lk(mu);
     if (cache[dev].cus == 0) {
         int cus = 0, nb = 0;
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        e = ddsp_device_cus(&cus);
         if (e != hipSuccess) return e;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, osc_chunk_synth_kernel<K, KR, false>, 256, sizeof(float) * 32 * kRow);
         if (e != hipSuccess) return e;

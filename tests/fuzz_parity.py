@@ -330,7 +330,7 @@ NOISE_BWD_FRAME_FLOOR = 1e-3
 
 
 def noise_bwd_lpf_log(F, hop):
-    """pick_bwd_lpf_log (csrc/ddsp_noise.hip): log2 lanes per frame of the batched backward, -1 when no tile fits in LDS."""
+    """pick_bwd_lpf_log (csrc/ddsp_noise_plan.h): log2 lanes per frame of the batched backward, -1 when no tile fits in LDS."""
     S = 2 * (F - 1)
     for limit in (48 * 1024, 80 * 1024, 160 * 1024):
         for l in range(4):
@@ -342,7 +342,8 @@ def noise_bwd_lpf_log(F, hop):
 
 def noise_bwd_form(B, T, F, hop, mode=0, aligned=True):
     """The kernel form ddsp_noise_backward_ws takes: 'A' (in-LDS FFT correlation), 'B' (FFT correlation + split-bf16 product),
-    'C0'..'C3' (batched direct kernel, log2 lanes per frame), 'D' (one frame per workgroup) -- by the dispatch's own conditions."""
+    'C0'..'C3' (batched direct kernel, log2 lanes per frame), 'D' (one frame per workgroup) -- by the conditions of plan_noise_backward
+    (csrc/ddsp_noise_plan.h); tests/test_noise_plan_host.py holds the two against each other."""
     if not mode & 3 and hop == 512 and aligned:
         if not mode & 16 and ddsp._lib.lib().ddsp_noise_workspace_bytes(B, T, F, hop) > 0:
             return "B"

@@ -10,6 +10,7 @@ import torch
 
 import ddsp_pytorch_amd as ddsp
 from ddsp_pytorch_amd import synthetic as syn
+import fuzz_parity as fz
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +110,31 @@ def test_workspace_contract_abi5():
     assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y1.data_ptr(), 2, 2100, 195, 512, 11, 0, None, 0, ws.data_ptr(),
                                    ctypes.c_size_t(need), s) == 0
     assert float((y0 - y1).abs().max()) <= TOL * max(1.0, float(y0.abs().max()))
+
+
+def test_misaligned_output_with_a_full_workspace_is_the_frame_kernel():
+    """y 4 bytes off a 16-byte boundary at the default shape, >= 4 096 frames, full workspace: neither the FFT form nor the batched
+    kernel can store it, so the one-frame-per-workgroup kernel runs (and no product before it): the bits of the same call under
+    mode 1 into an aligned buffer."""
+    L = ddsp._lib.lib()
+    B, T, nf = 2, 2100, 195
+    rng = np.random.default_rng(12)
+    Hn = dev(syn.controller_range(rng.standard_normal((B, T, nf), dtype=np.float32)))
+    need = L.ddsp_noise_workspace_bytes(B, T, nf, 512)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    y_off = fz.misaligned(np.zeros((B, T * 512), np.float32))
+    assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y_off.data_ptr(), B, T, nf, 512, 11, 5, None, 0, ws.data_ptr(),
+                                   ctypes.c_size_t(need), s) == 0
+    y_ref = torch.empty(B, T * 512, device="cuda")
+    assert L.ddsp_noise_set_generic(1) == 0
+    try:
+        assert L.ddsp_noise_forward_ws(Hn.data_ptr(), None, y_ref.data_ptr(), B, T, nf, 512, 11, 5, None, 0, ws.data_ptr(),
+                                       ctypes.c_size_t(need), s) == 0
+    finally:
+        L.ddsp_noise_set_generic(0)
+    assert torch.equal(y_off, y_ref)
 
 
 def test_matrix_product_form_in_a_captured_graph():
