@@ -6,7 +6,12 @@
 //   * n_fft = 64 ... 1024: frames 2q and 2q + 1 of one row are packed as one complex sequence a + i b (a row's last frame of an
 //     odd count is paired with zeros); a wavefront takes 512 / n_fft pairs at a time (one for 1024).  Bin k of each frame comes
 //     out of the Hermitian split A = (Z_k + conj Z_{n-k}) / 2, B = -i (Z_k - conj Z_{n-k}) / 2.  Pairing inside a row keeps every
-//     row's result independent of the rest of the batch.
+//     row's result independent of the rest of the batch.  The two frames of a pair are equalised by powers of two
+//     (ddsp_wave_fft.h: frame_scale): each is scaled by 2^-e, e the exponent of its largest |sample|, on load and by 2^e on the
+//     split's outputs -- both exact, so |X| and everything after it round as they do for a frame transformed alone, and a quiet
+//     frame (an onset after silence, a zero margin) does not carry its partner's rounding noise into its logarithms.  An
+//     all-zero frame comes out as exact zeros (log10(1e-20) in every bin, the reference's value).  A frame with a NaN or an
+//     infinite sample is NaN, as torch.stft makes it, and enters the transform as zeros: its partner is computed alone.
 //   * n_fft = 2048: one real frame per wavefront through a 1024-point complex transform of z[m] = x[2m] + i x[2m+1] and the
 //     real-split step (the one-frame form of ddsp_mss_fft.hip).
 // The mean over bins is a per-lane sum in bin order and a fixed butterfly across the wavefront: deterministic.
@@ -39,6 +44,9 @@ __device__ __forceinline__ float bin_term(float re, float im, double aw)
     return db / 90.0f + 1.0f;
 }
 
+// |x| for the frame's maximum; a NaN counts as infinite, so that fmaxf keeps it
+__device__ __forceinline__ float abs_or_inf(float x) { return x != x ? __builtin_huge_valf() : fabsf(x); }
+
 template <int N>
 __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nunits)
 {
@@ -54,6 +62,8 @@ __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nu
     for (long unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
         long frame[BT];
         int nvalid[BT];
+        float outa[BT], outb[BT];                         // 2^e / 2 of the slot's two frames (0: an all-zero frame)
+        bool deada[BT], deadb[BT];                        // a frame with a sample that is not finite
         cf v[PL];
 #pragma unroll
         for (int b = 0; b < BT; ++b) {                    // wave-uniform slot bookkeeping
@@ -67,12 +77,27 @@ __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nu
                 nvalid[b] = (fa + 1 < p.F) ? 2 : 1;
                 start = row * p.L + fa * p.hop;
             }
+            float ma = 0.0f, mb = 0.0f;
 #pragma unroll
             for (int n1 = 0; n1 < R1; ++n1) {
                 const float *r = p.x + start + 64 * n1 + lane;
                 const float re = nvalid[b] > 0 ? r[0] : 0.0f;
                 const float im = nvalid[b] > 1 ? r[p.hop] : 0.0f;
                 v[b * R1 + n1] = make_float2(re, im);
+                ma = fmaxf(ma, abs_or_inf(re));
+                mb = fmaxf(mb, abs_or_inf(im));
+            }
+            ma = ddsp_wfft::wave_max(ma);
+            mb = ddsp_wfft::wave_max(mb);
+            const ddsp_wfft::FrameScale sa = ddsp_wfft::frame_scale_of(ma, 1.0f, 0.5f), sb = ddsp_wfft::frame_scale_of(mb, 1.0f, 0.5f);
+            deada[b] = !(ma < __builtin_huge_valf());
+            deadb[b] = !(mb < __builtin_huge_valf());
+            outa[b] = sa.out;
+            outb[b] = sb.out;
+#pragma unroll
+            for (int n1 = 0; n1 < R1; ++n1) {
+                const cf z = v[b * R1 + n1];
+                v[b * R1 + n1] = make_float2(deada[b] ? 0.0f : z.x * sa.in, deadb[b] ? 0.0f : z.y * sb.in);
             }
         }
         fft.template run<false>(v, buf);
@@ -86,14 +111,14 @@ __global__ void __launch_bounds__(64) loudness_pair_kernel(LoudParams p, long nu
             for (int k = lane; k < BINS; k += 64) {
                 const cf zk = zrow[k], zm = zrow[(N - k) & (N - 1)];
                 const double aw = p.aw[k];
-                sa += bin_term(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y), aw);
-                sb += bin_term(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x), aw);
+                sa += bin_term((zk.x + zm.x) * outa[b], (zk.y - zm.y) * outa[b], aw);     // the split's 1/2 is in outa, outb
+                sb += bin_term((zk.y + zm.y) * outb[b], (zm.x - zk.x) * outb[b], aw);
             }
             sa = wave_sum(sa);
             sb = wave_sum(sb);
             if (lane == 0 && nvalid[b] > 0) {
-                p.out[frame[b]] = sa / (float)BINS;
-                if (nvalid[b] > 1) p.out[frame[b] + 1] = sb / (float)BINS;
+                p.out[frame[b]] = deada[b] ? __builtin_nanf("") : sa / (float)BINS;
+                if (nvalid[b] > 1) p.out[frame[b] + 1] = deadb[b] ? __builtin_nanf("") : sb / (float)BINS;
             }
         }
         DDSP_WAVE_ORDER();

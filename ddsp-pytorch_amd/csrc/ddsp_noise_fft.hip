@@ -35,25 +35,8 @@ namespace {
 
 using namespace ddsp_wfft;
 
-// Power-of-two equaliser of a frame.  Two frames share every transform of this file (one in the real part, one in the imaginary part), so
-// each carries an fp32-epsilon share of the other: harmless when they are equally loud, a relative error of eps * ratio in the quiet
-// one when they are not (the reference transforms every frame alone).  Everything here is linear in the frame's magnitudes / gradient
-// row, so the frame is scaled by 2^-e on the way in and by 2^e on the way out -- exact -- with e the exponent of its largest
-// magnitude: both halves of a pair then sit in [0.5, 1).  An all-zero frame comes out as exact zeros (as the reference's does),
-// not as its partner's rounding residue.  `m`: the lane's own max |value|; `c_in`, `c_out`: the constants the two scalings fold into.
-struct FrameScale { float in, out; };
-__device__ __forceinline__ FrameScale frame_scale(float m, float c_in, float c_out)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d));
-    int e = 0;
-    if (m > 0.0f && m < __builtin_huge_valf()) (void)frexpf(m, &e);
-    e = max(-100, min(100, e));                         // 2^-e and 2^e stay normal numbers whatever the input holds
-    FrameScale s;
-    s.in = ldexpf(c_in, -e);
-    s.out = (m == 0.0f) ? 0.0f : ldexpf(c_out, e);
-    return s;
-}
+// Two frames share every transform of this file (one in the real part, one in the imaginary part) and everything here is linear in
+// a frame's magnitudes / gradient row: the pair is equalised by powers of two (ddsp_wave_fft.h: frame_scale).
 
 struct FrameSrc {
     long frame;   // index into [B*T]

@@ -277,6 +277,38 @@ __device__ __forceinline__ void fft_wave_batched(cf (&v)[8], const cf *t1, const
 }
 
 
+// ---- two real frames in one complex transform: the power-of-two equaliser ---------------------------------------------------
+// A transform of a + i b (the filtered noise's, the loudness's) leaves in each frame an fp32-epsilon share of the other: harmless
+// when they are equally loud, a relative error of eps * ratio in the quiet one when they are not (the reference transforms every
+// frame alone).  Where everything between the load and the split is linear in the frame, the frame is scaled by 2^-e on the way
+// in and by 2^e on the way out -- exact -- with e the exponent of its largest magnitude: both halves of a pair then sit in
+// [0.5, 1).  An all-zero frame comes out as exact zeros (as the reference's does), not as its partner's rounding residue.
+// `c_in`, `c_out`: the constants the two scalings fold into.
+struct FrameScale { float in, out; };
+
+// max over the 64 lanes, every lane gets it (fmaxf: a NaN lane is dropped, an infinite one wins)
+__device__ __forceinline__ float wave_max(float m)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) m = fmaxf(m, __shfl_xor(m, d));
+    return m;
+}
+
+// `m`: the frame's max |value| (wave_max).  Zero, infinite: e = 0.
+__device__ __forceinline__ FrameScale frame_scale_of(float m, float c_in, float c_out)
+{
+    int e = 0;
+    if (m > 0.0f && m < __builtin_huge_valf()) (void)frexpf(m, &e);
+    e = max(-100, min(100, e));                         // 2^-e and 2^e stay normal numbers whatever the input holds
+    FrameScale s;
+    s.in = ldexpf(c_in, -e);
+    s.out = (m == 0.0f) ? 0.0f : ldexpf(c_out, e);
+    return s;
+}
+
+// `m`: the lane's own max |value|
+__device__ __forceinline__ FrameScale frame_scale(float m, float c_in, float c_out) { return frame_scale_of(wave_max(m), c_in, c_out); }
+
 // ---- real signals: n_fft a power of two in 64 .. 2048 -----------------------------------------------------------------------
 constexpr bool real_size_supported(int n_fft) { return n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0; }
 

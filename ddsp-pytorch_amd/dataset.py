@@ -158,7 +158,6 @@ class DeviceAudio:
         duration, step = example_geometry(conf)
         resamplers, parts, table, start, n = {}, [], [], 0, 0
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
             for path in paths:
                 pcm, sr = load_audio(path)
                 length = resampled_length(pcm.shape[0], sr, conf.sample_rate)
@@ -170,11 +169,7 @@ class DeviceAudio:
                     if sr not in resamplers:
                         resamplers[sr] = Resample(sr, conf.sample_rate).to(device)
                     rs = resamplers[sr]
-                    mono = pcm_to_mono(x)
-                    y = torch.empty(length, device=device, dtype=torch.float32)
-                    rc = _lib.lib().ddsp_resample(mono.data_ptr(), rs.table.data_ptr(), rs.first.data_ptr(), y.data_ptr(), 1,
-                                                  mono.numel(), rs.orig, rs.new, rs.ntaps, stream)
-                    _lib.check(rc, "ddsp_resample")
+                    y = rs(pcm_to_mono(x).reshape(1, -1))[0].contiguous()      # ddsp_resample, or the stock ops where its table does not fit
                 parts.append(y)
                 table.append((start, length, hop_pad(length, conf.hop_length)[0], n))
                 start += length

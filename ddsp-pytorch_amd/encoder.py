@@ -111,27 +111,35 @@ def resampled_length(L: int, orig: int, new: int) -> int:
     return int(math.ceil(n * L / o)) if o != n else L
 
 
+RESAMPLE_TABLE_MAX = 16384               # floats of LDS that resample_kernel keeps its taps in (csrc/ddsp_encoder.hip: kMaxTable;
+                                         # tests/test_encoder_reference_host.py holds the two together)
+
+
 class Resample(nn.Module):
     """orig -> new Hz (torchaudio.transforms.Resample semantics; equal rates are the identity).  The kernel is not part of the
-    state dict (torchaudio keeps it out as well)."""
+    state dict (torchaudio keeps it out as well).  On the device one HIP launch (ddsp_resample) where the rate pair's table of
+    new' x ntaps support taps fits the kernel's LDS (`fits_kernel`; every pair of common audio rates does); a pair that does not
+    (44056 -> 16000 reduces to 5507 : 2000, 2000 x 34 taps) runs the stock pad + conv1d formulation on the device."""
 
     def __init__(self, orig: int, new: int):
         super().__init__()
         self.orig_freq, self.new_freq = int(orig), int(new)
         self.identity = self.orig_freq == self.new_freq
+        self.fits_kernel = True
         if not self.identity:
             kernel, self.width, self.orig, self.new = sinc_resample_kernel(orig, new)
             table, first, self.ntaps = support_taps(orig, new)
             self.register_buffer("kernel", kernel, persistent=False)
             self.register_buffer("table", table, persistent=False)
             self.register_buffer("first", first, persistent=False)
+            self.fits_kernel = self.new * self.ntaps <= RESAMPLE_TABLE_MAX
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.identity:
             return x
         B, L = x.shape
         target = resampled_length(L, self.orig_freq, self.new_freq)
-        if x.is_cuda:
+        if x.is_cuda and self.fits_kernel:
             x = x.contiguous().float()
             y = torch.empty((B, target), device=x.device, dtype=torch.float32)
             with torch.cuda.device(x.device):
@@ -139,7 +147,7 @@ class Resample(nn.Module):
                                               self.orig, self.new, self.ntaps, torch.cuda.current_stream().cuda_stream)
             _lib.check(rc, "ddsp_resample")
             return y
-        xp = F.pad(x, (self.width, self.width + self.orig))
+        xp = F.pad(x.float() if x.is_cuda else x, (self.width, self.width + self.orig))
         y = F.conv1d(xp[:, None], self.kernel, stride=self.orig)
         return y.transpose(1, 2).reshape(B, -1)[..., :target]
 

@@ -464,7 +464,9 @@ int ddsp_yin_salience(const float *y, const float *bin_table, float *probs, long
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
  * float64 (the reference's parameter dtype; each bin's fp32 level plus its weight is rounded to fp32 once, as torch's `+=` does).
  * One kernel, transforms in LDS; n_fft a power of two in [64, 2048] (ddsp_loudness_supported) and L >= n_fft, DDSP_ERANGE
- * otherwise.
+ * otherwise.  Every frame is within 2e-6 of the fp64 value whatever the level of its neighbours (frames that share a packed
+ * transform are equalised by powers of two); an all-zero frame gives the value of log10(1e-20) in every bin; a frame with a
+ * NaN or an infinite sample is NaN and no other frame is.
  */
 int ddsp_loudness_supported(int n_fft);
 int ddsp_loudness(const float *x, const double *a_weight, float *out, long B, long L, int n_fft, int hop, void *stream);

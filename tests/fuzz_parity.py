@@ -6,11 +6,12 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru]   (`training`: the loss-side kernels against
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder]   (`training`: the loss-side kernels against
 fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
 backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
 fp64 reference of tests/noise_grad_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
-reference of tests/gru_reference.py)"""
+reference of tests/gru_reference.py; `encoder`: the encoder's loudness and resampler kernels against the fp64 references of
+tests/encoder_reference.py)"""
 import os
 import sys
 
@@ -27,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import osc_grad_reference as R  # noqa: E402
 import noise_grad_reference as R_noise  # noqa: E402
 import gru_reference as R_gru  # noqa: E402
+import encoder_reference as R_enc  # noqa: E402
 
 
 def bits(a):
@@ -693,6 +695,31 @@ def sweep_training_kernels(cases: int, seed: int, verbose: bool = True):
     return bad
 
 
+def sweep_encoder_stages(cases: int, seed: int, verbose: bool = True):
+    """Random cases of the encoder's loudness and resampler kernels (R_enc.sweep_cases: random n_fft / hop / frame count with every
+    hop-long segment at its own level over six decades, random rate pair and length) against the fp64 references of
+    tests/encoder_reference.py, at the tests' tolerances: loudness 2e-6, resampled audio 1e-6.  -> (failed, {stage: worst error})"""
+    worst = {"loudness": 0.0, "resample": 0.0}
+    bad = 0
+    for i, c in enumerate(R_enc.sweep_cases(cases, seed)):
+        x = torch.from_numpy(c["x"]).cuda()
+        if c["kind"] == "loudness":
+            got = R_enc.loudness_encoder(c["n_fft"], c["hop"]).cuda()(x).cpu().numpy()[..., 0]
+            ref = R_enc.loudness_ref(c["x"], c["n_fft"], c["hop"], R_enc.a_weight_of(c["n_fft"]))
+            tol, what = R_enc.LOUDNESS_TOL, f"n_fft {c['n_fft']} hop {c['hop']} [{x.shape[0]}, {ref.shape[1]}] frames"
+        else:
+            got = ddsp.encoder.Resample(c["orig"], c["new"]).cuda()(x).cpu().numpy()
+            ref = R_enc.resample_ref(c["x"], c["orig"], c["new"])
+            tol, what = R_enc.RESAMPLE_TOL, f"{c['orig']} -> {c['new']} [{x.shape[0]}, {x.shape[1]}]"
+        err = float(np.abs(got - ref).max()) if got.shape == ref.shape else float("inf")
+        okay = err <= tol                                        # a NaN fails
+        bad += not okay
+        worst[c["kind"]] = max(worst[c["kind"]], err) if okay or err == err else float("nan")
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} case {i}: {c['kind']} {what}: {err:.2e}", flush=True)
+    return bad, worst
+
+
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2026
@@ -716,6 +743,11 @@ def main():
         print(f"GRU recurrence: cases {cases}, seed {seed}, failed {bad}; worst error / e32 per family: "
               + ", ".join(f"{k} {v:.2f}" for k, v in sorted(worst.items())) + "; instantiations reached: "
               + ", ".join(f"{k} x{v}" for k, v in sorted(counts.items())))
+        sys.exit(1 if bad else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "encoder":
+        bad, worst = sweep_encoder_stages(cases, seed, verbose=False)
+        print(f"encoder stages: cases {cases}, seed {seed}, failed {bad}; worst error: "
+              + ", ".join(f"{k} {v:.2e}" for k, v in sorted(worst.items())))
         sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "training":
         bad = sweep_training_kernels(cases, seed, verbose=False)

@@ -1,7 +1,7 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
 oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
-plus the chunked oscillator form, the loss-side kernels, the backward of the oscillator and of the filtered noise, and the GRU
-recurrence step by step against fp64."""
+plus the chunked oscillator form, the loss-side kernels, the backward of the oscillator and of the filtered noise, the GRU
+recurrence step by step against fp64, and the encoder's loudness and resampler kernels against fp64."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -52,3 +52,13 @@ def test_random_shapes_of_the_gru_recurrence_match_fp64_step_by_step(seed):
     bad, worst = fuzz_parity.sweep_gru(40, seed, verbose=False, counts=counts)
     assert bad == 0, (bad, worst)
     assert {f"gru_{d}_mfma_kernel<{KP}>" for d in ("fwd", "bwd") for KP in (4, 8, 16, 32)} <= set(counts), counts
+
+
+@pytest.mark.parametrize("seed", [808])
+def test_random_cases_of_the_encoder_stages_match_fp64(seed):
+    """40 random cases, alternately ddsp_loudness (random n_fft, hop and frame count, every hop-long segment at its own level over six
+    decades or exactly zero) and ddsp_resample (random rate pair, L <= 20 000), against the fp64 references of
+    tests/encoder_reference.py: loudness 2e-6, resampled audio 1e-6 (tests/test_encoder_reference_host.py holds the stock fp32
+    branch to half of that on the same cases)."""
+    bad, worst = fuzz_parity.sweep_encoder_stages(40, seed, verbose=False)
+    assert bad == 0, (bad, worst)

@@ -416,7 +416,7 @@ def test_noise_fft_backward_equals_direct_backward(nf, injected):
 def test_noise_error_is_relative_to_each_frames_own_level(hop, nf):
     """The reference transforms every frame alone (filtered_noise.py:7-32), so a quiet frame next to a loud one keeps its own
     relative accuracy.  The hop-512 form transforms two frames as one complex sequence: it equalises them by powers of two first
-    (csrc/ddsp_noise_fft.hip: frame_scale).  Frame levels spread over seven decades, one exactly-zero frame, an odd number
+    (csrc/ddsp_wave_fft.h: frame_scale).  Frame levels spread over seven decades, one exactly-zero frame, an odd number
     of frames per row; error per frame against the C oracle, relative to the frame's own peak."""
     rng = np.random.default_rng(4100 + hop + nf)
     B, T = 3, 21

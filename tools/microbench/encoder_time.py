@@ -129,6 +129,24 @@ def ab(min_s):
     out["loudness"] = {"stock_ms": time_ms(stock_loud, min_s), "hip_ms": lh,
                        "bytes": x.numel() * 4 + 16 * 172 * 4}
     out["loudness"]["hbm_fraction"] = out["loudness"]["bytes"] / (lh * 1e-3) / HBM_BYTES_PER_S
+    # ... and through the pair kernel (two frames per transform, equalised): every size at hop n_fft / 4 on the same batch;
+    # 1024 / 256 is the 16 kHz 'full' configuration
+    out["loudness_pair"] = {}
+    for n_fft in (64, 128, 256, 512, 1024):
+        class CfgN:
+            sample_rate, hop_length = 16000, n_fft // 4
+        CfgN.n_fft = n_fft
+        encn = ddsp.LoudnessEncoder(CfgN).cuda()
+        ones = torch.ones(n_fft, device="cuda")
+
+        def stock_loudn():
+            s = torch.stft(x, n_fft, n_fft // 4, center=False, return_complex=True, window=ones).permute(0, 2, 1)
+            d = torch.log10(torch.abs(s) + 1e-20) * 20
+            d += encn.a_weight
+            return torch.mean(d / 90 + 1, dim=-1, keepdim=True)
+
+        out["loudness_pair"][str(n_fft)] = {"stock_ms": time_ms(stock_loudn, min_s / 2), "hip_ms": time_ms(lambda: encn(x), min_s / 2),
+                                            "frames": 16 * (1 + (x.shape[1] - n_fft) // (n_fft // 4))}
     # resampler
     rs = ddsp.encoder.Resample(44100, 16000).cuda()
     yr = rs(x)
