@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .analysis import harmonic_analysis
 from .decoder import Decoder
 from .encoder import Encoder
 
@@ -33,6 +34,20 @@ class AutoEncoder(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
         return self.decoder(self.encoder(x))
+
+    def analyse(self, x: torch.Tensor, return_complex: bool = False) -> dict:
+        """audio [B, L] -> the oscillator bank's control dict without the decoder's network: the encoder's pitch track (and its
+        voicing, where that is on) of the clip padded as forward() pads it, then analysis.harmonic_analysis of the clip cropped to
+        its T = L // hop whole frames.  `self.decoder.harmonics(self.analyse(x))` is the harmonic resynthesis of x."""
+        bank = self.decoder.harmonics
+        with torch.no_grad():
+            z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
+        f0 = z['f0']
+        frames = f0.shape[1]
+        if frames * self.hop_length > x.shape[-1]:
+            raise ValueError(f"the encoder returned {frames} frames of hop {self.hop_length} for {x.shape[-1]} samples")
+        return harmonic_analysis(x[:, :frames * self.hop_length], f0, self.hop_length, bank.sample_rate, bank.n_harmonics,
+                                 self.padding + self.hop_length, voiced=z.get('voiced'), return_complex=return_complex)
 
     def live_window(self, x: np.ndarray) -> torch.Tensor:
         """The callback's window on the module's device, trimmed as autoencoder.py:28-30 trims it: [1, len - hop]."""

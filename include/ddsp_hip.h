@@ -459,6 +459,38 @@ int ddsp_pitch_voicing(const float *f0, const float *normalized, const float *pe
 int ddsp_yin_salience(const float *y, const float *bin_table, float *probs, long B, long Lr, int hop, long T, void *stream);
 
 /*
+ * Harmonic analysis: the inverse of the oscillator bank (DESIGN.md section 14 has the definition).  All fp32, dense row-major.
+ *   audio [B, N], N = T hop;  f0 [B, T] Hz;  voiced [B, T] bytes or NULL
+ * With up() the bank's own upsampling (pos = (n + 0.5) / hop - 0.5 clamped to [0, T - 1], linear between frames), f0* = f0 with
+ * frames that are not finite or <= 0 set to 0, and theta[n] = sum_{m <= n} up(f0*)[m] / sample_rate in turns:
+ *   frame t covers the samples s_t + j, j in [0, W), s_t = t hop - floor((W - hop) / 2), under the periodic Hann window w; samples
+ *   outside [0, N) are left out of the sum and of norm_t = sum of the w[j] inside
+ *   C[t, k] = (2 / norm_t) sum_j w[j] audio[s_t + j] exp(-2 pi i k theta[s_t + j]),  k = 1 .. H
+ *   C[t, k] = 0 where fl32(k f0[t]) > sample_rate / 2 (integer division, as the bank masks), where f0[t] is not finite or <= 0,
+ *   and where voiced[t] == 0
+ *   amp = |C|, a[t] = sum_k amp[t, k], c[t, k] = amp[t, k] / a[t], and c[t, :] = 1 / H where a[t] == 0
+ *   harm[n] = sum_k Re(up(C[:, k])[n] exp(+2 pi i k theta[n])),  resid = audio - harm
+ * ddsp_harm_analysis  -> C [B, T, H] interleaved (re, im), a [B, T], c [B, T, H]; it fills `workspace` with theta.
+ * ddsp_harm_resynth   C [B, T, H] interleaved (8-byte aligned) -> harm [B, N] and, where resid is not NULL, resid = audio - harm
+ *                     (audio may be NULL otherwise).  With DDSP_HARM_PHASE_READY in flags the workspace still holds the theta
+ *                     of a ddsp_harm_analysis or ddsp_harm_resynth call with the same f0, B, T, hop and sample_rate, and the
+ *                     phase pass is not run again.
+ * workspace: ddsp_harm_workspace_bytes(B, T, hop) bytes (0: the sizes are not positive or overflow), 16-byte aligned.  theta is
+ * accumulated as 64-bit fixed point and kept per sample as a 32-bit fraction of a turn.  W even, 2 <= W <= 4096, H <= 256, any
+ * hop >= 1 and T >= 1: a larger W or H, or sizes beyond 2^56 elements, are DDSP_ERANGE; a null pointer, an odd W or a size that is
+ * not positive DDSP_EINVAL; B == 0 returns 0.  Four launches (analysis) or three (resynthesis; one with the flag), no atomics
+ * on global memory, no allocation, no host synchronisation; every sum has one order: a row's results are the same bits from
+ * run to run and whatever else is in the batch.  A sample that is not finite reaches the frames whose windows hold it and,
+ * through them, the samples of `harm` that interpolate those frames; nothing else.
+ */
+#define DDSP_HARM_PHASE_READY 1u
+size_t ddsp_harm_workspace_bytes(long B, long T, int hop);
+int ddsp_harm_analysis(const float *audio, const float *f0, const uint8_t *voiced, float *C, float *a, float *c, void *workspace,
+                       long B, long T, int hop, int W, int H, int sample_rate, void *stream);
+int ddsp_harm_resynth(const float *C, const float *f0, const float *audio, float *harm, float *resid, void *workspace, long B,
+                      long T, int hop, int H, int sample_rate, unsigned flags, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
