@@ -14,6 +14,17 @@ The returned `f0` is the track the analysis demodulated with: the input with fra
 that `OscillatorBank` on the dict runs the same phases.  CUDA fp32 tensors with an even win_length <= 4096 and n_harmonics <= 256
 take the HIP kernels (csrc/ddsp_harm.hip); CPU tensors, and CUDA calls outside that range or in fp64, run the same definition as
 stock torch ops in the input's dtype (fp64 in, fp64 out), frames and samples in chunks that bound the memory.  No backward.
+
+Noise analysis: the inverse of `FilteredNoise` (include/ddsp_hip.h: ddsp_noise_analysis).  From a residual
+x [B, T hop] the band magnitudes H [B, T, n_filters] whose FilteredNoise frames have, in expectation, the in-frame
+autocorrelation measured on x (averaged over `average` frames), by `iterations` steps of a multiplicative fixed point:
+
+  noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=False) -> H [B, T, F]  (or (H, p), p the target spectrum)
+  NoiseAnalyzer(conf)     nn.Module without parameters over conf.n_noise_filters / hop_length
+
+hop >= 2 (n_filters - 1) is required (below it the filter is cropped and H is not identifiable).  CUDA fp32 tensors with
+n_filters <= 257 and hop <= 1024 take the HIP kernels (csrc/ddsp_noise_analysis.hip); everything else the same definition as
+stock torch ops in the input's dtype.  No backward.
 """
 from __future__ import annotations
 
@@ -29,6 +40,9 @@ KERNEL_MAX_WINDOW = 4096
 KERNEL_MAX_HARMONICS = 256
 PHASE_READY = 1                          # include/ddsp_hip.h: DDSP_HARM_PHASE_READY
 _CHUNK_ELEMENTS = 1 << 24                # the torch path's largest intermediate, in elements
+NOISE_KERNEL_MAX_FILTERS = 257           # csrc/ddsp_noise_analysis.hip: kMaxF, kMaxHop, kMaxGrid
+NOISE_KERNEL_MAX_HOP = 1024
+NOISE_KERNEL_MAX_FRAMES = 2 ** 31 - 1
 
 
 def _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, what):
@@ -263,3 +277,129 @@ class HarmonicAnalyzer(nn.Module):
 
     def forward(self, audio, f0, voiced=None):
         return harmonic_analysis(audio, f0, self.hop_length, self.sample_rate, self.n_harmonics, self.win_length, voiced=voiced)
+
+
+# ------------------------------------------------------------------------------------------------------------ noise analysis
+
+def _noise_tables(F: int, hop: int, dt, dev):
+    """(A [M, F], d [M], Cos [F, L]): the non-zero rows of the impulse-response map (offsets e = j below M / 2, j - M above; samples
+    d = e or hop + e) and c_l g[l] cos(pi b l / L); evaluated in fp64, rounded once to dt."""
+    L, M = F - 1, 2 * (F - 1)
+    j = torch.arange(M, device=dev)
+    e = torch.where(j < L, j, j - M)
+    b = torch.arange(F, device=dev)
+    cb = torch.where((b == 0) | (b == F - 1), 1.0, 2.0).double()
+    A = ((0.5 + 0.5 * torch.cos(math.pi * e.double() / L))[:, None] * (cb / M)[None, :]
+         * torch.cos(math.pi * torch.remainder(b[None, :] * e[:, None], M).double() / L))
+    lag = torch.arange(L, device=dev)
+    cl = torch.where(lag == 0, 1.0, 2.0).double() * (0.5 + 0.5 * torch.cos(math.pi * lag.double() / L))
+    Cos = cl[None, :] * torch.cos(math.pi * torch.remainder(b[:, None] * lag[None, :], M).double() / L)
+    return A.to(dt), torch.where(e >= 0, e, hop + e), Cos.to(dt)
+
+
+def _lagged(a: torch.Tensor, k: torch.Tensor, L: int, weights=None) -> torch.Tensor:
+    """a, k [n, hop] -> [n, L]: sum_{d < hop - l} w[l][d] a[d] k[d + l], w = 1 or the truncation weights hop - l - d."""
+    hop = a.shape[-1]
+    out = torch.empty((a.shape[0], L), dtype=a.dtype, device=a.device)
+    for lag in range(L):
+        prod = a[:, :hop - lag] * k[:, lag:]
+        out[:, lag] = (prod if weights is None else prod * weights[lag:]).sum(-1)
+    return out
+
+
+def _noise_spectrum(r: torch.Tensor, Cos: torch.Tensor) -> torch.Tensor:
+    q = r @ Cos.T
+    ext = torch.cat([q[:, 1:2], q, q[:, -2:-1]], dim=-1)
+    return 0.25 * ext[:, :-2] + 0.5 * ext[:, 1:-1] + 0.25 * ext[:, 2:]
+
+
+def _noise_torch(x, hop, F, average, iterations):
+    dt, dev = x.dtype, x.device
+    B = x.shape[0]
+    T, L = x.shape[1] // hop, F - 1
+    A, d, Cos = _noise_tables(F, hop, dt, dev)
+    weights = torch.arange(hop, 0, -1, device=dev).to(dt)        # weights[l + d] = hop - l - d
+    frames = x.reshape(B * T, hop)
+    step = max(1, _CHUNK_ELEMENTS // hop)
+    r = torch.cat([_lagged(frames[i:i + step], frames[i:i + step], L) for i in range(0, B * T, step)]).reshape(B, T, L)
+    s = min((average - 1) // 2, T - 1)
+    rbar = torch.zeros_like(r)
+    for o in range(-s, s + 1):                                   # t' = t + o ascending; no prefix sums: a NaN stays in its window
+        t0, t1 = max(0, -o), T - max(0, o)
+        rbar[:, t0:t1] += r[:, t0 + o:t1 + o]
+    t = torch.arange(T, device=dev)
+    rbar = rbar / ((t + s).clamp(max=T - 1) - (t - s).clamp(min=0) + 1).to(dt)[None, :, None]
+    p = _noise_spectrum(rbar.reshape(B * T, L), Cos).clamp(min=0)                # (clamp keeps a NaN)
+    H = torch.sqrt(3.0 * p / hop)
+    tiny = torch.finfo(dt).tiny
+    for _ in range(iterations):
+        for i in range(0, B * T, step):
+            Hc, pc = H[i:i + step], p[i:i + step]
+            k = torch.zeros((Hc.shape[0], hop), dtype=dt, device=dev)
+            k[:, d] = Hc @ A.T
+            R = _lagged(k, k, L, weights) / 3.0
+            H[i:i + step] = Hc * torch.sqrt(pc / _noise_spectrum(R, Cos).clamp(min=tiny))
+    return H.reshape(B, T, F), p.reshape(B, T, F)
+
+
+def _noise_in_kernel_range(x: torch.Tensor, hop: int, F: int) -> bool:
+    return (x.is_cuda and x.dtype == torch.float32 and F <= NOISE_KERNEL_MAX_FILTERS and hop <= NOISE_KERNEL_MAX_HOP
+            and x.shape[0] * (x.shape[1] // hop) <= NOISE_KERNEL_MAX_FRAMES)
+
+
+def _noise_device(x, hop, F, average, iterations, return_power):
+    B, T = x.shape[0], x.shape[1] // hop
+    H = torch.empty((B, T, F), device=x.device, dtype=torch.float32)
+    p = torch.empty_like(H) if return_power else None
+    ws = torch.empty(_lib.lib().ddsp_noise_analysis_workspace_bytes(B, T, F, hop), device=x.device, dtype=torch.uint8)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().ddsp_noise_analysis(x.data_ptr(), H.data_ptr(), None if p is None else p.data_ptr(), ws.data_ptr(), B, T, F,
+                                            hop, min(average, 2 * T + 1), iterations, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_noise_analysis")
+    return H, p
+
+
+def noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=False):
+    """x [B, T hop] -> H [B, T, n_filters] >= 0 as `FilteredNoise` reads it (with return_power: (H, p), p [B, T, n_filters] the
+    smoothed, lag-windowed spectrum of the averaged autocorrelation that H reproduces in expectation)."""
+    what = "noise_analysis"
+    hop, F, average, iterations = int(hop), int(n_filters), int(average), int(iterations)
+    if x.dim() != 2:
+        raise ValueError(f"{what}: x must be [B, N], got {tuple(x.shape)}")
+    if F < 2 or hop < 1:
+        raise ValueError(f"{what}: n_filters must be at least 2 and hop positive, got {F} and {hop}")
+    if hop < 2 * (F - 1):
+        raise ValueError(f"{what}: hop {hop} < 2 (n_filters - 1) = {2 * (F - 1)}: FilteredNoise crops the impulse response there "
+                         "and H is not identifiable")
+    if average < 1 or average % 2 == 0:
+        raise ValueError(f"{what}: average must be an odd count of frames, got {average}")
+    if iterations < 0:
+        raise ValueError(f"{what}: iterations must be at least 0, got {iterations}")
+    if x.shape[1] == 0 or x.shape[1] % hop:
+        raise ValueError(f"{what}: x has {x.shape[1]} samples, which is no positive number of whole frames of hop {hop}")
+    _refuse_grad(x, what)
+    x = x.detach()
+    if x.dtype not in (torch.float32, torch.float64):            # integers and 16-bit floats: analysed in fp32
+        x = x.float()
+    x = x.contiguous()
+    if x.shape[0] == 0:
+        H = torch.zeros((0, x.shape[1] // hop, F), dtype=x.dtype, device=x.device)
+        return (H, torch.zeros_like(H)) if return_power else H
+    if _noise_in_kernel_range(x, hop, F):
+        H, p = _noise_device(x, hop, F, average, iterations, return_power)
+    else:
+        H, p = _noise_torch(x, hop, F, average, iterations)
+    return (H, p) if return_power else H
+
+
+class NoiseAnalyzer(nn.Module):
+    """forward(x [B, T hop], average=1, iterations=16) -> H [B, T, n_noise_filters]: `noise_analysis` at the configuration's
+    n_noise_filters and hop_length.  No parameters."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.n_filters = conf.n_noise_filters
+        self.hop_length = conf.hop_length
+
+    def forward(self, x, average=1, iterations=16):
+        return noise_analysis(x, self.hop_length, self.n_filters, average=average, iterations=iterations)

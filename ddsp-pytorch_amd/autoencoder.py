@@ -2,6 +2,8 @@
 
   forward(x)                 audio [B, L] -> audio: pads (p // 2, p - p // 2) with p = n_fft - hop so that the loudness frames
                              and the CREPE frames line up with the decoder's hop grid (autoencoder.py:17-22)
+  analyse(x, noise=False)    the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True,
+                             H by noise analysis of the residual (analysis.py)
   forward_live(x, hidden)    the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
                              encoder, then Decoder.forward_live -> (audio as numpy, hidden)
@@ -18,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .analysis import harmonic_analysis
+from .analysis import harmonic_analysis, harmonic_residual, noise_analysis
 from .decoder import Decoder
 from .encoder import Encoder
 
@@ -30,15 +32,21 @@ class AutoEncoder(nn.Module):
         self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed)
         self.padding = conf.n_fft - conf.hop_length
         self.hop_length = conf.hop_length
+        self.n_noise_filters = conf.n_noise_filters
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
         return self.decoder(self.encoder(x))
 
-    def analyse(self, x: torch.Tensor, return_complex: bool = False) -> dict:
+    def analyse(self, x: torch.Tensor, return_complex: bool = False, noise: bool = False, average: int = 1,
+                iterations: int = 16) -> dict:
         """audio [B, L] -> the oscillator bank's control dict without the decoder's network: the encoder's pitch track (and its
         voicing, where that is on) of the clip padded as forward() pads it, then analysis.harmonic_analysis of the clip cropped to
-        its T = L // hop whole frames.  `self.decoder.harmonics(self.analyse(x))` is the harmonic resynthesis of x."""
+        its T = L // hop whole frames.  `self.decoder.harmonics(self.analyse(x))` is the harmonic resynthesis of x.
+
+        noise=True adds 'H' [B, T, n_noise_filters]: analysis.noise_analysis (with `average` and `iterations`) of the residual
+        analysis.harmonic_residual leaves, so that `self.decoder.synthesize(self.analyse(x, noise=True))` is the parametric
+        harmonic-plus-noise resynthesis of x."""
         bank = self.decoder.harmonics
         with torch.no_grad():
             z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
@@ -46,8 +54,13 @@ class AutoEncoder(nn.Module):
         frames = f0.shape[1]
         if frames * self.hop_length > x.shape[-1]:
             raise ValueError(f"the encoder returned {frames} frames of hop {self.hop_length} for {x.shape[-1]} samples")
-        return harmonic_analysis(x[:, :frames * self.hop_length], f0, self.hop_length, bank.sample_rate, bank.n_harmonics,
-                                 self.padding + self.hop_length, voiced=z.get('voiced'), return_complex=return_complex)
+        args = (x[:, :frames * self.hop_length], f0, self.hop_length, bank.sample_rate, bank.n_harmonics, self.padding + self.hop_length)
+        if not noise:
+            return harmonic_analysis(*args, voiced=z.get('voiced'), return_complex=return_complex)
+        _, resid, ctrl = harmonic_residual(*args, voiced=z.get('voiced'), return_complex=return_complex)
+        ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average,
+                                   iterations=iterations)
+        return ctrl
 
     def live_window(self, x: np.ndarray) -> torch.Tensor:
         """The callback's window on the module's device, trimmed as autoencoder.py:28-30 trims it: [1, len - hop]."""

@@ -491,6 +491,32 @@ int ddsp_harm_resynth(const float *C, const float *f0, const float *audio, float
                       long T, int hop, int H, int sample_rate, unsigned flags, void *stream);
 
 /*
+ * Noise analysis: the inverse of ddsp_noise_forward_ws, exact in expectation for the filter that call
+ * applies (truncated to the frame, the anti-causal half wrapped, Hann-windowed).  Per row, all fp32, dense row-major:
+ *   x [B, N], N = T hop; frame t is the samples [t hop, (t + 1) hop).  F = n_filters >= 2, M = 2 (F - 1), L = F - 1, hop >= M.
+ *   1. k = Amat H, Amat [hop x F] = the impulse-response map on unit vectors (irfft, roll by M / 2, periodic Hann of size M, pad
+ *      to hop, roll by -M / 2); its non-zero rows are d in [0, M / 2) and [hop - M / 2, hop).
+ *   2. a frame of the noise is y[n] = sum_{m <= n} s[m] k[n - m] with s iid uniform(-1, 1), so its expected in-frame
+ *      autocorrelation is R(H)[l] = 1/3 sum_{d = 0}^{hop - 1 - l} (hop - l - d) k[d] k[d + l], l in [0, L).
+ *   3. r_t[l] = sum_{n = 0}^{hop - 1 - l} x[t hop + n] x[t hop + n + l]; rbar_t = the mean of r_t' over t' in [t - s, t + s]
+ *      inside [0, T), s = (average - 1) / 2 (average odd; it may exceed T).
+ *   4. P(r)[b] = S(q)[b], q[b] = sum_{l < L} c_l g[l] r[l] cos(pi b l / (F - 1)), c_0 = 1, c_l = 2, g[l] = 1/2 + 1/2 cos(pi l / L),
+ *      S the smoothing (1/4, 1/2, 1/4) with mirrored ends (q[-1] = q[1], q[F] = q[F - 2]).
+ *   5. p = max(P(rbar_t), 0); H^0 = sqrt(3 p / hop); H^{i + 1} = H^i sqrt(p / max(P(R(H^i)), FLT_MIN)); H = H^iterations >= 0.
+ * ddsp_noise_analysis  -> H [B, T, F] and, where power is not NULL, power [B, T, F] = p.
+ * workspace: ddsp_noise_analysis_workspace_bytes(B, T, F, hop) bytes (0: sizes that are not positive, overflow or lie outside the
+ * range below), 16-byte aligned; the call fills it with its tables and r.  Range: 2 <= F <= 257 and 2 (F - 1) <= hop <= 1024,
+ * B T <= 2^31 - 1: anything else is DDSP_ERANGE.  A null x, H or workspace, T, F - 1, hop or iterations + 1 that is not positive,
+ * an average that is even or below 1: DDSP_EINVAL, before anything touches the device; B == 0 returns 0.  Three launches, no
+ * atomics on global memory, no allocation, no host synchronisation; every sum has one order: a row's results are the same bits
+ * from run to run and whatever else is in the batch.  A silent frame gives H = 0.  A sample that is not finite reaches the frames
+ * whose averaging window holds its frame, and nothing else.
+ */
+size_t ddsp_noise_analysis_workspace_bytes(long B, long T, int F, int hop);
+int ddsp_noise_analysis(const float *x, float *H, float *power, void *workspace, long B, long T, int F, int hop, int average,
+                        int iterations, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
