@@ -27,13 +27,15 @@
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
 #include "ddsp_osc_common.h"
+#include "ddsp_osc_plan.h"
 
 using namespace ddsp_osc;
 
 namespace {
 
 // Production walk over samples [n_beg, n_end) of frame t, written stage by stage over the lane's K harmonics
-// so that the K independent dependency chains interleave.
+// so that the K independent dependency chains interleave (the stages shared with the backward and the chunked totals walk:
+// ddsp_osc_common.h).
 // KL <= K: only the lane's first KL harmonic slots are walked (the others are silent in this frame, see
 // osc_synth_kernel).  NS consecutive samples are advanced per iteration: a stage then covers NS*KL independent
 // instructions, which keeps the short walks (KL = K/4, K/2) from stalling on the latency of the previous stage;
@@ -54,10 +56,6 @@ __device__ __forceinline__ void walk_fast(const OscParams &p, FrameState<K> &st,
         upsample_weights(p.scale, t * p.R + n_beg, i0f, w0s, lam);
         dlam = (t == 0 && n_beg == 0) ? 0.0f : p.scale;
     }
-    // Each stage is one instruction TYPE over the lane's harmonics; the scheduling barriers keep the stages
-    // apart: runs of same-type VALU instructions issue ~10 % faster on gfx950 than the interleaved chains
-    // (tools/microbench/valu_rates.hip: "chain staged" vs "osc chain").
-#define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
     // LDS operations of one wavefront execute in order, so the staging buffer needs no s_waitcnt between lane 0's
     // writes and the group's reads -- only the compiler must not reorder them (DDSP_WAVE_ORDER).  (A wavefront-scope fence
     // here also waits for the global stores of the previous flush: measured 2x slowdown of the short walks.)
@@ -76,78 +74,28 @@ __device__ __forceinline__ void walk_fast(const OscParams &p, FrameState<K> &st,
                 upsample_weights(p.scale, t * p.R + n + e, i0f, w0[e], w1[e]);
             }
         }
-        float v[NS][KL];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int e = 0; e < NS; ++e)
-#pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = w1[e] * st.x1[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int e = 0; e < NS; ++e)
-#pragma unroll
-            for (int m = 0; m < KL; ++m) v[e][m] = __fmaf_rn(w0[e], st.x0[m], v[e][m]);  // fl32(fma(w0,x[i0],fl32(w1*x[i1])))
         DDSP_STAGE_END();
         double d[NS][KL];
-#pragma unroll
-        for (int e = 0; e < NS; ++e)
-#pragma unroll
-            for (int m = 0; m < KL; ++m) d[e][m] = (double)v[e][m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int e = 0; e < NS; ++e)
-#pragma unroll
-            for (int m = 0; m < KL; ++m) {
-                st.acc[m] += d[e][m];                                                // :41 double accumulator
-                d[e][m] = st.acc[m];
-            }
-        DDSP_STAGE_END();
+        phase_chain(w0, w1, st.x0, st.x1, st.acc, d);
         if (MODE == MODE_SYNTH) {
+            float v[NS][KL], q[NS][KL];
 #pragma unroll
             for (int e = 0; e < NS; ++e)
 #pragma unroll
                 for (int m = 0; m < KL; ++m) v[e][m] = (float)d[e][m];               // ... rounded to fp32 per sample
             DDSP_STAGE_END();
-            // P - q*2pi32 is exact in fp32 for q = rint(P/2pi32 +- 0.25) < 2^21: r in (-4.8, 4.8).  Taking the
-            // nearest multiple instead of the floor changes sin(r) by <= |2pi32 - 2pi| = 1.75e-7.
-            float q[NS][KL];
             if (fresh) {   // wave-uniform
-#pragma unroll
-                for (int e = 0; e < NS; ++e)
-#pragma unroll
-                    for (int m = 0; m < KL; ++m) q[e][m] = __fmaf_rn(v[e][m], kInvTwoPi32, kRoundMagic);
-                DDSP_STAGE_END();
-#pragma unroll
-                for (int e = 0; e < NS; ++e)
-#pragma unroll
-                    for (int m = 0; m < KL; ++m) q[e][m] = q[e][m] - kRoundMagic;
-                DDSP_STAGE_END();
+                phase_quotient(v, q);
                 if (QKEEP) {
 #pragma unroll
                     for (int m = 0; m < KL; ++m) qk[m] = q[0][m];
                 }
-            } else {
-                // The previous sample's quotient: below Nyquist the phase advanced by at most pi since then, so
-                // r = P - q*2pi32 stays in (-pi, 2 pi] -- still a multiple of 2^-21 below 8, i.e. exact -- and v_sin_f32
-                // takes any argument within +-256 revolutions.  Saves the two rounding instructions every other sample.
+            } else {       // the previous sample's quotient
 #pragma unroll
                 for (int m = 0; m < KL; ++m) q[0][m] = qk[m];
             }
-#pragma unroll
-            for (int e = 0; e < NS; ++e)
-#pragma unroll
-                for (int m = 0; m < KL; ++m) v[e][m] = __fmaf_rn(-q[e][m], kTwoPi32, v[e][m]);  // :42
-            DDSP_STAGE_END();
-#pragma unroll
-            for (int e = 0; e < NS; ++e)
-#pragma unroll
-                for (int m = 0; m < KL; ++m) v[e][m] = v[e][m] * kRevPerRad;
-            DDSP_STAGE_END();
-#pragma unroll
-            for (int e = 0; e < NS; ++e)
-#pragma unroll
-                for (int m = 0; m < KL; ++m) v[e][m] = __builtin_amdgcn_sinf(v[e][m]);  // v_sin_f32 (revolutions)
-            DDSP_STAGE_END();
+            phase_remainder(v, q);
+            sin_of_phase(v);
 #pragma unroll
             for (int e = 0; e < NS; ++e)
 #pragma unroll
@@ -213,7 +161,6 @@ __device__ __forceinline__ void walk_fast(const OscParams &p, FrameState<K> &st,
     };
     // (one copy of the body, the choice is a scalar branch: two unrolled copies cost 30 more VGPRs and a wavefront per SIMD)
     for (int n = n_beg; n < n_end; n += NS) one_step(n, !QKEEP || ((n - n_beg) & 1) == 0);
-#undef DDSP_STAGE_END
 }
 
 // Reference-exact walk: libm fmodf modulo, live offsets (:70), live state and debug phase outputs.
@@ -419,27 +366,10 @@ __global__ void __launch_bounds__(256, (SKIP && K <= 13) ? 3 : 1) osc_synth_kern
     const int b = (int)(f / p.T);
     const int t = (int)(f - (long)b * p.T);
     const int ia = max(t - 1, 0), ib = t, ic = (p.R == 1) ? t : min(t + 1, p.T - 1);  // hop 1: F.interpolate copies (no neighbour term)
-    const int sb = t / (256 >> p.logG);
 
     FrameState<K> st;
-    bool fast = true;
-    const float *wb = p.w + (long)b * p.T * p.H;
-#pragma unroll
-    for (int m = 0; m < K; ++m) {
-        const int h = j + m * G;
-        st.acc[m] = 0.0;
-        if (h < p.H) {
-            st.acc[m] = p.loc[((long)b * p.T + t) * p.H + h] + p.sup[((long)b * p.NSB + sb) * p.H + h];
-            // The fast modulo needs 0 <= P < kFastPhaseLimit over the whole frame: increments of the three
-            // bracketing frames non-negative (phases then grow monotonically) and the end-of-frame bound small.
-            const float xa = wb[(long)ia * p.H + h], xb = wb[(long)ib * p.H + h], xc = wb[(long)ic * p.H + h];
-            const float xmax = fmaxf(fmaxf(xa, xb), xc);
-            const float bound = (float)st.acc[m] + (float)p.R * xmax * 1.0001f;
-            // (xmax: a quotient reused for the next sample leaves |r| <= pi + increment; v_sin_f32 wants |r| < 256 * 2 pi)
-            fast = fast && (xa >= 0.0f) && (xb >= 0.0f) && (xc >= 0.0f) && (st.acc[m] >= 0.0) && (bound < kFastPhaseLimit) && (xmax < 1024.0f);
-        }
-    }
-    fast = __all(fast);  // wave-uniform
+    bool fast;
+    DDSP_FRAME_START(K, st, fast);
     if (VARIANT == VAR_FAST && !fast) {
         if ((threadIdx.x & 63) == 0) atomicOr(p.redo_flag, 1);  // the EXACT kernel that follows redoes this wavefront
         return;
@@ -448,26 +378,10 @@ __global__ void __launch_bounds__(256, (SKIP && K <= 13) ? 3 : 1) osc_synth_kern
     const int split = split_index(t, p.R, p.scale);
     float L0, L1;
     if (VARIANT == VAR_FAST) {
-        // Harmonics whose amplitude is exactly zero at all three bracketing frames (above Nyquist: :31-32) are silent
-        // for the whole frame and their phase is not needed either (every frame starts from the scanned totals), so
-        // the walk stops at the highest slot that is audible anywhere in the wavefront: 1/4, 1/2 or all of K.
+        // the walk stops at the highest slot that is audible anywhere in the wavefront: 1/4, 1/2 or all of K
         constexpr int KQ = (K + 3) / 4, KH = (K + 1) / 2;
         int mlive = K;
-        if (SKIP) {
-            // from f0 (three loads) instead of the 3 x K amplitudes themselves (39 loads and their addresses: the registers this
-            // variant spilled): a harmonic above Nyquist at all three bracketing frames has amplitude exactly zero there (:31-32).
-            // Zero amplitudes BELOW Nyquist are simply walked; NaN f0 compares false -> kept; an all-masked frame (NaN amplitudes,
-            // :33) still reaches the output through slot 0, which every walk includes.
-            mlive = 0;
-            const long rowbase = (long)b * p.T;
-            const float fmin3 = fminf(fminf(p.f0[rowbase + ia], p.f0[rowbase + ib]), p.f0[rowbase + ic]);
-#pragma unroll
-            for (int m = 0; m < K; ++m) {
-                const int h = j + m * G;
-                const bool keep = h < p.H && !((float)(h + 1) * fmin3 > p.nyquist);
-                if (__any(keep)) mlive = m + 1;
-            }
-        }
+        if (SKIP) DDSP_AUDIBLE_SLOTS(K, mlive);
 #define DDSP_WALK2(KL, NS)                                                                                   \
         do {                                                                                                 \
             load_synth_segment<K>(p, st, b, j, ia, t == 0 ? ic : ib, L0, L1);   /* frame 0 clamps to source 0 but keeps neighbour 1 */                                              \
@@ -570,8 +484,7 @@ namespace ddsp_osc {
 // Cost model (measured on MI355X): padded harmonic slots are pure waste; the per-sample work
 // shared by a lane's harmonics (weights, cross-lane sum, store) is amortised over K; K >= 20 leaves only two
 // wavefronts per SIMD (>= 200 VGPRs), which costs about 10 %.
-const int kKs[] = {4, 8, 12, 13, 15, 16, 20, 23, 25};
-
+// The values of K: kOscKs (ddsp_osc_plan.h).
 double tiling_cost(int H, int K, int logG, long frames)
 {
     const double waste = (double)((1 << logG) * K) / (double)H;
@@ -592,7 +505,7 @@ bool pick_tiling(int H, long frames, Tiling *out)
     double best = 1e30;
     bool found = false;
     const int forced = g_forced_k.load(std::memory_order_relaxed);
-    for (int K : kKs) {
+    for (int K : kOscKs) {
         if (forced && K != forced) continue;
         const int lanes = (H + K - 1) / K;
         int logG = 0;
@@ -645,7 +558,7 @@ extern "C" int ddsp_osc_set_tiling(int harmonics_per_lane)
     if (harmonics_per_lane != 0) {
         if (!ddsp_hooks_on()) return DDSP_EPERM;
         bool known = false;
-        for (int K : kKs) known = known || (K == harmonics_per_lane);
+        for (int K : kOscKs) known = known || (K == harmonics_per_lane);
         if (!known) return DDSP_ERANGE;
     }
     g_forced_k.store(harmonics_per_lane, std::memory_order_relaxed);
@@ -716,14 +629,7 @@ extern "C" int ddsp_osc_forward_ex(const float *f0, const float *c, const float 
     p.force_exact = (dbg_phi != nullptr || live_in != nullptr || live_out != nullptr) ? 1 : 0;
 
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
     if (!(flags & DDSP_OSC_KEEP_FRAME_SCRATCH) && g_path.load(std::memory_order_relaxed) == 0 && chunked_eligible(p))
         return (int)launch_chunked_k(p, scratch, s);
-    switch (p.K) {
-#define DDSP_CASE(KK) case KK: e = launch_frames<KK>(p, s); break;
-        DDSP_CASE(4) DDSP_CASE(8) DDSP_CASE(12) DDSP_CASE(13) DDSP_CASE(15) DDSP_CASE(16) DDSP_CASE(20) DDSP_CASE(23) DDSP_CASE(25)
-#undef DDSP_CASE
-        default: return DDSP_ERANGE;
-    }
-    return (int)e;
+    return dispatch_k(p.K, [&](auto k) { return (int)launch_frames<decltype(k)::value>(p, s); }, (int)DDSP_ERANGE);
 }

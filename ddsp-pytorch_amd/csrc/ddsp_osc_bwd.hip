@@ -20,6 +20,7 @@
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
 #include "ddsp_osc_common.h"
+#include "ddsp_osc_plan.h"
 
 using namespace ddsp_osc;
 
@@ -44,9 +45,9 @@ __device__ __forceinline__ void walk_bwd(const OscParams &p, FrameState<K> &st, 
         upsample_weights(p.scale, t * p.R + n_beg, i0f, w0s, lam);
         dlam = (t == 0 && n_beg == 0) ? 0.0f : p.scale;
     }
-    // stage-ordered like the forward synth walk (ddsp_osc.hip: walk_fast): one instruction type at a time over the K harmonics
-#define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
-    float qk[KL];
+    // stage-ordered like the forward synth walk, from the same helpers (ddsp_osc_common.h), so that the phases are the forward's;
+    // the modulo's quotient is computed on every other sample and reused for the next one
+    float qk[1][KL];
     for (int n = n_beg; n < n_end; ++n) {
         float w0, w1;
         if (POW2) {
@@ -58,47 +59,24 @@ __device__ __forceinline__ void walk_bwd(const OscParams &p, FrameState<K> &st, 
         }
         const float gi = g_lds ? g_lds[n] : g_glb[n];
         const float gl = gi * __fmaf_rn(w0, L0, w1 * L1);
-        float v[KL];
         DDSP_STAGE_END();
+        const float w0s[1] = {w0}, w1s[1] = {w1};   // (the helpers take NS samples per call: one here)
+        double d[1][KL];
+        phase_chain(w0s, w1s, st.x0, st.x1, st.acc, d);
+        float vs[1][KL];
+        float (&v)[KL] = vs[0];
 #pragma unroll
-        for (int m = 0; m < KL; ++m) v[m] = w1 * st.x1[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < KL; ++m) v[m] = __fmaf_rn(w0, st.x0[m], v[m]);
-        DDSP_STAGE_END();
-        double d[KL];
-#pragma unroll
-        for (int m = 0; m < KL; ++m) d[m] = (double)v[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < KL; ++m) st.acc[m] += d[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < KL; ++m) v[m] = (float)st.acc[m];
+        for (int m = 0; m < KL; ++m) v[m] = (float)st.acc[m];   // (= d[0][m]; read from d, K = 23 compiles to other code)
         DDSP_STAGE_END();
         if (EXACT) {
 #pragma unroll
             for (int m = 0; m < KL; ++m) v[m] = remainder_two_pi_call(v[m]);
+            DDSP_STAGE_END();
         } else {
-            // the modulo's quotient is computed on every other sample and reused for the next one (ddsp_osc.hip: walk_fast)
-            if (!POW2 || ((n - n_beg) & 1) == 0) {   // wave-uniform
-#pragma unroll
-                for (int m = 0; m < KL; ++m) qk[m] = __fmaf_rn(v[m], kInvTwoPi32, kRoundMagic);
-                DDSP_STAGE_END();
-#pragma unroll
-                for (int m = 0; m < KL; ++m) qk[m] = qk[m] - kRoundMagic;
-                DDSP_STAGE_END();
-            }
-#pragma unroll
-            for (int m = 0; m < KL; ++m) v[m] = __fmaf_rn(-qk[m], kTwoPi32, v[m]);
+            if (!POW2 || ((n - n_beg) & 1) == 0) phase_quotient(vs, qk);   // wave-uniform
+            phase_remainder(vs, qk);
         }
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < KL; ++m) v[m] = v[m] * kRevPerRad;
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < KL; ++m) v[m] = __builtin_amdgcn_sinf(v[m]);
-        DDSP_STAGE_END();
+        sin_of_phase(vs);
         float A[KL];
 #pragma unroll
         for (int m = 0; m < KL; ++m) A[m] = __fmaf_rn(w1, st.da[m], st.a0[m]);
@@ -122,7 +100,6 @@ __device__ __forceinline__ void walk_bwd(const OscParams &p, FrameState<K> &st, 
         galo = __fmaf_rn(w0, gu, galo);
         gahi = __fmaf_rn(w1, gu, gahi);
     }
-#undef DDSP_STAGE_END
 }
 
 template <int K, bool POW2>
@@ -147,24 +124,10 @@ __global__ void __launch_bounds__(256) osc_bwd_kernel(OscParams p, int use_lds)
     const int b = (int)(f / p.T);
     const int t = (int)(f - (long)b * p.T);
     const int ia = max(t - 1, 0), ib = t, ic = (p.R == 1) ? t : min(t + 1, p.T - 1);  // hop 1: F.interpolate copies (no neighbour term)
-    const int sb = t / FPB;
 
     FrameState<K> st;
-    bool fast = true;
-    const float *wb = p.w + (long)b * p.T * p.H;
-#pragma unroll
-    for (int m = 0; m < K; ++m) {
-        const int h = j + m * G;
-        st.acc[m] = 0.0;
-        if (h < p.H) {
-            st.acc[m] = p.loc[((long)b * p.T + t) * p.H + h] + p.sup[((long)b * p.NSB + sb) * p.H + h];
-            const float xa = wb[(long)ia * p.H + h], xb = wb[(long)ib * p.H + h], xc = wb[(long)ic * p.H + h];
-            const float xmax = fmaxf(fmaxf(xa, xb), xc);
-            const float bound = (float)st.acc[m] + (float)p.R * xmax * 1.0001f;
-            fast = fast && (xa >= 0.0f) && (xb >= 0.0f) && (xc >= 0.0f) && (st.acc[m] >= 0.0) && (bound < kFastPhaseLimit) && (xmax < 1024.0f);
-        }
-    }
-    fast = __all(fast);
+    bool fast;
+    DDSP_FRAME_START(K, st, fast);
     const int split = POW2 ? (p.R >> 1) : split_index(t, p.R, p.scale);
     const float *g_lds = use_lds ? g_s + (active ? fl : 0) * p.R : nullptr;
     const float *g_glb = p.grad_y + f * p.R;
@@ -174,20 +137,11 @@ __global__ void __launch_bounds__(256) osc_bwd_kernel(OscParams p, int use_lds)
     float ga_m1 = 0.0f, ga_0 = 0.0f, ga_p1 = 0.0f;
     float L0, L1;
     // Harmonics above Nyquist at all three bracketing frames (:31-32, strict >) get a zero gradient at each of them and their
-    // phase feeds nothing else: the walk stops at the highest slot that is below Nyquist anywhere in the wavefront.
+    // phase feeds nothing else: the walk stops at the highest slot that is below Nyquist anywhere in the wavefront
+    // (`!(hz > nyquist)` at the smallest of the three f0 <=> unmasked at one of them).
     constexpr int KQ = (K + 3) / 4, KH = (K + 1) / 2;
-    int mlive = 0;
-    {
-        const long rowbase = (long)b * p.T;
-        const float fmin3 = fminf(fminf(p.f0[rowbase + ia], p.f0[rowbase + ib]), p.f0[rowbase + ic]);
-#pragma unroll
-        for (int m = 0; m < K; ++m) {
-            const int h = j + m * G;
-            // NaN f0 compares false -> kept; `!(hz > nyquist)` at the smallest of the three f0 <=> unmasked at one of them
-            const bool keep = h < p.H && !((float)(h + 1) * fmin3 > p.nyquist);
-            if (__any(keep)) mlive = m + 1;
-        }
-    }
+    int mlive;
+    DDSP_AUDIBLE_SLOTS(K, mlive);
 #define DDSP_BWD2(KL)                                                                                                     \
     do {                                                                                                                  \
         load_synth_segment<K>(p, st, b, j, ia, t == 0 ? ic : ib, L0, L1);   /* frame 0 clamps to source 0, keeps neighbour 1 */ \
@@ -312,12 +266,5 @@ extern "C" int ddsp_osc_backward(const float *grad_y, const float *f0, const flo
     p.part_c = (float *)bwd_scratch;
     p.part_a = (float *)((char *)bwd_scratch + align256((size_t)B * T * 3 * H * sizeof(float)));
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (p.K) {
-#define DDSP_CASE(KK) case KK: e = launch_bwd<KK>(p, s); break;
-        DDSP_CASE(4) DDSP_CASE(8) DDSP_CASE(12) DDSP_CASE(13) DDSP_CASE(15) DDSP_CASE(16) DDSP_CASE(20) DDSP_CASE(23) DDSP_CASE(25)
-#undef DDSP_CASE
-        default: return DDSP_ERANGE;
-    }
-    return (int)e;
+    return dispatch_k(p.K, [&](auto k) { return (int)launch_bwd<decltype(k)::value>(p, s); }, (int)DDSP_ERANGE);
 }

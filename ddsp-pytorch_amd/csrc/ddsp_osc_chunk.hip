@@ -59,8 +59,6 @@ constexpr int kTotalsTurnEvery = 16;   // totals walk: the same (a multiple of 4
 constexpr int kRow = 256 + 4;          // staging row: one float per thread of the workgroup, padded
 constexpr float kReuseMaxInc = 4.8f;   // quotient reuse: r = P - q*2pi32 stays exact while |r| < 8, i.e. increments < 8 - pi
 
-#define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
-
 // F.interpolate weights inside a segment (App. A item 4 for a power-of-two hop): sample n has w1 = (2n+1)/(2 hop), exact, and
 // advances by exactly 1/hop per sample; segment 0 has its source index clamped to 0: w1 = 0 throughout.  (Built by the
 // scalar unit instead -- 25 dependent SALU instructions per sample -- the walk ran 13 % slower: gpurun_out r04a.)
@@ -222,6 +220,8 @@ __device__ __forceinline__ void walk_synth(const OscParams &p, ChunkState<K, KR>
             w1[e] = w1[e - 1] + dlam;
             w0[e] = w0[e - 1] - dlam;
         }
+        // (the sample body keeps its own copy of the chain: through phase_chain this kernel compiles to other code, see
+        // profiles/osc_shared_chain_codegen.md)
         float v[NS][KLR], r[NS][KL];
         DDSP_STAGE_END();
 #pragma unroll
@@ -412,21 +412,10 @@ __device__ __forceinline__ void walk_totals(const OscParams &p, double (&acc)[K]
     for (int n = nb; n < nb + kTotalsTurnEvery; n += 4) {   // four samples unrolled: one block, no copy of the weights
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        float v[K];
         DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < K; ++m) v[m] = lam * x1[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < K; ++m) v[m] = __fmaf_rn(mal, x0[m], v[m]);
-        DDSP_STAGE_END();
-        double d[K];
-#pragma unroll
-        for (int m = 0; m < K; ++m) d[m] = (double)v[m];
-        DDSP_STAGE_END();
-#pragma unroll
-        for (int m = 0; m < K; ++m) acc[m] += d[m];
-        DDSP_STAGE_END();
+        const float w0[1] = {mal}, w1[1] = {lam};
+        double d[1][K];
+        phase_chain(w0, w1, x0, x1, acc, d);
         lam += dlam;   // (in place, after their last use: no copies)
         mal -= dlam;
     }
@@ -1040,13 +1029,7 @@ hipError_t launch_chunked(OscParams p, void *scratch, hipStream_t s)
 hipError_t chunk_geometry_k(OscParams &p, int *cus, int *wg_per_cu)
 {
     Residency res = {};
-    hipError_t e = hipErrorInvalidValue;
-    switch (p.K) {
-#define DDSP_CASE(KK) case KK: e = chunk_geometry<KK>(p, &res); break;
-        DDSP_CASE(4) DDSP_CASE(8) DDSP_CASE(12) DDSP_CASE(13) DDSP_CASE(15) DDSP_CASE(16) DDSP_CASE(20) DDSP_CASE(23) DDSP_CASE(25)
-#undef DDSP_CASE
-        default: break;
-    }
+    const hipError_t e = dispatch_k(p.K, [&](auto k) { return chunk_geometry<decltype(k)::value>(p, &res); }, hipErrorInvalidValue);
     *cus = res.cus;
     *wg_per_cu = res.wg_per_cu;
     return e;
@@ -1063,12 +1046,7 @@ const int *chunk_flag_words(OscParams p)
 
 hipError_t launch_chunked_k(const OscParams &p, void *scratch, hipStream_t s)
 {
-    switch (p.K) {
-#define DDSP_CASE(KK) case KK: return launch_chunked<KK>(p, scratch, s);
-        DDSP_CASE(4) DDSP_CASE(8) DDSP_CASE(12) DDSP_CASE(13) DDSP_CASE(15) DDSP_CASE(16) DDSP_CASE(20) DDSP_CASE(23) DDSP_CASE(25)
-#undef DDSP_CASE
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_k(p.K, [&](auto k) { return launch_chunked<decltype(k)::value>(p, scratch, s); }, hipErrorInvalidValue);
 }
 
 }  // namespace ddsp_osc

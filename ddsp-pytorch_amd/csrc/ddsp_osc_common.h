@@ -1,5 +1,5 @@
-// Shared device helpers and host-side parameter block of the oscillator kernels
-// (ddsp_osc.hip: forward, ddsp_osc_bwd.hip: backward).  See ddsp_osc.hip for the design notes.
+// Shared device helpers and host-side parameter block of the oscillator kernels (ddsp_osc.hip: forward, frame form;
+// ddsp_osc_chunk.hip: forward, chunked form; ddsp_osc_bwd.hip: backward).  See ddsp_osc.hip for the design notes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,6 +170,112 @@ __device__ __forceinline__ void load_synth_segment(const OscParams &p, FrameStat
     L0 = p.a[rowbase + i0];
     L1 = p.a[rowbase + i1];
 }
+
+// ---- the staged phase chain -------------------------------------------------------------------------------------------
+// The production walks are written stage by stage -- one instruction TYPE over the lane's harmonics -- and scheduling barriers
+// keep the stages apart: runs of same-type VALU instructions issue ~10 % faster on gfx950 than the interleaved chains
+// (tools/microbench/valu_rates.hip: "chain staged" vs "osc chain").
+#define DDSP_STAGE_END() __builtin_amdgcn_sched_barrier(0)
+
+// one stage: a statement over the NS samples (e) x KL slots (m), fully unrolled
+#define DDSP_EACH_SLOT(NS, KL) _Pragma("unroll") for (int e = 0; e < NS; ++e) _Pragma("unroll") for (int m = 0; m < KL; ++m)
+
+// Stages 1-4 for NS consecutive samples over the lane's first KL slots: upsampled increment fl32(fma(w0,x[i0],fl32(w1*x[i1]))),
+// widened, added to the fp64 accumulator (:41); d gets the running phases.  Only the accumulate is carried from sample to sample.
+template <int NS, int KL, int K>
+__device__ __forceinline__ void phase_chain(const float (&w0)[NS], const float (&w1)[NS], const float (&x0)[K], const float (&x1)[K],
+                                            double (&acc)[K], double (&d)[NS][KL])
+{
+    float v[NS][KL];
+    DDSP_EACH_SLOT(NS, KL) v[e][m] = w1[e] * x1[m];
+    DDSP_STAGE_END();
+    DDSP_EACH_SLOT(NS, KL) v[e][m] = __fmaf_rn(w0[e], x0[m], v[e][m]);
+    DDSP_STAGE_END();
+    DDSP_EACH_SLOT(NS, KL) d[e][m] = (double)v[e][m];
+    DDSP_STAGE_END();
+    DDSP_EACH_SLOT(NS, KL) {
+        acc[m] += d[e][m];
+        d[e][m] = acc[m];
+    }
+    DDSP_STAGE_END();
+}
+
+// Fast modulo, in two parts: q = rint(P/2pi32) by the rounding magic, then v = P - q*2pi32 (:42), which is exact in fp32 for
+// q = rint(P/2pi32 +- 0.25) < 2^21: r in (-4.8, 4.8).  Taking the nearest multiple instead of the floor changes sin(r) by
+// <= |2pi32 - 2pi| = 1.75e-7.
+// A walk may keep the quotients of one sample and skip phase_quotient on the next (a wave-uniform choice): below Nyquist the
+// phase advanced by at most pi since then, so r stays in (-pi, 2 pi] -- still a multiple of 2^-21 below 8, i.e. exact -- and
+// v_sin_f32 takes any argument within +-256 revolutions.  Saves the two rounding instructions every other sample.
+template <int NS, int KL>
+__device__ __forceinline__ void phase_quotient(const float (&v)[NS][KL], float (&q)[NS][KL])
+{
+    DDSP_EACH_SLOT(NS, KL) q[e][m] = __fmaf_rn(v[e][m], kInvTwoPi32, kRoundMagic);
+    DDSP_STAGE_END();
+    DDSP_EACH_SLOT(NS, KL) q[e][m] = q[e][m] - kRoundMagic;
+    DDSP_STAGE_END();
+}
+template <int NS, int KL>
+__device__ __forceinline__ void phase_remainder(float (&v)[NS][KL], const float (&q)[NS][KL])
+{
+    DDSP_EACH_SLOT(NS, KL) v[e][m] = __fmaf_rn(-q[e][m], kTwoPi32, v[e][m]);
+    DDSP_STAGE_END();
+}
+
+// sin of reduced phases: to revolutions, then v_sin_f32
+template <int NS, int KL>
+__device__ __forceinline__ void sin_of_phase(float (&v)[NS][KL])
+{
+    DDSP_EACH_SLOT(NS, KL) v[e][m] = v[e][m] * kRevPerRad;
+    DDSP_STAGE_END();
+    DDSP_EACH_SLOT(NS, KL) v[e][m] = __builtin_amdgcn_sinf(v[e][m]);
+    DDSP_STAGE_END();
+}
+
+// ---- frame prologue: what the frame-form synth kernel and the backward (which re-walks exactly its phases) decide alike ----
+// Both expand in the scope of a frame kernel and read its p, b, t, j, G, ia, ib, ic.  Macros, not functions: as __forceinline__
+// functions the same text compiled to other register allocations (6 more VGPRs in the EXACT synth kernels, 2 more spilled SGPRs in
+// osc_bwd_kernel<25, false>: profiles/osc_shared_chain_codegen.md).
+
+// st.acc = start phase of frame t = superblock prefix + local prefix; fast = the whole wavefront may take the fast modulo.
+// That needs 0 <= P < kFastPhaseLimit over the whole frame: increments of the three bracketing frames non-negative (phases
+// then grow monotonically) and the end-of-frame bound small.
+// (xmax: a quotient reused for the next sample leaves |r| <= pi + increment; v_sin_f32 wants |r| < 256 * 2 pi)
+#define DDSP_FRAME_START(K, st, fast)                                                                                          \
+    do {                                                                                                                       \
+        const int sb = t / (256 >> p.logG);                                                                                    \
+        fast = true;                                                                                                           \
+        const float *wb = p.w + (long)b * p.T * p.H;                                                                           \
+        _Pragma("unroll") for (int m = 0; m < K; ++m) {                                                                        \
+            const int h = j + m * G;                                                                                           \
+            st.acc[m] = 0.0;                                                                                                   \
+            if (h < p.H) {                                                                                                     \
+                st.acc[m] = p.loc[((long)b * p.T + t) * p.H + h] + p.sup[((long)b * p.NSB + sb) * p.H + h];                    \
+                const float xa = wb[(long)ia * p.H + h], xb = wb[(long)ib * p.H + h], xc = wb[(long)ic * p.H + h];             \
+                const float xmax = fmaxf(fmaxf(xa, xb), xc);                                                                   \
+                const float bound = (float)st.acc[m] + (float)p.R * xmax * 1.0001f;                                            \
+                fast = fast && (xa >= 0.0f) && (xb >= 0.0f) && (xc >= 0.0f) && (st.acc[m] >= 0.0) && (bound < kFastPhaseLimit) && \
+                       (xmax < 1024.0f);                                                                                       \
+            }                                                                                                                  \
+        }                                                                                                                      \
+        fast = __all(fast); /* wave-uniform */                                                                                 \
+    } while (0)
+
+// mlive = slots to walk: harmonics above Nyquist at all three bracketing frames (:31-32, strict >) are silent for the whole frame
+// and their phase is not needed either (every frame starts from the scanned totals), so a walk may stop at the highest slot that
+// is audible anywhere in the wavefront.  From f0 (three loads) instead of the 3 x K amplitudes themselves (39 loads and their
+// addresses: the registers this spilled).  Zero amplitudes BELOW Nyquist are simply walked; NaN f0 compares false -> kept; an
+// all-masked frame (NaN amplitudes, :33) still reaches the output through slot 0, which every walk includes.
+#define DDSP_AUDIBLE_SLOTS(K, mlive)                                                                                           \
+    do {                                                                                                                       \
+        mlive = 0;                                                                                                             \
+        const long rowbase = (long)b * p.T;                                                                                    \
+        const float fmin3 = fminf(fminf(p.f0[rowbase + ia], p.f0[rowbase + ib]), p.f0[rowbase + ic]);                          \
+        _Pragma("unroll") for (int m = 0; m < K; ++m) {                                                                        \
+            const int h = j + m * G;                                                                                           \
+            const bool keep = h < p.H && !((float)(h + 1) * fmin3 > p.nyquist);                                                \
+            if (__any(keep)) mlive = m + 1;                                                                                    \
+        }                                                                                                                      \
+    } while (0)
 
 
 // ---- host side (defined in ddsp_osc.hip) ---------------------------------------------------------------

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 namespace ddsp_osc {
@@ -22,27 +23,52 @@ constexpr int kPlanParents = 7;         // root slots that may feed derived ones
 constexpr int kPlanMaxChildren = 3;     // derived slots per root slot
 constexpr uint16_t kNoHarmonic = 0xffff;
 
+// THE list of K -- harmonics per lane, a template parameter of every oscillator kernel -- with, per K, the derived slots fed by
+// root slots 0..6.  Everything that enumerates K derives from it: kOscKs, dispatch_k, slot_children.  The children are
+// non-increasing in the root slot: small harmonics have the long families.  Found by exhaustive search over the shapes with the
+// most derived slots that pack every (H, K, G) the tilings select (tests/test_osc_slot_plan_host.py).
+#define DDSP_OSC_KS(X)                                                                                                  \
+    X(4, 1, 0, 0, 0, 0, 0, 0) X(8, 2, 1, 0, 0, 0, 0, 0) X(12, 3, 2, 1, 0, 0, 0, 0) X(13, 3, 2, 1, 0, 0, 0, 0)         \
+    X(15, 3, 2, 1, 1, 0, 0, 0) X(16, 3, 2, 1, 1, 0, 0, 0) X(20, 3, 2, 2, 1, 1, 0, 0) X(23, 3, 2, 2, 1, 1, 1, 0)       \
+    X(25, 3, 2, 2, 1, 1, 1, 1)
+
+#define DDSP_K_VALUE(KK, ...) KK,
+constexpr int kOscKs[] = {DDSP_OSC_KS(DDSP_K_VALUE)};
+#undef DDSP_K_VALUE
+
+// f(std::integral_constant<int, K>{}) for a listed K, `unknown` for any other
+template <class F, class R>
+R dispatch_k(int K, F &&f, R unknown)
+{
+    switch (K) {
+#define DDSP_K_CASE(KK, ...) case KK: return f(std::integral_constant<int, KK>{});
+        DDSP_OSC_KS(DDSP_K_CASE)
+#undef DDSP_K_CASE
+        default: return unknown;
+    }
+}
+
 constexpr int pick7(int i, int a, int b, int c, int d, int e, int f, int g)
 {
     return i == 0 ? a : i == 1 ? b : i == 2 ? c : i == 3 ? d : i == 4 ? e : i == 5 ? f : i == 6 ? g : 0;
 }
-// Derived slots fed by root slot i.  Non-increasing in i: small harmonics have the long families.  Found by exhaustive
-// search over the shapes with the most derived slots that pack every (H, K, G) the tilings select (tests/test_osc_slot_plan_host.py).
+// Derived slots fed by root slot i.
 constexpr int slot_children(int K, int i)
 {
     switch (K) {
-        case 4: return pick7(i, 1, 0, 0, 0, 0, 0, 0);
-        case 8: return pick7(i, 2, 1, 0, 0, 0, 0, 0);
-        case 12: return pick7(i, 3, 2, 1, 0, 0, 0, 0);
-        case 13: return pick7(i, 3, 2, 1, 0, 0, 0, 0);
-        case 15: return pick7(i, 3, 2, 1, 1, 0, 0, 0);
-        case 16: return pick7(i, 3, 2, 1, 1, 0, 0, 0);
-        case 20: return pick7(i, 3, 2, 2, 1, 1, 0, 0);
-        case 23: return pick7(i, 3, 2, 2, 1, 1, 1, 0);
-        case 25: return pick7(i, 3, 2, 2, 1, 1, 1, 1);
+#define DDSP_K_CHILDREN(KK, ...) case KK: return pick7(i, __VA_ARGS__);
+        DDSP_OSC_KS(DDSP_K_CHILDREN)
+#undef DDSP_K_CHILDREN
         default: return 0;
     }
 }
+constexpr bool plan_covers_every_k()
+{
+    for (int K : kOscKs)
+        if (K > kPlanMaxK || slot_children(K, 0) < 1) return false;
+    return true;
+}
+static_assert(plan_covers_every_k(), "every listed K needs a slot_children shape and kPlanMaxK must bound it");
 constexpr int plan_derived(int K)
 {
     int n = 0;

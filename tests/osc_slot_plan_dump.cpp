@@ -1,5 +1,6 @@
 // Prints the chunked oscillator's slot plans as text for tests/test_osc_slot_plan_host.py:
 //   usage: osc_slot_plan_dump H K G ...   (triples)
+//   ks K ...                                     first line: the list of K the kernels are instantiated for (kOscKs)
 //   plan H K G ok KR KD cls0 cls1 cls2 cls3      then one line per lane: "lane j : h/shift ..." (h 1-based, 0 = padding)
 //   parents K : parent of each derived slot
 #include <stdio.h>
@@ -10,6 +11,9 @@
 int main(int argc, char **argv)
 {
     using namespace ddsp_osc;
+    printf("ks");
+    for (int K : kOscKs) printf(" %d", K);
+    printf("\n");
     for (int a = 1; a + 2 < argc; a += 3) {
         const int H = atoi(argv[a]), K = atoi(argv[a + 1]), G = atoi(argv[a + 2]);
         SlotPlan pl;

@@ -7,7 +7,7 @@ every lane of every plan.  For every K that has derived slots x G in {4, 8, 16} 
 (amplitude 0) are counted, not checked: they carry shift 0 in the table and the kernels keep them out of their range tests.
 
 The plan header is plain C++; the test compiles tests/osc_plan_shift_check.cpp against it, as test_osc_slot_plan_host.py does
-with its dump program.
+with its dump program -- which is also where the list of K comes from (its first line).
 """
 import os
 import shutil
@@ -16,7 +16,6 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KS = (4, 8, 12, 13, 15, 16, 20, 23, 25)         # the K of slot_children (csrc/ddsp_osc.hip: kKs)
 HMAX = 400
 # slot_children per K, written out again here: derived slots are numbered root slot by root slot, child r of a root has t = r + 1
 CHILDREN = {4: (1,), 8: (2, 1), 12: (3, 2, 1), 13: (3, 2, 1), 15: (3, 2, 1, 1), 16: (3, 2, 1, 1), 20: (3, 2, 2, 1, 1),
@@ -29,9 +28,14 @@ def report(tmp_path_factory):
     if cxx is None and os.path.exists("/opt/rocm/llvm/bin/clang++"):
         cxx = "/opt/rocm/llvm/bin/clang++"
     assert cxx, "a host C++ compiler is needed to read the slot plans"
-    exe = str(tmp_path_factory.mktemp("shift") / "osc_plan_shift_check")
-    subprocess.run([cxx, "-std=c++17", "-O2", "-I", os.path.join(ROOT, "ddsp-pytorch_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "osc_plan_shift_check.cpp"), "-o", exe], check=True)
+    tmp = tmp_path_factory.mktemp("shift")
+    exe, dump = str(tmp / "osc_plan_shift_check"), str(tmp / "osc_slot_plan_dump")
+    for out, opt in ((exe, "-O2"), (dump, "-O0")):
+        subprocess.run([cxx, "-std=c++17", opt, "-I", os.path.join(ROOT, "ddsp-pytorch_amd", "csrc"),
+                        os.path.join(ROOT, "tests", os.path.basename(out) + ".cpp"), "-o", out], check=True)
+    first = subprocess.run([dump], check=True, capture_output=True, text=True).stdout.split()
+    assert first[0] == "ks"
+    KS = tuple(int(v) for v in first[1:])
     # (one process per K, side by side: the planner's search over 1 200 shapes per K is what takes the time)
     procs = [subprocess.Popen([exe, str(HMAX), str(k)], stdout=subprocess.PIPE, text=True) for k in KS]
     txt = []
@@ -48,11 +52,11 @@ def report(tmp_path_factory):
             shifts[int(w[1])] = [int(v) for v in w[3:]]
         else:
             bad.append(line)
-    return per_k, shifts, bad
+    return per_k, shifts, bad, KS
 
 
 def test_every_filled_derived_slot_has_the_compile_time_shift(report):
-    per_k, _, bad = report
+    per_k, _, bad, KS = report
     assert sorted(per_k) == sorted(KS)
     assert not bad, bad[:10]
     for K in KS:
@@ -64,7 +68,8 @@ def test_every_filled_derived_slot_has_the_compile_time_shift(report):
 
 
 def test_derived_shift_is_rank_plus_one(report):
-    _, shifts, _ = report
+    _, shifts, _, KS = report
+    assert sorted(KS) == sorted(CHILDREN)
     for K in KS:
         want = [r + 1 for n in CHILDREN[K] for r in range(n)]
         assert shifts[K] == want, (K, shifts[K], want)

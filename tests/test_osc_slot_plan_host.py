@@ -18,7 +18,6 @@ import pytest
 from oracle import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KS = (4, 8, 12, 13, 15, 16, 20, 23, 25)         # csrc/ddsp_osc.hip: kKs
 
 
 def bits(x):
@@ -77,10 +76,10 @@ def test_even_harmonics_double_in_the_oracle(kind, H, hop, sr):
 
 
 # ---- the planner ------------------------------------------------------------------------------------------------------
-def selectable():
+def selectable(ks):
     """(H, K, G) the chunked form can be launched with: pick_tiling's G for every K, 4..16 lanes per row."""
     out = []
-    for K in KS:
+    for K in ks:
         for H in range(1, 401):
             lanes = -(-H // K)
             G = 1
@@ -109,6 +108,8 @@ def plans(tmp_path_factory):
             cur = None
             for line in txt:
                 w = line.split()
+                if w[0] == "ks":
+                    continue
                 if w[0] == "plan":
                     H, K, G, ok, KR, KD = (int(v) for v in w[1:7])
                     cur = dict(H=H, K=K, G=G, ok=ok, KR=KR, KD=KD, cls=[int(v) for v in w[7:11]], lanes=[], parents=[])
@@ -118,6 +119,9 @@ def plans(tmp_path_factory):
                 else:
                     cur["lanes"].append([tuple(int(v) for v in s.split("/")) for s in w[3:]])
         return res
+    first = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
+    assert first[0] == "ks"
+    get.ks = tuple(int(v) for v in first[1:])           # the list of K (csrc/ddsp_osc_plan.h: DDSP_OSC_KS)
     return get
 
 
@@ -155,8 +159,12 @@ def check_plan(p):
     assert p["cls"] == sorted(p["cls"], reverse=True)
 
 
+def test_the_list_of_k(plans):
+    assert plans.ks == (4, 8, 12, 13, 15, 16, 20, 23, 25)
+
+
 def test_planner_properties_for_every_selectable_shape(plans):
-    triples = selectable()
+    triples = selectable(plans.ks)
     got = plans(triples)
     assert len(got) == len(triples) > 1000
     for t in triples:
