@@ -44,6 +44,9 @@ SIGNATURES = {
     "ddsp_noise_workspace_bytes": (_size, [_i32, _i32, _i32, _i32]),
     "ddsp_noise_forward_ws": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _i32, _vp, _size, _vp]),
     "ddsp_noise_backward_ws": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _size, _vp]),
+    "ddsp_noise_ola_workspace_bytes": (_size, [_i32, _i32, _i32, _i32]),
+    "ddsp_noise_ola_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _i32, _vp, _size, _vp]),
+    "ddsp_noise_ola_backward": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _size, _vp]),
     "ddsp_osc_backward_scratch_bytes": (_size, [_i32, _i32, _i32]),
     "ddsp_osc_backward": (_i32, [_vp] * 8 + [_i32] * 5 + [_vp]),
     "ddsp_osc_set_tiling": (_i32, [_i32]),

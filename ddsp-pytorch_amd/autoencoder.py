@@ -26,10 +26,10 @@ from .encoder import Encoder
 
 
 class AutoEncoder(nn.Module):
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None, noise_overlap_add=None):
         super().__init__()
         self.encoder = Encoder(conf, weights, voicing=voicing, tracker=tracker)
-        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed)
+        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed, noise_overlap_add=noise_overlap_add)
         self.padding = conf.n_fft - conf.hop_length
         self.hop_length = conf.hop_length
         self.n_noise_filters = conf.n_noise_filters
@@ -47,6 +47,9 @@ class AutoEncoder(nn.Module):
         noise=True adds 'H' [B, T, n_noise_filters]: analysis.noise_analysis (with `average` and `iterations`) of the residual
         analysis.harmonic_residual leaves, so that `self.decoder.synthesize(self.analyse(x, noise=True))` is the parametric
         harmonic-plus-noise resynthesis of x."""
+        if noise and self.decoder.noise.overlap_add:
+            # noise_analysis inverts the truncated model: its H played through the overlap-add would come out too strong
+            raise ValueError("analyse(noise=True) inverts the truncated noise model; it does not apply to a decoder with noise_overlap_add")
         bank = self.decoder.harmonics
         with torch.no_grad():
             z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))

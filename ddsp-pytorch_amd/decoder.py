@@ -348,11 +348,11 @@ class Controller(nn.Module):
 class Decoder(nn.Module):
     """controller -> harmonics + noise -> reverb (decoder.py:119-147), all on the device."""
 
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None):
         super().__init__()
         self.controller = Controller(conf)
         self.harmonics = OscillatorBank(conf)
-        self.noise = FilteredNoise(conf, rng=noise_rng, seed=seed)
+        self.noise = FilteredNoise(conf, rng=noise_rng, seed=seed, overlap_add=noise_overlap_add)
         self.reverb = Reverb(conf)
 
     def synthesize(self, ctrl, live: bool = False):
@@ -367,6 +367,9 @@ class Decoder(nn.Module):
         return self.reverb(self.synthesize(self.controller(z)))
 
     def forward_live(self, z, hidden):
+        if self.noise.overlap_add:
+            # a callback's block would lose the M/2 samples its frames spread into the neighbouring blocks
+            raise ValueError("forward_live does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
         ctrl, hidden = self.controller(z, hidden)
         audio = self.reverb.live_forward(self.synthesize(ctrl, live=True))
         return audio.cpu().squeeze(0).numpy(), hidden   # one D2H per callback (rt/synth.py:50-52)

@@ -13,8 +13,10 @@ import torch.nn as nn
 from . import _lib
 
 
-def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, out=None, accumulate=False, counter=None):
-    """Raw launcher over the C ABI (include/ddsp_hip.h: ddsp_noise_forward_ws).
+def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, out=None, accumulate=False, counter=None,
+                  overlap_add: bool = False):
+    """Raw launcher over the C ABI (include/ddsp_hip.h: ddsp_noise_forward_ws; overlap_add=True: ddsp_noise_ola_forward, every
+    frame's whole impulse response overlap-added instead of the reference's first `hop` samples -- same draw, same arguments).
     `counter`: a 1-element int64 CUDA tensor added to `offset` to give the Philox offset of the in-kernel draw (read on the
     device at launch time, so a captured launch draws from wherever the counter stands at each replay); excludes `uniform`."""
     if Hmag.dim() != 3:
@@ -38,6 +40,8 @@ def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, 
         raise ValueError("counter must be a 1-element int64 CUDA tensor and excludes an injected draw")
     with torch.cuda.device(Hmag.device):
         stream = torch.cuda.current_stream().cuda_stream
+        if overlap_add:
+            return _ola_forward(Hmag, uniform, out, B, T, F, hop, seed, offset, counter, accumulate, stream)
         # (the reference's default shape: impulse responses of the whole batch as one matrix-core product, include/ddsp_hip.h)
         ws_bytes = _lib.lib().ddsp_noise_workspace_bytes(B, T, F, hop)
         ws = torch.empty(ws_bytes, device=Hmag.device, dtype=torch.uint8) if ws_bytes else None
@@ -48,8 +52,25 @@ def noise_forward(Hmag, hop: int, uniform=None, seed: int = 0, offset: int = 0, 
     return out
 
 
-def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0, offset: int = 0, counter=None):
-    """Raw launcher of ddsp_noise_backward_ws: grad_y [B,T*hop] -> grad_H [B,T,F] for the same draw as the forward
+def _ola_workspace(B, T, F, hop, device):
+    """The overlap-add form's workspace (required).  A size of 0 is a shape outside the range: the call itself then reports it."""
+    ws_bytes = _lib.lib().ddsp_noise_ola_workspace_bytes(B, T, F, hop)
+    return torch.empty(max(ws_bytes, 4), device=device, dtype=torch.uint8), ws_bytes
+
+
+def _ola_forward(Hmag, uniform, out, B, T, F, hop, seed, offset, counter, accumulate, stream):
+    ws, ws_bytes = _ola_workspace(B, T, F, hop, Hmag.device)
+    rc = _lib.lib().ddsp_noise_ola_forward(Hmag.data_ptr(), None if uniform is None else uniform.data_ptr(), out.data_ptr(),
+                                           B, T, F, hop, seed, offset, None if counter is None else counter.data_ptr(),
+                                           1 if accumulate else 0, ws.data_ptr(), ws_bytes, stream)
+    _lib.check(rc, "ddsp_noise_ola_forward")
+    return out
+
+
+def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0, offset: int = 0, counter=None,
+                   overlap_add: bool = False):
+    """Raw launcher of ddsp_noise_backward_ws (overlap_add=True: ddsp_noise_ola_backward, the gradient of that form):
+    grad_y [B,T*hop] -> grad_H [B,T,F] for the same draw as the forward
     (`counter`: the device counter the forward read, still at the same value).  Checked before any launch, as noise_forward
     checks its arguments: the kernels read B*T*hop samples of grad_y and uniform."""
     if grad_y.dim() != 2 or hop <= 0 or grad_y.shape[1] % hop != 0:
@@ -73,6 +94,13 @@ def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0
         return grad_h
     with torch.cuda.device(grad_y.device):
         stream = torch.cuda.current_stream().cuda_stream
+        if overlap_add:
+            ws, ws_bytes = _ola_workspace(B, T, n_filters, hop, grad_y.device)
+            rc = _lib.lib().ddsp_noise_ola_backward(grad_y.data_ptr(), None if uniform is None else uniform.data_ptr(), grad_h.data_ptr(),
+                                                    B, T, n_filters, hop, seed, offset, None if counter is None else counter.data_ptr(),
+                                                    ws.data_ptr(), ws_bytes, stream)
+            _lib.check(rc, "ddsp_noise_ola_backward")
+            return grad_h
         ws_bytes = _lib.lib().ddsp_noise_workspace_bytes(B, T, n_filters, hop)
         ws = torch.empty(ws_bytes, device=grad_y.device, dtype=torch.uint8) if ws_bytes else None
         rc = _lib.lib().ddsp_noise_backward_ws(grad_y.data_ptr(), None if uniform is None else uniform.data_ptr(), grad_h.data_ptr(),
@@ -135,27 +163,31 @@ class _NoiseFunction(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, Hmag, uniform, hop, seed, offset, counter=None):
+    def forward(ctx, Hmag, uniform, hop, seed, offset, counter=None, overlap_add=False):
         if uniform is not None:
             uniform = uniform.detach().to(device=Hmag.device, dtype=torch.float32).contiguous()
-        y = noise_forward(Hmag, hop, uniform=uniform, seed=seed, offset=offset, counter=counter)
+        y = noise_forward(Hmag, hop, uniform=uniform, seed=seed, offset=offset, counter=counter, overlap_add=overlap_add)
         ctx.save_for_backward(uniform)
         ctx.counter = counter        # read again by the backward: the owner advances it only after that (GraphedTrainStep)
-        ctx.meta = (hop, Hmag.shape[-1], seed, offset)
+        ctx.meta = (hop, Hmag.shape[-1], seed, offset, bool(overlap_add))
         return y
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_y):
         (uniform,) = ctx.saved_tensors
-        hop, nf, seed, offset = ctx.meta
-        return noise_backward(grad_y, hop, nf, uniform=uniform, seed=seed, offset=offset, counter=ctx.counter), None, None, None, None, None
+        hop, nf, seed, offset, overlap_add = ctx.meta
+        return (noise_backward(grad_y, hop, nf, uniform=uniform, seed=seed, offset=offset, counter=ctx.counter, overlap_add=overlap_add),
+                None, None, None, None, None, None)
 
 
 class FilteredNoise(nn.Module):
-    def __init__(self, conf, rng: str = 'host', seed: int = 0):
+    def __init__(self, conf, rng: str = 'host', seed: int = 0, overlap_add=None):
+        """`overlap_add` (None: `conf.noise_overlap_add`, False where the configuration has none): every frame's whole impulse
+        response is overlap-added instead of the reference's first `hop` samples per frame."""
         super().__init__()
         self.block_size = conf.hop_length
+        self.overlap_add = bool(getattr(conf, 'noise_overlap_add', False) if overlap_add is None else overlap_add)
         if rng not in ('host', 'device'):
             raise ValueError("rng must be 'host' (torch CPU generator, reference-compatible) or 'device' (Philox)")
         self.rng = rng
@@ -191,9 +223,9 @@ class FilteredNoise(nn.Module):
         if torch.is_grad_enabled() and param.requires_grad:
             if not param.is_cuda:
                 raise _lib.DdspHipError("FilteredNoise runs on the GPU only (no CPU fallback): move the controls to cuda")
-            return _NoiseFunction.apply(param, noise, self.block_size, self.seed, offset, counter)
+            return _NoiseFunction.apply(param, noise, self.block_size, self.seed, offset, counter, self.overlap_add)
         return noise_forward(param, self.block_size, uniform=noise, seed=self.seed, offset=offset, out=out,
-                             accumulate=out is not None, counter=counter)
+                             accumulate=out is not None, counter=counter, overlap_add=self.overlap_add)
 
     def draws(self, batch: int, frames: int) -> int:
         """Philox counters one in-kernel draw of this shape consumes."""

@@ -30,6 +30,9 @@ class GraphedSynth:
         self.H = torch.ones((batch, frames, n_noise_filters), device=dev)
         self.state = torch.zeros(H, device=dev)           # last_phases (fp32, as after the reference's first live call)
         self.seed = noise_seed
+        self.overlap_add = bool(getattr(conf, 'noise_overlap_add', False))
+        if live and self.overlap_add:
+            raise ValueError("the live pass does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
         self._step = torch.zeros(1, dtype=torch.int64, device=dev)     # Philox offset of the next call's draw
         self._draws_per_call = batch * frames * ((conf.hop_length + 3) // 4)
         self.out = None
@@ -45,7 +48,7 @@ class GraphedSynth:
             y, _, _ = osc_forward(self.f0, self.c, self.a, self.hop, self.sample_rate)
         # the Philox offset of the draw lives on the device and advances inside the graph: every replay is fresh noise,
         # the same sequence as un-captured calls with offset = call index x draws per call
-        y = noise_forward(self.H, self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step)
+        y = noise_forward(self.H, self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step, overlap_add=self.overlap_add)
         self._step.add_(self._draws_per_call)
         return y
 
@@ -88,6 +91,8 @@ class GraphedLiveDecoder:
     """
 
     def __init__(self, decoder, frames: int, noise_seed: int = 0, carry_hidden: bool = False):
+        if decoder.noise.overlap_add:
+            raise ValueError("the live decoder does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
         self.dec = decoder.eval()
         dev = next(decoder.parameters()).device
         if dev.type != "cuda":

@@ -109,6 +109,36 @@ int ddsp_noise_backward_ws(const float *grad_y, const float *uniform, float *gra
                            uint64_t offset, const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Filtered noise with overlap-add (csrc/ddsp_noise_ola.hip): an opt-in beside the reference's truncated
+ * form above, chosen by the caller.  Same arguments, same draw (uniform, or seed / offset / counter_dev with the counter rule
+ * offset + *counter_dev + frame ceil(hop / 4) + quad, frame = b T + t), so one (seed, offset) gives both forms the same samples.
+ * With M = 2 (F - 1), N = T hop:
+ *   1. x[b, t hop + j] = fl32(2 u[b, t, j] - 1).
+ *   2. h_t[e] = (1/2 + 1/2 cos(2 pi e / M)) (1/M) sum_{k<F} c_k H_t[k] cos(2 pi k e / M) for e in [-M/2, M/2), c_0 = c_{F-1} = 1,
+ *      c_k = 2 otherwise: the windowed zero-phase response before the reference pads or crops it.  h_t[-M/2] = 0 by its window
+ *      weight; that tap is never evaluated.  h_t is even over the others.
+ *   3. y[b, n] = sum_e h_{floor((n - e) / hop)}[e] x[b, n - e] over the e with 0 <= n - e < N: every noise sample is filtered by
+ *      the response of its own frame, and each frame's hop + M - 1 samples are overlap-added at their place.  Frames outside the
+ *      clip contribute nothing.  accumulate != 0: y += noise, bit-equal to adding the plain result to y in fp32.
+ *   4. Backward (the draw is a constant; g = grad_y, 0 outside [0, N)): q_t[e] = sum_{j<hop} x[t hop + j] g[t hop + j + e],
+ *      grad_H[t, k] = (c_k / M) sum_e (1/2 + 1/2 cos(2 pi e / M)) cos(2 pi k e / M) q_t[e].
+ *   5. A non-finite H_t reaches the samples [t hop - M/2 + 1, (t + 1) hop + M/2 - 2] of its row inside [0, N) and nothing else;
+ *      a non-finite g[n] reaches the frames t with n in that interval.
+ * Every output is one chain of fp32 multiply-adds in a fixed order (y over ascending source sample, q over ascending j), so a
+ * row's bits depend neither on the batch nor on the run.  No float atomics, nothing allocated or synchronised: two launches each
+ * way.  workspace: ddsp_noise_ola_workspace_bytes(B, T, F, hop) bytes (the responses, or the folded correlations, of every
+ * frame), required; the pointers need 4-byte alignment only.  Range: 2 <= F <= 257, 1 <= hop <= 1024, B T <= 2^31 - 1 and
+ * T hop < 2^31 - 8192, DDSP_ERANGE beyond (the size query then returns 0); a null pointer, a size that is not positive or a
+ * workspace that is too small is DDSP_EINVAL before anything touches the device; B == 0 returns 0.
+ */
+size_t ddsp_noise_ola_workspace_bytes(int B, int T, int F, int hop);
+int ddsp_noise_ola_forward(const float *Hmag, const float *uniform, float *y, int B, int T, int F, int hop, uint64_t seed,
+                           uint64_t offset, const uint64_t *counter_dev, int accumulate, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int ddsp_noise_ola_backward(const float *grad_y, const float *uniform, float *grad_H, int B, int T, int F, int hop, uint64_t seed,
+                            uint64_t offset, const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Backward of ddsp_osc_forward_ex w.r.t. c and a (autograd of harmonic_oscillator.py:24-62; f0 carries no gradient,
  * decoder.py:105).  `fwd_scratch` is the scratch buffer the matching ddsp_osc_forward_ex call filled with
  * DDSP_OSC_KEEP_FRAME_SCRATCH (same B,T,H,hop, sample_rate, same tiling); `bwd_scratch` >= ddsp_osc_backward_scratch_bytes(B,T,H).
