@@ -47,6 +47,8 @@ SIGNATURES = {
     "ddsp_noise_ola_workspace_bytes": (_size, [_i32, _i32, _i32, _i32]),
     "ddsp_noise_ola_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _i32, _vp, _size, _vp]),
     "ddsp_noise_ola_backward": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _size, _vp]),
+    "ddsp_noise_ola_stream_state_floats": (_size, [_i32]),
+    "ddsp_noise_ola_stream": (_i32, [_vp] * 6 + [_i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _size, _vp]),
     "ddsp_osc_backward_scratch_bytes": (_size, [_i32, _i32, _i32]),
     "ddsp_osc_backward": (_i32, [_vp] * 8 + [_i32] * 5 + [_vp]),
     "ddsp_osc_set_tiling": (_i32, [_i32]),

@@ -4,7 +4,8 @@
                              and the CREPE frames line up with the decoder's hop grid (autoencoder.py:17-22)
   analyse(x, noise=False)    the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True,
                              H by noise analysis of the residual (analysis.py)
-  forward_live(x, hidden)    the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
+  forward_live(x, hidden, delayed=False)
+                             the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
                              encoder, then Decoder.forward_live -> (audio as numpy, hidden)
 
@@ -71,6 +72,8 @@ class AutoEncoder(nn.Module):
         audio_in = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).unsqueeze(0).to(device, non_blocking=False)
         return audio_in[:, self.hop_length // 2:-(self.hop_length - self.hop_length // 2)]
 
-    def forward_live(self, x: np.ndarray, hidden: torch.Tensor):
+    def forward_live(self, x: np.ndarray, hidden: torch.Tensor, delayed: bool = False):
+        """`delayed`: Decoder.forward_live's (the overlap-add noise as a stream, the audio n_noise_filters - 2 samples late)."""
+        self.decoder.check_live(delayed, "forward_live")
         z = self.encoder(self.live_window(x))
-        return self.decoder.forward_live(z, hidden)
+        return self.decoder.forward_live(z, hidden, delayed=delayed)

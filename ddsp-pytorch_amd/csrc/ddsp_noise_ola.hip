@@ -14,6 +14,8 @@
 //   backward  ola_corr     one workgroup per (row, group of frames); a thread owns 8 consecutive lags and walks j in ascending blocks
 //                          of 8 (same register block); lags folded onto d = |e| and windowed -> Gs [frames][P] in the workspace
 //             cos_sum<PROJ> Gs -> dH [frames][F]
+//   stream    cos_sum<IR>, then ola_stream: ola_conv's tiles and chains over one block of frames, each chain started from the tail the
+//             earlier blocks left and stored to the output (with the delayed dry signal) or to the new tail
 // Orders (each output is ONE chain of fp32 FMAs from 0): y[n] over m ascending; q_t[e] over j ascending; the cosine sums over the
 // inner index 1 .. P - 1 ascending, then the edge terms.  None depends on the batch, the tile or the run.
 #include <hip/hip_runtime.h>
@@ -158,51 +160,23 @@ __device__ __forceinline__ void stage_draw(float *xs, const OlaDraw &d, long row
     }
 }
 
-// ---- forward: the convolution --------------------------------------------------------------------------------------------------------
-struct OlaConvParams {
-    const float *hh;              // [B T][P]
-    float *y;                     // [B][T hop]
-    OlaDraw draw;
-    int T, F, hop, accumulate;
-    int rows_cap;                 // HLDS: response rows the LDS was sized for
-};
-
-// HLDS: the responses of the frames a tile touches are staged in LDS as zero-padded even rows.  Otherwise (small hops with many
-// bands: the rows do not fit) every tap is read from the workspace; same chains, same bits.
-template <bool HLDS>
-__global__ void __launch_bounds__(kThreads) ola_conv_kernel(OlaConvParams p)
+// rows[r][e + C] = h_{fa + r}[e] for e in [-C, Pa + 8), zero for |e| >= P: the even rows the fast path of ola_chains reads
+__device__ __forceinline__ void stage_rows(float *rows, const float *hrow0, const OlaGeom &g, int fa, int nrows)
 {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const OlaGeom g = ola_geom(p.F);
-    const int hop = p.hop, T = p.T, N = T * hop, P = g.P;
-    const int tid = threadIdx.x;
-    const int tiles = (N + kTile - 1) / kTile;
-    const long row = blockIdx.x / tiles;
-    const int tile0 = (int)(blockIdx.x - row * tiles) * kTile;
-    const int xfirst = tile0 - g.Pa, xcount = kTile + g.Pa + g.Pb + 8;
-    float *xs = smem;                                   // [xcount] (a multiple of 8)
-    float *rows = xs + xcount;                          // HLDS: [nrows][RS]
-    const int fa = max(xfirst, 0) / hop;
-    const int fb = min(min(xfirst + xcount, N) - 1, N - 1) / hop;
-    const float *hrow0 = p.hh + row * (long)T * P;
+    for (int r = 0; r < nrows; ++r)
+        for (int q = threadIdx.x; q < g.LEN; q += kThreads) {
+            const int e = abs(q - g.C);
+            rows[r * g.RS + q] = e < g.P ? hrow0[(long)(fa + r) * g.P + e] : 0.0f;
+        }
+}
 
-    stage_draw(xs, p.draw, row, T, hop, xfirst, xcount, fa, fb);
-    if (HLDS) {
-        const int nrows = min(fb - fa + 1, p.rows_cap);
-        for (int r = 0; r < nrows; ++r)
-            for (int q = tid; q < g.LEN; q += kThreads) {
-                const int e = abs(q - g.C);
-                rows[r * g.RS + q] = e < P ? hrow0[(long)(fa + r) * P + e] : 0.0f;
-            }
-    }
-    __syncthreads();
-
-    const int n0 = tile0 + 8 * tid;
-    if (n0 >= N) return;
-    float acc[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] = 0.0f;
-
+// The chains of a thread's 8 outputs n0 .. n0 + 7 (n0 a multiple of 8, possibly negative) over the sources m in [0, N), ascending, on top
+// of what acc holds.  xs[i] = x[xfirst + i]; fa: the frame of max(xfirst, 0), the first staged response row.
+template <bool HLDS>
+__device__ __forceinline__ void ola_chains(float (&acc)[8], const float *xs, const float *rows, const float *hrow0, const OlaGeom &g,
+                                           int n0, int xfirst, int fa, int hop, int N)
+{
+    const int P = g.P;
     int f = fa, fnext = (fa + 1) * hop;                 // the frame of max(m0, 0), kept by stepping
     const int nblocks = (g.Pa + g.Pb) / 8 + 1;
     for (int j = 0; j < nblocks; ++j) {
@@ -248,10 +222,114 @@ __global__ void __launch_bounds__(kThreads) ola_conv_kernel(OlaConvParams p)
             }
         }
     }
+}
+
+// ---- forward: the convolution --------------------------------------------------------------------------------------------------------
+struct OlaConvParams {
+    const float *hh;              // [B T][P]
+    float *y;                     // [B][T hop]
+    OlaDraw draw;
+    int T, F, hop, accumulate;
+    int rows_cap;                 // HLDS: response rows the LDS was sized for
+};
+
+// HLDS: the responses of the frames a tile touches are staged in LDS as zero-padded even rows.  Otherwise (small hops with many
+// bands: the rows do not fit) every tap is read from the workspace; same chains, same bits.
+template <bool HLDS>
+__global__ void __launch_bounds__(kThreads) ola_conv_kernel(OlaConvParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const OlaGeom g = ola_geom(p.F);
+    const int hop = p.hop, T = p.T, N = T * hop, P = g.P;
+    const int tid = threadIdx.x;
+    const int tiles = (N + kTile - 1) / kTile;
+    const long row = blockIdx.x / tiles;
+    const int tile0 = (int)(blockIdx.x - row * tiles) * kTile;
+    const int xfirst = tile0 - g.Pa, xcount = kTile + g.Pa + g.Pb + 8;
+    float *xs = smem;                                   // [xcount] (a multiple of 8)
+    float *rows = xs + xcount;                          // HLDS: [nrows][RS]
+    const int fa = max(xfirst, 0) / hop;
+    const int fb = min(min(xfirst + xcount, N) - 1, N - 1) / hop;
+    const float *hrow0 = p.hh + row * (long)T * P;
+
+    stage_draw(xs, p.draw, row, T, hop, xfirst, xcount, fa, fb);
+    if (HLDS) stage_rows(rows, hrow0, g, fa, min(fb - fa + 1, p.rows_cap));
+    __syncthreads();
+
+    const int n0 = tile0 + 8 * tid;
+    if (n0 >= N) return;
+    float acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = 0.0f;
+    ola_chains<HLDS>(acc, xs, rows, hrow0, g, n0, xfirst, fa, hop, N);
     float *dst = p.y + row * (long)N + n0;
 #pragma unroll
     for (int u = 0; u < 8; ++u)
         if (n0 + u < N) dst[u] = p.accumulate ? dst[u] + acc[u] : acc[u];
+}
+
+// ---- the stream: one block of frames, D = P - 1 samples late, with a carried tail ----------------------------------------------------------
+// stream[i] = y[i - D] + dry[i - D] for i in [0, N) (include/ddsp_hip.h).  The block's sources m in [0, N) reach the outputs
+// n in [-D, N + P - 1), i.e. the stream samples i = n + D in [0, N + M - 2): the first N leave, the other M - 2 are the new tail.
+struct OlaStreamParams {
+    const float *hh;              // [B T][P]
+    const float *dry;             // [B][T hop] nullable
+    float *out;                   // [B][T hop]
+    const float *state_in;        // [B][3F - 6]: M - 2 of tail, then D of dry history (null when F == 2)
+    float *state_out;
+    OlaDraw draw;
+    int T, F, hop;
+    int rows_cap;
+};
+
+// ola_conv_kernel's tiles over n in [-Pa, N + P - 1): they start at a multiple of 8, so the source blocks stay aligned to the frames,
+// and the outputs below -D are masked.  A chain starts from the tail's partial sum where there is one.
+template <bool HLDS>
+__global__ void __launch_bounds__(kThreads) ola_stream_kernel(OlaStreamParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const OlaGeom g = ola_geom(p.F);
+    const int hop = p.hop, T = p.T, N = T * hop, P = g.P;
+    const int delay = P - 1, L = 2 * P - 2;             // D and the tail's length M - 2
+    const int tid = threadIdx.x;
+    const int tiles = (N + P - 1 + g.Pa + kTile - 1) / kTile;
+    const long row = blockIdx.x / tiles;
+    const int tile = (int)(blockIdx.x - row * tiles);
+    const int tile0 = tile * kTile - g.Pa;
+    const int xfirst = tile0 - g.Pa, xcount = kTile + g.Pa + g.Pb + 8;      // xfirst < N for every tile: Pa >= P - 1
+    float *xs = smem;
+    float *rows = xs + xcount;
+    const int fa = max(xfirst, 0) / hop;
+    const int fb = (min(xfirst + xcount, N) - 1) / hop;
+    const float *hrow0 = p.hh + row * (long)T * P;
+    const float *tail_in = p.state_in + row * (long)(L + delay), *hist_in = tail_in + L;
+    float *tail_out = p.state_out + row * (long)(L + delay), *hist_out = tail_out + L;
+    const float *dry = p.dry ? p.dry + row * (long)N : nullptr;
+
+    stage_draw(xs, p.draw, row, T, hop, xfirst, xcount, fa, fb);
+    if (HLDS) stage_rows(rows, hrow0, g, fa, min(fb - fa + 1, p.rows_cap));
+    if (tile == 0)                                      // the dry history: the last D samples of (old history, this block's dry)
+        for (int k = tid; k < delay; k += kThreads) {
+            const int src = N - delay + k;
+            hist_out[k] = src >= 0 ? (dry ? dry[src] : 0.0f) : hist_in[N + k];
+        }
+    __syncthreads();
+
+    const int n0 = tile0 + 8 * tid, i0 = n0 + delay;
+    if (i0 >= N + L) return;                            // (i0 >= -7: Pa - D < 8)
+    float acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = (i0 + u >= 0 && i0 + u < L) ? tail_in[i0 + u] : 0.0f;
+    ola_chains<HLDS>(acc, xs, rows, hrow0, g, n0, xfirst, fa, hop, N);
+    float *dst = p.out + row * (long)N;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u;
+        if (i < 0 || i >= N + L) continue;
+        if (i >= N) tail_out[i - N] = acc[u];
+        else if (dry) dst[i] = (i < delay ? hist_in[i] : dry[i - delay]) + acc[u];
+        else dst[i] = acc[u];
+    }
 }
 
 // ---- backward: the correlation, folded and windowed ------------------------------------------------------------------------------------
@@ -411,6 +489,49 @@ extern "C" int ddsp_noise_ola_forward(const float *Hmag, const float *uniform, f
         hipLaunchKernelGGL(ola_conv_kernel<true>, grid, dim3(kThreads), staged, s, p);
     else
         hipLaunchKernelGGL(ola_conv_kernel<false>, grid, dim3(kThreads), xbytes, s, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t ddsp_noise_ola_stream_state_floats(int F)
+{
+    return (F < 3 || F > kMaxF) ? 0 : (size_t)(3 * F - 6);
+}
+
+extern "C" int ddsp_noise_ola_stream(const float *Hmag, const float *uniform, const float *dry, float *out, const float *state_in,
+                                     float *state_out, int B, int T, int F, int hop, uint64_t seed, uint64_t offset,
+                                     const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (uniform && counter_dev) return DDSP_EINVAL;
+    if (B == 0) return 0;
+    if (!Hmag || !out || B < 0 || T <= 0 || F < 2 || hop <= 0) return DDSP_EINVAL;
+    if (out == dry || (F > 2 && (!state_in || !state_out || state_in == state_out))) return DDSP_EINVAL;
+    const int rc = validate(B, T, F, hop);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < ddsp_noise_ola_workspace_bytes(B, T, F, hop) || ((uintptr_t)workspace % 4) != 0) return DDSP_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const long frames = (long)B * T;
+    float *hh = (float *)workspace;
+    const OlaGeom g = ola_geom(F);
+    const long N = (long)T * hop;
+    const long blocks = (long)B * ((N + g.P - 1 + g.Pa + kTile - 1) / kTile);
+    if (blocks >= (1L << 31)) return DDSP_ERANGE;
+    hipLaunchKernelGGL(cos_sum_kernel<true>, dim3((unsigned)((frames + kCsFrames - 1) / kCsFrames)), dim3(kThreads), cos_sum_lds(F, true), s,
+                       Hmag, hh, frames, F);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+
+    OlaStreamParams p;
+    p.hh = hh; p.dry = dry; p.out = out; p.state_in = state_in; p.state_out = state_out;
+    p.draw = {uniform, seed, offset, counter_dev};
+    p.T = T; p.F = F; p.hop = hop;
+    p.rows_cap = conv_rows_cap(F, hop);
+    const size_t xbytes = (size_t)(kTile + g.Pa + g.Pb + 8) * sizeof(float);
+    const size_t staged = xbytes + (size_t)p.rows_cap * g.RS * sizeof(float);
+    const dim3 grid((unsigned)blocks);
+    if (staged <= kLdsBudget)
+        hipLaunchKernelGGL(ola_stream_kernel<true>, grid, dim3(kThreads), staged, s, p);
+    else
+        hipLaunchKernelGGL(ola_stream_kernel<false>, grid, dim3(kThreads), xbytes, s, p);
     return (int)hipGetLastError();
 }
 

@@ -355,8 +355,24 @@ class Decoder(nn.Module):
         self.noise = FilteredNoise(conf, rng=noise_rng, seed=seed, overlap_add=noise_overlap_add)
         self.reverb = Reverb(conf)
 
-    def synthesize(self, ctrl, live: bool = False):
-        """`harmonics + noise` for a control dict (decoder.py:129-132 / :141-144)."""
+    def check_live(self, delayed: bool, what: str) -> None:
+        """The one rule of every real-time entry point: the overlap-add noise runs live only as a stream `noise.stream_delay` samples
+        late, and accepting that latency is the caller's decision (`delayed=True`); the truncated noise has nothing to delay."""
+        if self.noise.overlap_add and not delayed:
+            raise ValueError(f"{what}: the overlap-add noise (noise_overlap_add) runs live only as a stream that carries its tail from "
+                             "block to block and emits the audio n_noise_filters - 2 samples late: pass delayed=True to accept that")
+        if delayed and not self.noise.overlap_add:
+            raise ValueError(f"{what}: delayed=True is the stream form of the overlap-add noise (noise_overlap_add); "
+                             "the truncated noise has nothing to delay")
+
+    def synthesize(self, ctrl, live: bool = False, delayed: bool = False):
+        """`harmonics + noise` for a control dict (decoder.py:129-132 / :141-144).  `delayed` (with `live`, overlap-add noise only): the
+        block of the stream `FilteredNoise.live` carries, harmonics and noise together `noise.stream_delay` samples late."""
+        if delayed:
+            if not live:
+                raise ValueError("synthesize: delayed=True belongs to the live pass (live=True); a whole clip needs no delay")
+            self.check_live(delayed, "synthesize")
+            return self.noise.live(ctrl, dry=self.harmonics.live(ctrl))
         dry = self.harmonics.live(ctrl) if live else self.harmonics(ctrl)
         if torch.is_grad_enabled() and (dry.requires_grad or ctrl['H'].requires_grad):
             return dry + self.noise(ctrl)
@@ -366,10 +382,9 @@ class Decoder(nn.Module):
     def forward(self, z):
         return self.reverb(self.synthesize(self.controller(z)))
 
-    def forward_live(self, z, hidden):
-        if self.noise.overlap_add:
-            # a callback's block would lose the M/2 samples its frames spread into the neighbouring blocks
-            raise ValueError("forward_live does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
+    def forward_live(self, z, hidden, delayed: bool = False):
+        # (without the stream a callback's block would lose the M/2 samples its frames spread into the neighbouring blocks)
+        self.check_live(delayed, "forward_live")
         ctrl, hidden = self.controller(z, hidden)
-        audio = self.reverb.live_forward(self.synthesize(ctrl, live=True))
+        audio = self.reverb.live_forward(self.synthesize(ctrl, live=True, delayed=delayed))
         return audio.cpu().squeeze(0).numpy(), hidden   # one D2H per callback (rt/synth.py:50-52)

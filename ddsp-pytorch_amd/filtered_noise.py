@@ -67,6 +67,53 @@ def _ola_forward(Hmag, uniform, out, B, T, F, hop, seed, offset, counter, accumu
     return out
 
 
+def ola_stream_state(batch: int, n_filters: int, device) -> torch.Tensor:
+    """The zero state [B, 3F - 6] a stream of `noise_ola_stream` starts from (F = 2: [B, 0])."""
+    return torch.zeros((batch, max(3 * n_filters - 6, 0)), device=device, dtype=torch.float32)
+
+
+def noise_ola_stream(Hmag, hop: int, state, dry=None, uniform=None, seed: int = 0, offset: int = 0, counter=None, state_out=None):
+    """Raw launcher of ddsp_noise_ola_stream (include/ddsp_hip.h): the overlap-add noise of one block of frames H [B,T,F], emitted
+    F - 2 samples late together with the equally delayed `dry` [B, T*hop] (None: the noise alone) -> (out [B, T*hop], new state).
+    `state` [B, 3F - 6] (`ola_stream_state`: zeros start a stream) is only read; the new one is written to `state_out` (a distinct
+    tensor of the same shape; None: a new one).  The draw is noise_forward's: for one row, `offset` (or the device `counter`)
+    advanced by T * ceil(hop / 4) per block gives the samples of one long clip."""
+    if Hmag.dim() != 3:
+        raise ValueError("expected H [B,T,F]")
+    if not Hmag.is_cuda:
+        raise _lib.DdspHipError("FilteredNoise runs on the GPU only (no CPU fallback): move the controls to cuda")
+    Hmag = Hmag.detach().contiguous().float()
+    B, T, F = Hmag.shape
+    dev = Hmag.device
+
+    def fp32(t, shape, name):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 {list(shape)} tensor on {dev}, got {t.dtype} {list(t.shape)} on {t.device}")
+        return t.detach()
+
+    state = fp32(state, (B, max(3 * F - 6, 0)), "state")
+    state_out = torch.empty_like(state) if state_out is None else fp32(state_out, tuple(state.shape), "state_out")
+    if dry is not None:
+        dry = fp32(dry, (B, T * hop), "dry")
+    out = torch.empty((B, T * hop), device=dev, dtype=torch.float32)
+    if B == 0:
+        return out, state_out
+    if uniform is not None:
+        if tuple(uniform.shape) != (B, T, hop):
+            raise ValueError(f"uniform must be [B,T,hop] = {(B, T, hop)}, got {tuple(uniform.shape)}")
+        uniform = uniform.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if counter is not None and (uniform is not None or counter.dtype != torch.int64 or counter.numel() != 1 or not counter.is_cuda):
+        raise ValueError("counter must be a 1-element int64 CUDA tensor and excludes an injected draw")
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()      # noqa: E731
+    with torch.cuda.device(dev):
+        ws, ws_bytes = _ola_workspace(B, T, F, hop, dev)
+        rc = _lib.lib().ddsp_noise_ola_stream(Hmag.data_ptr(), ptr(uniform), ptr(dry), out.data_ptr(), ptr(state), ptr(state_out),
+                                              B, T, F, hop, seed, offset, ptr(counter), ws.data_ptr(), ws_bytes,
+                                              torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_noise_ola_stream")
+    return out, state_out
+
+
 def noise_backward(grad_y, hop: int, n_filters: int, uniform=None, seed: int = 0, offset: int = 0, counter=None,
                    overlap_add: bool = False):
     """Raw launcher of ddsp_noise_backward_ws (overlap_add=True: ddsp_noise_ola_backward, the gradient of that form):
@@ -200,6 +247,58 @@ class FilteredNoise(nn.Module):
         # the forward AND the backward kernel at run time and advanced by a node of the graph after both
         self.counter = None
         self._last_draws = 0
+        # `live`: the stream state [B, 3F - 6] and the spare the new one is written to.  Plain attributes, not buffers (the reference has
+        # no such state and the state_dict stays empty); the state keeps its address, so a captured callback can replay on it
+        self.n_filters = getattr(conf, 'n_noise_filters', None)
+        self._stream_state = self._stream_spare = None
+        self._stream_fresh = True        # nothing streamed since the last reset: the next block may come in another shape
+
+    @property
+    def stream_delay(self) -> int:
+        """Samples by which `live` emits its signal late: F - 2 with the overlap-add mode on, 0 otherwise."""
+        if not self.overlap_add:
+            return 0
+        if self.n_filters is None:
+            raise ValueError("stream_delay is F - 2: the number of bands is known from conf.n_noise_filters or after the first live call")
+        return self.n_filters - 2
+
+    def reset_stream(self) -> None:
+        """Restart `live`'s stream: the carried tail and dry history are zeroed (the draw's offset is `reseed`'s business)."""
+        if self._stream_state is not None:
+            self._stream_state.zero_()
+        self._stream_fresh = True
+
+    def live(self, x, noise=None, dry=None):
+        """One block of the overlap-add noise as a stream (include/ddsp_hip.h: ddsp_noise_ola_stream): `x['H']`
+        [B,T,F] -> [B, T*hop], `stream_delay` samples late, plus the equally delayed `dry` [B, T*hop].  The tail the block's frames
+        spread beyond it is carried to the next call; `reset_stream()` starts over, and a batch, band count or device that changes
+        without one is an error.  Inference only."""
+        if not self.overlap_add:
+            raise ValueError("live is the stream form of the overlap-add noise (noise_overlap_add); the truncated noise has nothing to carry")
+        param = x['H']
+        B, T, F = param.shape
+        if not param.is_cuda:
+            raise _lib.DdspHipError("FilteredNoise runs on the GPU only (no CPU fallback): move the controls to cuda")
+        state = self._stream_state
+        fits = state is not None and state.shape[0] == B and self.n_filters == F and state.device == param.device
+        if state is None or (self._stream_fresh and not fits):
+            state = self._stream_state = ola_stream_state(B, F, param.device)
+            self._stream_spare = torch.empty_like(state)
+            self.n_filters = F
+        elif not fits:
+            raise ValueError(f"live: the stream was started with batch {state.shape[0]}, {self.n_filters} bands on {state.device}; "
+                             f"call reset_stream() before a block of batch {B}, {F} bands on {param.device}")
+        self._stream_fresh = False
+        if noise is None and self.rng == 'host':
+            noise = torch.rand(B, T, self.block_size)
+        offset = 0
+        if noise is None:
+            offset = self._offset
+            self._offset += self.draws(B, T)
+        out, new = noise_ola_stream(param, self.block_size, state, dry=dry, uniform=noise, seed=self.seed, offset=offset,
+                                    state_out=self._stream_spare)
+        state.copy_(new)        # the state keeps its address, as Reverb._live_hip's history does
+        return out
 
     def reseed(self, seed: int, offset: int = 0) -> None:
         """Restart the in-kernel (rng='device') stream: a resumed training run passes a fresh seed (or the offset it saved)

@@ -6,7 +6,9 @@ them cost more than the kernels.  `GraphedSynth` captures the pass once for a fi
 the caller writes the controls into the static input tensors (`f0`, `c`, `a`, `H`) and reads `out`.
 
 With `live=True` the oscillator runs as `OscillatorBank.live` (harmonic_oscillator.py:64-75): the phase state
-of batch row 0 is carried from replay to replay inside the graph (state_out -> state_in copy node).
+of batch row 0 is carried from replay to replay inside the graph (state_out -> state_in copy node).  With the overlap-add noise
+the live pass runs only `delayed=True`: the noise is the stream of `noise_ola_stream`, whose state (`noise_state`) is advanced by a
+copy node in the same way, and `out` is the signal `delay` = n_noise_filters - 2 samples late.
 """
 from __future__ import annotations
 
@@ -14,13 +16,13 @@ import torch
 
 from . import _lib
 from . import dense
-from .filtered_noise import FilteredNoise, noise_forward
+from .filtered_noise import FilteredNoise, noise_forward, noise_ola_stream, ola_stream_state
 from .harmonic_oscillator import osc_forward
 
 
 class GraphedSynth:
     def __init__(self, conf, batch: int, frames: int, n_noise_filters: int, device="cuda", live: bool = False,
-                 noise_seed: int = 0):
+                 noise_seed: int = 0, delayed: bool = False):
         self.hop, self.sample_rate, self.live = conf.hop_length, conf.sample_rate, live
         dev = torch.device(device)
         H = conf.n_harmonics
@@ -31,8 +33,15 @@ class GraphedSynth:
         self.state = torch.zeros(H, device=dev)           # last_phases (fp32, as after the reference's first live call)
         self.seed = noise_seed
         self.overlap_add = bool(getattr(conf, 'noise_overlap_add', False))
-        if live and self.overlap_add:
-            raise ValueError("the live pass does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
+        if live and self.overlap_add and not delayed:
+            raise ValueError("the live pass runs the overlap-add noise (noise_overlap_add) only as a stream that carries its tail from "
+                             "block to block and emits the audio n_noise_filters - 2 samples late: pass delayed=True to accept that")
+        if delayed and not (live and self.overlap_add):
+            raise ValueError("delayed=True is the stream form of the overlap-add noise (noise_overlap_add) in the live pass (live=True); "
+                             "the truncated noise has nothing to delay")
+        self.delayed = delayed
+        self.delay = n_noise_filters - 2 if delayed else 0
+        self.noise_state = ola_stream_state(batch, n_noise_filters, dev) if delayed else None
         self._step = torch.zeros(1, dtype=torch.int64, device=dev)     # Philox offset of the next call's draw
         self._draws_per_call = batch * frames * ((conf.hop_length + 3) // 4)
         self.out = None
@@ -48,7 +57,11 @@ class GraphedSynth:
             y, _, _ = osc_forward(self.f0, self.c, self.a, self.hop, self.sample_rate)
         # the Philox offset of the draw lives on the device and advances inside the graph: every replay is fresh noise,
         # the same sequence as un-captured calls with offset = call index x draws per call
-        y = noise_forward(self.H, self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step, overlap_add=self.overlap_add)
+        if self.delayed:
+            y, new_noise = noise_ola_stream(self.H, self.hop, self.noise_state, dry=y, seed=self.seed, counter=self._step)
+            self.noise_state.copy_(new_noise)
+        else:
+            y = noise_forward(self.H, self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step, overlap_add=self.overlap_add)
         self._step.add_(self._draws_per_call)
         return y
 
@@ -56,19 +69,25 @@ class GraphedSynth:
         if not self.f0.is_cuda:
             raise _lib.DdspHipError("GraphedSynth needs a GPU")
         saved = self.state.clone()
-        self._step.zero_()
+
+        def restore():
+            self.state.copy_(saved)
+            self._step.zero_()
+            if self.noise_state is not None:
+                self.noise_state.zero_()
+
+        restore()
         side = torch.cuda.Stream(device=self.f0.device)
         side.wait_stream(torch.cuda.current_stream(self.f0.device))
         with torch.cuda.stream(side):
             for _ in range(2):
                 self._pass()                      # warm-up: lazy one-time attribute calls, allocator pools
         torch.cuda.current_stream(self.f0.device).wait_stream(side)
-        self.state.copy_(saved)
+        restore()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.out = self._pass()
-        self.state.copy_(saved)
-        self._step.zero_()
+        restore()
 
     def run(self):
         """Replay the captured pass on the current controls; returns the static output tensor [B, T*hop]."""
@@ -86,13 +105,13 @@ class GraphedLiveDecoder:
     controller (MLPs, GRU recurrence, heads) -> harmonics.live + noise -> reverb.live_forward.  Per callback the host does
     three small H2D copies into the static inputs, one replay and one D2H of the audio.  Every piece of state stays on
     the device and is advanced by nodes of the graph: the oscillator phases (`state`), the reverb's one-second history
-    (`decoder.reverb.buffer`), the Philox offset of the noise draw, and the GRU state (`hidden_out`; the reference hands
-    the callback's INPUT state back, SURVEY App. C.7 -- `carry_hidden=True` feeds the new one forward instead).
+    (`decoder.reverb.buffer`), the Philox offset of the noise draw, with `delayed=True` (a decoder with the overlap-add noise: the
+    audio comes `delay` = n_noise_filters - 2 samples late) the noise stream's tail and dry history (`noise_state`), and
+    the GRU state (`hidden_out`; the reference hands the callback's INPUT state back, SURVEY App. C.7 -- `carry_hidden=True` feeds the new one forward instead).
     """
 
-    def __init__(self, decoder, frames: int, noise_seed: int = 0, carry_hidden: bool = False):
-        if decoder.noise.overlap_add:
-            raise ValueError("the live decoder does not support the overlap-add noise (noise_overlap_add): no tail is carried between blocks")
+    def __init__(self, decoder, frames: int, noise_seed: int = 0, carry_hidden: bool = False, delayed: bool = False):
+        decoder.check_live(delayed, "GraphedLiveDecoder")
         self.dec = decoder.eval()
         dev = next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -108,6 +127,10 @@ class GraphedLiveDecoder:
         self.state = osc.last_phases.data.detach().to(device=dev, dtype=torch.float32).clone()
         self._step = torch.zeros(1, dtype=torch.int64, device=dev)
         self._draws_per_call = frames * ((self.hop + 3) // 4)
+        n_filters = decoder.controller.dense_filter.out_features
+        self.delayed = delayed
+        self.delay = n_filters - 2 if delayed else 0
+        self.noise_state = ola_stream_state(1, n_filters, dev) if delayed else None
         self.out = None
         self._capture()
 
@@ -117,7 +140,11 @@ class GraphedLiveDecoder:
             y, new_state, _ = osc_forward(ctrl["f0"], ctrl["c"], ctrl["a"], self.hop, self.sample_rate, live_in=self.state,
                                           want_live_out=True)
             self.state.copy_(new_state)
-            noise_forward(ctrl["H"], self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step)
+            if self.delayed:
+                y, new_noise = noise_ola_stream(ctrl["H"], self.hop, self.noise_state, dry=y, seed=self.seed, counter=self._step)
+                self.noise_state.copy_(new_noise)
+            else:
+                noise_forward(ctrl["H"], self.hop, seed=self.seed, out=y, accumulate=True, counter=self._step)
             self._step.add_(self._draws_per_call)
             audio = self.dec.reverb.live_forward(y)
             self.hidden_out.copy_(ctrl["hidden"])
@@ -134,6 +161,8 @@ class GraphedLiveDecoder:
             self.dec.reverb.buffer.data.copy_(keep[1])
             self.hidden.copy_(keep[2])
             self._step.zero_()
+            if self.noise_state is not None:
+                self.noise_state.zero_()
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))

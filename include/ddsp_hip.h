@@ -139,6 +139,34 @@ int ddsp_noise_ola_backward(const float *grad_y, const float *uniform, float *gr
                             uint64_t offset, const uint64_t *counter_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The overlap-add noise as a stream: one block of T frames (n_b = T hop samples; T may change from call to call) per call, for the
+ * real-time callback.  The response is zero-phase: y[n] depends on sources up to n + P - 1 (P = F - 1, M = 2 P), so the stream runs
+ * D = P - 1 = F - 2 samples late, the smallest delay at which every emitted sample is complete, and the accumulated input `dry`
+ * (the harmonics) is delayed by the same D.  With y the definition above extended to all integer n over the sources m >= 0 of the
+ * concatenated blocks:
+ *   stream[i] = y[i - D] + dry[i - D]      (dry[< 0] = 0; the first D samples hold the pre-ring y[-D .. -1] the offline form crops)
+ * and a call returns the next n_b samples of it in out [B, n_b].
+ *   state_in / state_out [B, 3F - 6]  per row M - 2 floats of tail -- the partial sums, over the sources so far, of the next M - 2
+ *                      stream samples -- then D floats of dry history (the last D samples of dry).  All zeros start a stream.  Two
+ *                      distinct buffers (workgroups read what others overwrite); F == 2 has no state and both may be NULL.  A tail
+ *                      longer than the block is shifted and continued.
+ *   dry [B, n_b]       nullable: NULL emits the noise alone (nothing is added, zeros enter the history).  Must not be `out`.
+ *   draw               as above with frame = b T + t: for one row, advancing offset (or *counter_dev) by T ceil(hop / 4) per call
+ *                      draws the samples of one long clip; a block needs no sample of an earlier block.
+ * Every y[n] stays ONE chain of fp32 multiply-adds over ascending source sample: a block starts each chain from the tail's value
+ * instead of 0 and stores it to out (plus the delayed dry value: one fp32 add) or to the new tail.  So the streamed blocks equal,
+ * bit for bit, ddsp_noise_ola_forward on the concatenated controls behind leading silent frames (H = 0), shifted by D.  A
+ * non-finite H_t reaches the stream samples [t hop, (t + 1) hop + M - 3] of its row and nothing else, across calls; after that the
+ * state is finite again.  Two launches, no atomics, nothing allocated or synchronised.  workspace, range and error order as
+ * ddsp_noise_ola_forward; out == dry, state_in == state_out or a null state pointer with F > 2 is DDSP_EINVAL before anything
+ * touches the device.  ddsp_noise_ola_stream_state_floats: 3F - 6 per row; 0 for F < 3 or F out of range.
+ */
+size_t ddsp_noise_ola_stream_state_floats(int F);
+int ddsp_noise_ola_stream(const float *Hmag, const float *uniform, const float *dry, float *out, const float *state_in,
+                          float *state_out, int B, int T, int F, int hop, uint64_t seed, uint64_t offset, const uint64_t *counter_dev,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Backward of ddsp_osc_forward_ex w.r.t. c and a (autograd of harmonic_oscillator.py:24-62; f0 carries no gradient,
  * decoder.py:105).  `fwd_scratch` is the scratch buffer the matching ddsp_osc_forward_ex call filled with
  * DDSP_OSC_KEEP_FRAME_SCRATCH (same B,T,H,hop, sample_rate, same tiling); `bwd_scratch` >= ddsp_osc_backward_scratch_bytes(B,T,H).
