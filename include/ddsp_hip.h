@@ -635,6 +635,47 @@ int ddsp_griffinlim(const float *mag, const float *angles, const float *window, 
                     size_t workspace_bytes, long B, long T, int n_fft, int hop, long L, int n_iter, float c, void *stream);
 
 /*
+ * Test hook (DDSP_EPERM unless DDSP_TEST_HOOKS=1 was set when the library was loaded): the pieces of the shared one-wavefront
+ * FFT (csrc/ddsp_wave_fft.h) on the caller's data, one wavefront per unit, for tests/test_gpu_wave_fft.py.  The kernels load the
+ * input in the layout the header documents, call its function and store the result in natural order; they do no arithmetic of
+ * their own.  Complex data is interleaved (re, im); `in` and `out` are device memory, 8-byte aligned, and must not overlap.
+ *
+ *   form                            in (floats per unit)                     out (floats per unit)
+ *   DDSP_WFFT_PAIR_FWD + i, i < 5   [BT, N] complex, N = 64 << i,            [BT, N] complex: PairFft<N>::run<false>, natural(i)
+ *   DDSP_WFFT_PAIR_INV + i          BT = 8, 4, 2, 1, 1 transforms per unit   the same with run<true> (unnormalised: N ifft)
+ *   DDSP_WFFT_WAVE8_FWD, _INV       [512] complex                            [512] complex: fft_wave<8, INV, false>, store_natural
+ *   DDSP_WFFT_WAVE8_HALFZERO        [256] complex (the lower half)           [512] complex: fft_wave<8, false, true>
+ *   DDSP_WFFT_WAVE16_FWD, _INV      [1024] complex                           [1024] complex
+ *   DDSP_WFFT_WAVE16_HALFZERO       [512] complex                            [1024] complex
+ *   DDSP_WFFT_REAL2048_FWD          [2048] real                              [1025] complex: rfft (fft_wave<16>, split2048)
+ *   DDSP_WFFT_REAL2048_INV          [1025] complex, bins 0 and 1024 real     [2048] real: 2048 irfft (pack2048, fft_wave<16, true>)
+ *   DDSP_WFFT_TWIDDLES              nothing (in is not read)                 [64 lanes, DDSP_WFFT_TWIDDLE_COUNT] complex, per lane:
+ *                                     Twiddles<8> t1[8], t2[0][8]; Twiddles<16> t1[16], t2[0][8], t2[1][8]; PairFft<128>::t1s[2];
+ *                                     PairFft<256>::t1s[4]; PairFft<64>, <128>, <256>::tw.t2[0][8]; lane_w2048; twiddle2048 it = 0..8
+ *   DDSP_WFFT_SCALE                 c_in, c_out in front, then one m a unit  (frame_scale_of(m, c_in, c_out).in, .out)
+ *   DDSP_WFFT_WAVEMAX               [64]                                     [64]: wave_max as each lane sees it
+ *
+ * ddsp_wfft_probe_sizes gives the floats of `in` and `out` for `units` units.  An unknown form, a null pointer, negative units or
+ * more than 2^20 of them: DDSP_EINVAL; units == 0 returns 0; nothing is launched before these checks.  One launch on `stream`.
+ */
+#define DDSP_WFFT_PAIR_FWD 0
+#define DDSP_WFFT_PAIR_INV 5
+#define DDSP_WFFT_WAVE8_FWD 10
+#define DDSP_WFFT_WAVE8_INV 11
+#define DDSP_WFFT_WAVE8_HALFZERO 12
+#define DDSP_WFFT_WAVE16_FWD 13
+#define DDSP_WFFT_WAVE16_INV 14
+#define DDSP_WFFT_WAVE16_HALFZERO 15
+#define DDSP_WFFT_REAL2048_FWD 16
+#define DDSP_WFFT_REAL2048_INV 17
+#define DDSP_WFFT_TWIDDLES 18
+#define DDSP_WFFT_SCALE 19
+#define DDSP_WFFT_WAVEMAX 20
+#define DDSP_WFFT_TWIDDLE_COUNT 88
+int ddsp_wfft_probe_sizes(int form, long units, long *in_floats, long *out_floats);
+int ddsp_wfft_probe(int form, const float *in, float *out, long units, void *stream);
+
+/*
  * The trainer's batch fetch from a device-resident training set (train/train.py:48: DataLoader(shuffle=True), collate, copy).
  *
  * ddsp_gather_batch  for each of n_arrays (<= DDSP_GATHER_MAX_ARRAYS) fp32 arrays: dst[a] [rows, row_floats[a]] row r <-
