@@ -121,6 +121,7 @@ SIGNATURES = {
     "ddsp_griffinlim": (_i32, [_vp] * 6 + [_size, _long, _long, _i32, _i32, _long, _i32, _f32, _vp]),
     "ddsp_wfft_probe_sizes": (_i32, [_i32, _long, ctypes.POINTER(_long), ctypes.POINTER(_long)]),
     "ddsp_wfft_probe": (_i32, [_i32, _vp, _vp, _long, _vp]),
+    "ddsp_griffinlim_stage": (_i32, [_i32] + [_vp] * 8 + [_long, _long, _i32, _i32, _long, _f32, _vp]),
     "ddsp_gather_batch": (_i32, [_vp, _vp, ctypes.POINTER(_long), _i32, _vp, _vp, _long, _long, _i32, _i32, _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)

@@ -401,7 +401,64 @@ hipError_t run(GlParams p, const float *env, float *y, long B, long Lnat, int n_
     return launch_overlap(p, env, y, B, N, Lnat, s);
 }
 
+// One launcher of the three on the caller's buffers (the test hook ddsp_griffinlim_stage)
+template <int N>
+hipError_t run_stage(int stage, const GlParams &p, const float *env, float *out, long B, long Lnat, hipStream_t s)
+{
+    switch (stage) {
+    case DDSP_GL_STAGE_SYNTH: return launch_synth<N>(p, s);
+    case DDSP_GL_STAGE_OVERLAP: return launch_overlap(p, env, out, B, N, Lnat, s);
+    default: return launch_analysis<N>(p, s);
+    }
+}
+
 }  // namespace
+
+extern "C" int ddsp_griffinlim_stage(int stage, const float *S, const float *ang0, const float *R, const float *Rprev, const float *in,
+                                     const float *window, const float *env, float *out, long B, long T, int n_fft, int hop, long L,
+                                     float c, void *stream)
+{
+    if (!ddsp_hooks_on()) return DDSP_EPERM;
+    if (!out || B <= 0 || T <= 0 || hop <= 0 || L <= 0 || !(c >= 0.0f && c < 1.0f)) return DDSP_EINVAL;
+    switch (stage) {
+    case DDSP_GL_STAGE_SYNTH: if (!S || !window) return DDSP_EINVAL; break;
+    case DDSP_GL_STAGE_OVERLAP: if (!in || !env) return DDSP_EINVAL; break;
+    case DDSP_GL_STAGE_ANALYSIS: if (!in || !window) return DDSP_EINVAL; break;
+    default: return DDSP_EINVAL;
+    }
+    // ddsp_griffinlim's own range checks, in its order
+    if (!ddsp_griffinlim_supported(n_fft)) return DDSP_ERANGE;
+    if (1 + L / hop != T || L <= n_fft / 2 || B > 65535 || T > (1l << 24)) return DDSP_ERANGE;
+    if ((double)B * (double)T * (double)n_fft > (double)(1l << 40)) return DDSP_ERANGE;
+    GlParams p;
+    p.S = S;
+    p.ang0 = (const cf *)ang0;
+    p.R = (const cf *)R;
+    p.Rprev = (const cf *)Rprev;
+    p.Rout = stage == DDSP_GL_STAGE_ANALYSIS ? (cf *)out : nullptr;
+    p.frames = stage == DDSP_GL_STAGE_SYNTH ? out : const_cast<float *>(in);     // (the overlap launch only reads them)
+    p.y = in;
+    p.window = window;
+    p.nframes = B * T;
+    p.T = T;
+    p.L = L;
+    p.hop = hop;
+    p.F = n_fft / 2 + 1;
+    p.c = c;
+    const long natural = (long)n_fft + (long)hop * (T - 1) - n_fft / 2;          // as in ddsp_griffinlim
+    const long Lnat = L < natural ? L : natural;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    switch (n_fft) {
+    case 64: e = run_stage<64>(stage, p, env, out, B, Lnat, s); break;
+    case 128: e = run_stage<128>(stage, p, env, out, B, Lnat, s); break;
+    case 256: e = run_stage<256>(stage, p, env, out, B, Lnat, s); break;
+    case 512: e = run_stage<512>(stage, p, env, out, B, Lnat, s); break;
+    case 1024: e = run_stage<1024>(stage, p, env, out, B, Lnat, s); break;
+    default: e = run_stage<2048>(stage, p, env, out, B, Lnat, s); break;
+    }
+    return (int)e;
+}
 
 extern "C" int ddsp_griffinlim_supported(int n_fft) { return ddsp_wfft::real_size_supported(n_fft) ? 1 : 0; }
 

@@ -676,6 +676,32 @@ int ddsp_wfft_probe_sizes(int form, long units, long *in_floats, long *out_float
 int ddsp_wfft_probe(int form, const float *in, float *out, long units, void *stream);
 
 /*
+ * Test hook (DDSP_EPERM unless DDSP_TEST_HOOKS=1 was set when the library was loaded): ONE of the three launches of a Griffin-Lim
+ * iteration (csrc/ddsp_griffinlim.hip) on the caller's buffers, for tests/test_gpu_griffinlim_stages.py.  It fills the kernels'
+ * parameter block and calls the launcher ddsp_griffinlim calls; it does no arithmetic of its own.  Everything is device memory in
+ * the kernels' own frame-major layout (ddsp_griffinlim transposes into it), F = n_fft / 2 + 1, complex data interleaved (re, im),
+ * 8-byte aligned; `out` must not overlap an input.
+ *
+ *   stage                    reads                                                                  out
+ *   DDSP_GL_STAGE_SYNTH      S [B T, F]; ang0 [B T, F] complex or NULL (every angle 1), used when   frames [B T, n_fft]:
+ *                            R is NULL; R [B T, F] complex or NULL; Rprev [B T, F] complex or NULL  irfft(S angles) window
+ *                            (no momentum term), read with R only; window [n_fft]; c
+ *   DDSP_GL_STAGE_OVERLAP    in = frames [B T, n_fft]; env [L] (read below min(L, n_fft/2 +         y [B, L]
+ *                            hop (T - 1)) only)
+ *   DDSP_GL_STAGE_ANALYSIS   in = y [B, L]; window [n_fft]                                          R [B T, F] complex
+ *
+ * Arguments a stage does not read may be NULL.  DDSP_EINVAL: an unknown stage, a null `out` or a null pointer the stage reads,
+ * B, T, hop or L <= 0, c outside [0, 1).  DDSP_ERANGE: ddsp_griffinlim's constraints (n_fft, 1 + L / hop == T, L > n_fft / 2,
+ * B <= 65535, the size limits).  Nothing is launched before these checks.  One launch on `stream`, no synchronisation.
+ */
+#define DDSP_GL_STAGE_SYNTH 0
+#define DDSP_GL_STAGE_OVERLAP 1
+#define DDSP_GL_STAGE_ANALYSIS 2
+int ddsp_griffinlim_stage(int stage, const float *S, const float *ang0, const float *R, const float *Rprev, const float *in,
+                          const float *window, const float *env, float *out, long B, long T, int n_fft, int hop, long L, float c,
+                          void *stream);
+
+/*
  * The trainer's batch fetch from a device-resident training set (train/train.py:48: DataLoader(shuffle=True), collate, copy).
  *
  * ddsp_gather_batch  for each of n_arrays (<= DDSP_GATHER_MAX_ARRAYS) fp32 arrays: dst[a] [rows, row_floats[a]] row r <-

@@ -6,12 +6,13 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder]   (`training`: the loss-side kernels against
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder | griffinlim]   (`training`: the loss-side kernels against
 fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
 backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
 fp64 reference of tests/noise_grad_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
 reference of tests/gru_reference.py; `encoder`: the encoder's loudness and resampler kernels against the fp64 references of
-tests/encoder_reference.py)"""
+tests/encoder_reference.py; `griffinlim`: Griffin-Lim's synthesis, overlap-add and analysis kernels one at a time through
+ddsp_griffinlim_stage against the fp64 reference and the criteria of tests/griffinlim_reference.py)"""
 import os
 import sys
 
@@ -29,6 +30,7 @@ import osc_grad_reference as R  # noqa: E402
 import noise_grad_reference as R_noise  # noqa: E402
 import gru_reference as R_gru  # noqa: E402
 import encoder_reference as R_enc  # noqa: E402
+import griffinlim_reference as R_gl  # noqa: E402
 
 
 def bits(a):
@@ -720,9 +722,32 @@ def sweep_encoder_stages(cases: int, seed: int, verbose: bool = True):
     return bad, worst
 
 
+def sweep_griffinlim_stages(cases: int, seed: int, verbose: bool = True):
+    """Random cases of Griffin-Lim's three kernels, each alone through ddsp_griffinlim_stage (R_gl.random_case: random n_fft, hop
+    up to n_fft / 2 with a Hann window of random win_length and up to n_fft with the rectangular one, B, T <= 40, extra length, c,
+    with and without initial angles, R and Rprev), under the criteria of the stages alone: synthesis and analysis at most
+    CPU_FACTOR times the CPU fp32 formulation's error and under the derived ceiling, the overlap-add bit for bit the fp32
+    restatement and within the summation bound.  -> (failed, the figures of the failed cases)"""
+    rng = np.random.default_rng(seed)
+    bad, report = 0, []
+    for i in range(cases):
+        case = R_gl.random_case(rng)
+        okay, lines = R_gl.run_case(case, seed * 1000 + i)
+        bad += not okay
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} case {i}: {case}\n  " + "\n  ".join(lines), flush=True)
+        if not okay:
+            report.extend(lines)
+    return bad, report
+
+
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2026
+    if len(sys.argv) > 3 and sys.argv[3] == "griffinlim":
+        bad, _ = sweep_griffinlim_stages(cases, seed, verbose=True)
+        print(f"Griffin-Lim stages: cases {cases}, seed {seed}, failed {bad}")
+        sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "chunked":
         bad, worst = sweep_chunked(cases, seed, verbose=False)
         print(f"chunked oscillator form: cases {cases}, seed {seed}, failed {bad}, worst audio error {worst:.2e}")

@@ -1,7 +1,8 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
 oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
 plus the chunked oscillator form, the loss-side kernels, the backward of the oscillator and of the filtered noise, the GRU
-recurrence step by step against fp64, and the encoder's loudness and resampler kernels against fp64."""
+recurrence step by step against fp64, the encoder's loudness and resampler kernels against fp64, and Griffin-Lim's three kernels
+one at a time against fp64."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -62,3 +63,12 @@ def test_random_cases_of_the_encoder_stages_match_fp64(seed):
     branch to half of that on the same cases)."""
     bad, worst = fuzz_parity.sweep_encoder_stages(40, seed, verbose=False)
     assert bad == 0, (bad, worst)
+
+
+@pytest.mark.parametrize("seed", [909])
+def test_random_cases_of_the_griffinlim_stages_match_fp64(seed):
+    """40 random cases of Griffin-Lim's synthesis, overlap-add and analysis kernels, each alone through ddsp_griffinlim_stage, under
+    the criteria of tests/griffinlim_reference.py: the transforms at most CPU_FACTOR times the CPU fp32 formulation's error and
+    under the derived ceiling, the overlap-add bit for bit its fp32 restatement and within the summation bound."""
+    bad, report = fuzz_parity.sweep_griffinlim_stages(40, seed, verbose=False)
+    assert bad == 0, (bad, report)

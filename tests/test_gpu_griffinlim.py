@@ -1,6 +1,8 @@
 """Griffin-Lim on the MI355X: the HIP path (csrc/ddsp_griffinlim.hip) against the G27 fixtures per iteration count, against the
 device's own stock loop on random shapes, run to run, in convergence, and the stock-loop fallback for n_fft the kernels do
-not take.  Tolerance: 4x the fixture's (or the case's) fp32-vs-fp64 spread, the encoder's rule."""
+not take.  Tolerance: 4x the fixture's (or the case's) fp32-vs-fp64 spread, the encoder's rule.  These are free-running
+comparisons of a chaotic iteration; the three kernels are held to fp64 one at a time, and one teacher-forced step at a time
+along the same G27 trajectories, in tests/test_gpu_griffinlim_stages.py."""
 import numpy as np
 import pytest
 import torch
@@ -41,7 +43,9 @@ def _exact64(spec, window, angles, n_fft, hop_length, win_length, power, n_iter,
 # Measured on the MI355X, err / spread per iteration count: <= 1.8 everywhere except n2048_h256 (momentum 0.99) from iteration 6
 # on, where one near-cancelling bin of R - c R_prev takes a different phase in the HIP run than in the stock fp32 runs and the
 # ratio jumps from 0.68 to 10 and then drifts to 14 .. 38.  Those iterations are held to 64x; the spectral
-# convergence of the same path is checked separately (test_convergence_no_worse_than_stock).
+# convergence of the same path is checked separately (test_convergence_no_worse_than_stock).  It is conditioning, not the
+# 2048-point kernels: each single step from the fp64 trajectory's state is as accurate on the device as the stock fp32 step
+# (tests/test_gpu_griffinlim_stages.py::test_teacher_forced_steps_along_g27; kappa reaches 1.4e4 at iteration 6).
 LOOSE = {("n2048_h256", n): 64 for n in range(6, 17)}
 
 
