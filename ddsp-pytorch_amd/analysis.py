@@ -19,12 +19,17 @@ Noise analysis: the inverse of `FilteredNoise` (include/dd
 x [B, T hop] the band magnitudes H [B, T, n_filters] whose FilteredNoise frames have, in expectation, the in-frame
 autocorrelation measured on x (averaged over `average` frames), by `iterations` steps of a multiplicative fixed point:
 
-  noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=False) -> H [B, T, F]  (or (H, p), p the target spectrum)
-  NoiseAnalyzer(conf)     nn.Module without parameters over conf.n_noise_filters / hop_length
+  noise_analysis(x, hop, n_filters, average=1, iterations=None, return_power=False, overlap_add=False)
+                                                                        -> H [B, T, F]  (or (H, p), p the target spectrum)
+  NoiseAnalyzer(conf, overlap_add=None)   nn.Module without parameters over conf.n_noise_filters / hop_length
 
 hop >= 2 (n_filters - 1) is required (below it the filter is cropped and H is not identifiable).  CUDA fp32 tensors with
 n_filters <= 257 and hop <= 1024 take the HIP kernels (csrc/ddsp_noise_analysis.hip); everything else the same definition as
 stock torch ops in the input's dtype.  No backward.
+
+overlap_add=True inverts FilteredNoise's overlap-add mode instead (ddsp_noise_analysis_ola): that noise is
+stationary, so the model is (hop / 3) times the autocorrelation of the frame's whole response, the measured products cross frame
+boundaries and any hop >= 1 is analysable.  `iterations=None` is 16 for the truncated model and 8 for the overlap-add one.
 """
 from __future__ import annotations
 
@@ -43,6 +48,9 @@ _CHUNK_ELEMENTS = 1 << 24                # the torch path's largest intermediate
 NOISE_KERNEL_MAX_FILTERS = 257           # csrc/ddsp_noise_analysis.hip: kMaxF, kMaxHop, kMaxGrid
 NOISE_KERNEL_MAX_HOP = 1024
 NOISE_KERNEL_MAX_FRAMES = 2 ** 31 - 1
+NOISE_OLA_KERNEL_MAX_SAMPLES = 2 ** 31 - 8192   # (exclusive) samples of one row of the overlap-add analysis
+NOISE_ITERATIONS = 16                    # the defaults of `iterations`: the truncated model and the overlap-add one
+NOISE_OLA_ITERATIONS = 8
 
 
 def _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, what):
@@ -313,6 +321,18 @@ def _noise_spectrum(r: torch.Tensor, Cos: torch.Tensor) -> torch.Tensor:
     return 0.25 * ext[:, :-2] + 0.5 * ext[:, 1:-1] + 0.25 * ext[:, 2:]
 
 
+def _frame_average(r: torch.Tensor, average: int) -> torch.Tensor:
+    """r [B, T, L] -> the mean over t' in [t - s, t + s] inside [0, T), s = (average - 1) / 2."""
+    T = r.shape[1]
+    s = min((average - 1) // 2, T - 1)
+    rbar = torch.zeros_like(r)
+    for o in range(-s, s + 1):                                   # t' = t + o ascending; no prefix sums: a NaN stays in its window
+        t0, t1 = max(0, -o), T - max(0, o)
+        rbar[:, t0:t1] += r[:, t0 + o:t1 + o]
+    t = torch.arange(T, device=r.device)
+    return rbar / ((t + s).clamp(max=T - 1) - (t - s).clamp(min=0) + 1).to(r.dtype)[None, :, None]
+
+
 def _noise_torch(x, hop, F, average, iterations):
     dt, dev = x.dtype, x.device
     B = x.shape[0]
@@ -322,13 +342,7 @@ def _noise_torch(x, hop, F, average, iterations):
     frames = x.reshape(B * T, hop)
     step = max(1, _CHUNK_ELEMENTS // hop)
     r = torch.cat([_lagged(frames[i:i + step], frames[i:i + step], L) for i in range(0, B * T, step)]).reshape(B, T, L)
-    s = min((average - 1) // 2, T - 1)
-    rbar = torch.zeros_like(r)
-    for o in range(-s, s + 1):                                   # t' = t + o ascending; no prefix sums: a NaN stays in its window
-        t0, t1 = max(0, -o), T - max(0, o)
-        rbar[:, t0:t1] += r[:, t0 + o:t1 + o]
-    t = torch.arange(T, device=dev)
-    rbar = rbar / ((t + s).clamp(max=T - 1) - (t - s).clamp(min=0) + 1).to(dt)[None, :, None]
+    rbar = _frame_average(r, average)
     p = _noise_spectrum(rbar.reshape(B * T, L), Cos).clamp(min=0)                # (clamp keeps a NaN)
     H = torch.sqrt(3.0 * p / hop)
     tiny = torch.finfo(dt).tiny
@@ -342,35 +356,91 @@ def _noise_torch(x, hop, F, average, iterations):
     return H.reshape(B, T, F), p.reshape(B, T, F)
 
 
+def _noise_ola_tables(F: int, dt, dev):
+    """(HT [P, F], Cos [F, L]): the half response hh[d] = h[+-d] of unit vector b, (1/2 + 1/2 cos(pi d / P)) (c_b / M)
+    cos(2 pi b d / M), and c_l g[l] cos(pi b l / L); evaluated in fp64, rounded once to dt."""
+    P, M = F - 1, 2 * (F - 1)
+    d = torch.arange(P, device=dev)
+    b = torch.arange(F, device=dev)
+    cb = torch.where((b == 0) | (b == F - 1), 1.0, 2.0).double()
+    HT = ((0.5 + 0.5 * torch.cos(math.pi * d.double() / P))[:, None] * (cb / M)[None, :]
+          * torch.cos(math.pi * torch.remainder(b[None, :] * d[:, None], M).double() / P))
+    return HT.to(dt), _noise_tables(F, M, dt, dev)[2]
+
+
+def _noise_ola_measure(x: torch.Tensor, hop: int, L: int) -> torch.Tensor:
+    """x [B, N] -> r [B, T, L]: r_t[l] = (hop / c) sum_{n < hop, t hop + n + l < N} x[t hop + n] x[t hop + n + l], c the count of terms."""
+    B, N = x.shape
+    T = N // hop
+    r = torch.zeros((B, T, L), dtype=x.dtype, device=x.device)
+    step = max(1, _CHUNK_ELEMENTS // N)
+    for lag in range(min(L, N)):
+        for i in range(0, B, step):
+            prod = torch.nn.functional.pad(x[i:i + step, :N - lag] * x[i:i + step, lag:], (0, lag))
+            r[i:i + step, :, lag] = prod.reshape(-1, T, hop).sum(-1)
+    count = (N - torch.arange(T, device=x.device)[:, None] * hop - torch.arange(L, device=x.device)[None, :]).clamp(0, hop)
+    scale = torch.where(count > 0, hop / count.clamp(min=1).to(x.dtype), torch.zeros((), dtype=x.dtype, device=x.device))
+    return r * scale[None]
+
+
+def _noise_ola_torch(x, hop, F, average, iterations):
+    dt, dev = x.dtype, x.device
+    B = x.shape[0]
+    T, L = x.shape[1] // hop, F - 1
+    HT, Cos = _noise_ola_tables(F, dt, dev)
+    rbar = _frame_average(_noise_ola_measure(x, hop, L), average)
+    p = _noise_spectrum(rbar.reshape(B * T, L), Cos).clamp(min=0)                # (clamp keeps a NaN)
+    H = torch.sqrt(3.0 * p / hop)
+    tiny = torch.finfo(dt).tiny
+    step = max(1, _CHUNK_ELEMENTS // (2 * L + 1))
+    for _ in range(iterations):
+        for i in range(0, B * T, step):
+            Hc, pc = H[i:i + step], p[i:i + step]
+            hh = Hc @ HT.T                                                       # [n, P]: h[d], d >= 0
+            h = torch.cat([hh[:, 1:].flip(-1), hh], dim=-1)                      # h[e] at e + P - 1
+            R = _lagged(h, h, L) * (hop / 3.0)
+            H[i:i + step] = Hc * torch.sqrt(pc / _noise_spectrum(R, Cos).clamp(min=tiny))
+    return H.reshape(B, T, F), p.reshape(B, T, F)
+
+
 def _noise_in_kernel_range(x: torch.Tensor, hop: int, F: int) -> bool:
     return (x.is_cuda and x.dtype == torch.float32 and F <= NOISE_KERNEL_MAX_FILTERS and hop <= NOISE_KERNEL_MAX_HOP
             and x.shape[0] * (x.shape[1] // hop) <= NOISE_KERNEL_MAX_FRAMES)
 
 
-def _noise_device(x, hop, F, average, iterations, return_power):
+def _noise_ola_in_kernel_range(x: torch.Tensor, hop: int, F: int) -> bool:
+    return _noise_in_kernel_range(x, hop, F) and x.shape[1] < NOISE_OLA_KERNEL_MAX_SAMPLES
+
+
+def _noise_device(x, hop, F, average, iterations, return_power, overlap_add=False):
     B, T = x.shape[0], x.shape[1] // hop
+    name = "ddsp_noise_analysis_ola" if overlap_add else "ddsp_noise_analysis"
     H = torch.empty((B, T, F), device=x.device, dtype=torch.float32)
     p = torch.empty_like(H) if return_power else None
-    ws = torch.empty(_lib.lib().ddsp_noise_analysis_workspace_bytes(B, T, F, hop), device=x.device, dtype=torch.uint8)
+    ws = torch.empty(getattr(_lib.lib(), name + "_workspace_bytes")(B, T, F, hop), device=x.device, dtype=torch.uint8)
     with torch.cuda.device(x.device):
-        rc = _lib.lib().ddsp_noise_analysis(x.data_ptr(), H.data_ptr(), None if p is None else p.data_ptr(), ws.data_ptr(), B, T, F,
-                                            hop, min(average, 2 * T + 1), iterations, torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "ddsp_noise_analysis")
+        rc = getattr(_lib.lib(), name)(x.data_ptr(), H.data_ptr(), None if p is None else p.data_ptr(), ws.data_ptr(), B, T, F,
+                                       hop, min(average, 2 * T + 1), iterations, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, name)
     return H, p
 
 
-def noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=False):
+def noise_analysis(x, hop, n_filters, average=1, iterations=None, return_power=False, overlap_add=False):
     """x [B, T hop] -> H [B, T, n_filters] >= 0 as `FilteredNoise` reads it (with return_power: (H, p), p [B, T, n_filters] the
-    smoothed, lag-windowed spectrum of the averaged autocorrelation that H reproduces in expectation)."""
+    smoothed, lag-windowed spectrum of the averaged autocorrelation that H reproduces in expectation).  overlap_add: the model of
+    FilteredNoise's overlap-add mode (any hop >= 1) instead of the truncated one; iterations=None: 16 and 8 of them."""
     what = "noise_analysis"
+    overlap_add = bool(overlap_add)
+    if iterations is None:
+        iterations = NOISE_OLA_ITERATIONS if overlap_add else NOISE_ITERATIONS
     hop, F, average, iterations = int(hop), int(n_filters), int(average), int(iterations)
     if x.dim() != 2:
         raise ValueError(f"{what}: x must be [B, N], got {tuple(x.shape)}")
     if F < 2 or hop < 1:
         raise ValueError(f"{what}: n_filters must be at least 2 and hop positive, got {F} and {hop}")
-    if hop < 2 * (F - 1):
+    if hop < 2 * (F - 1) and not overlap_add:
         raise ValueError(f"{what}: hop {hop} < 2 (n_filters - 1) = {2 * (F - 1)}: FilteredNoise crops the impulse response there "
-                         "and H is not identifiable")
+                         "and H is not identifiable (its overlap-add mode, overlap_add=True, has no such limit)")
     if average < 1 or average % 2 == 0:
         raise ValueError(f"{what}: average must be an odd count of frames, got {average}")
     if iterations < 0:
@@ -385,7 +455,12 @@ def noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=Fal
     if x.shape[0] == 0:
         H = torch.zeros((0, x.shape[1] // hop, F), dtype=x.dtype, device=x.device)
         return (H, torch.zeros_like(H)) if return_power else H
-    if _noise_in_kernel_range(x, hop, F):
+    if overlap_add:
+        if _noise_ola_in_kernel_range(x, hop, F):
+            H, p = _noise_device(x, hop, F, average, iterations, return_power, overlap_add=True)
+        else:
+            H, p = _noise_ola_torch(x, hop, F, average, iterations)
+    elif _noise_in_kernel_range(x, hop, F):
         H, p = _noise_device(x, hop, F, average, iterations, return_power)
     else:
         H, p = _noise_torch(x, hop, F, average, iterations)
@@ -393,13 +468,16 @@ def noise_analysis(x, hop, n_filters, average=1, iterations=16, return_power=Fal
 
 
 class NoiseAnalyzer(nn.Module):
-    """forward(x [B, T hop], average=1, iterations=16) -> H [B, T, n_noise_filters]: `noise_analysis` at the configuration's
-    n_noise_filters and hop_length.  No parameters."""
+    """forward(x [B, T hop], average=1, iterations=None) -> H [B, T, n_noise_filters]: `noise_analysis` at the configuration's
+    n_noise_filters and hop_length.  overlap_add: None reads conf.noise_overlap_add (off where there is none), as `FilteredNoise`
+    does.  No parameters."""
 
-    def __init__(self, conf):
+    def __init__(self, conf, overlap_add=None):
         super().__init__()
         self.n_filters = conf.n_noise_filters
         self.hop_length = conf.hop_length
+        self.overlap_add = bool(getattr(conf, 'noise_overlap_add', False) if overlap_add is None else overlap_add)
 
-    def forward(self, x, average=1, iterations=16):
-        return noise_analysis(x, self.hop_length, self.n_filters, average=average, iterations=iterations)
+    def forward(self, x, average=1, iterations=None):
+        return noise_analysis(x, self.hop_length, self.n_filters, average=average, iterations=iterations,
+                              overlap_add=self.overlap_add)

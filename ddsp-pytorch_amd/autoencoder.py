@@ -2,8 +2,8 @@
 
   forward(x)                 audio [B, L] -> audio: pads (p // 2, p - p // 2) with p = n_fft - hop so that the loudness frames
                              and the CREPE frames line up with the decoder's hop grid (autoencoder.py:17-22)
-  analyse(x, noise=False)    the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True,
-                             H by noise analysis of the residual (analysis.py)
+  analyse(x, noise=False)    the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True
+                             (the truncated noise model) or noise='overlap_add', H by noise analysis of the residual (analysis.py)
   forward_live(x, hidden, delayed=False)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -39,18 +39,26 @@ class AutoEncoder(nn.Module):
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
         return self.decoder(self.encoder(x))
 
-    def analyse(self, x: torch.Tensor, return_complex: bool = False, noise: bool = False, average: int = 1,
-                iterations: int = 16) -> dict:
+    def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None) -> dict:
         """audio [B, L] -> the oscillator bank's control dict without the decoder's network: the encoder's pitch track (and its
         voicing, where that is on) of the clip padded as forward() pads it, then analysis.harmonic_analysis of the clip cropped to
         its T = L // hop whole frames.  `self.decoder.harmonics(self.analyse(x))` is the harmonic resynthesis of x.
 
         noise=True adds 'H' [B, T, n_noise_filters]: analysis.noise_analysis (with `average` and `iterations`) of the residual
         analysis.harmonic_residual leaves, so that `self.decoder.synthesize(self.analyse(x, noise=True))` is the parametric
-        harmonic-plus-noise resynthesis of x."""
-        if noise and self.decoder.noise.overlap_add:
-            # noise_analysis inverts the truncated model: its H played through the overlap-add would come out too strong
-            raise ValueError("analyse(noise=True) inverts the truncated noise model; it does not apply to a decoder with noise_overlap_add")
+        harmonic-plus-noise resynthesis of x.  noise=True and noise='truncated' invert the truncated noise model (16 iterations
+        unless told otherwise), noise='overlap_add' the overlap-add one (8); each is refused on a decoder built with the other
+        form, whose synthesis would play its H at the wrong level."""
+        if noise not in (False, True, 'truncated', 'overlap_add'):
+            raise ValueError(f"analyse: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
+        overlap_add = noise == 'overlap_add'
+        if noise and not overlap_add and self.decoder.noise.overlap_add:
+            # the truncated model's H played through the overlap-add would come out too strong
+            raise ValueError("analyse(noise=True) inverts the truncated noise model; it does not apply to a decoder with noise_overlap_add: "
+                             "ask for noise='overlap_add'")
+        if overlap_add and not self.decoder.noise.overlap_add:
+            raise ValueError("analyse(noise='overlap_add') inverts the overlap-add noise model; on a decoder without noise_overlap_add its H "
+                             "would come out too weak: ask for noise=True")
         bank = self.decoder.harmonics
         with torch.no_grad():
             z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
@@ -63,7 +71,7 @@ class AutoEncoder(nn.Module):
             return harmonic_analysis(*args, voiced=z.get('voiced'), return_complex=return_complex)
         _, resid, ctrl = harmonic_residual(*args, voiced=z.get('voiced'), return_complex=return_complex)
         ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average,
-                                   iterations=iterations)
+                                   iterations=iterations, overlap_add=overlap_add)
         return ctrl
 
     def live_window(self, x: np.ndarray) -> torch.Tensor:

@@ -575,6 +575,32 @@ int ddsp_noise_analysis(const float *x, float *H, float *power, void *workspace,
                         int iterations, void *stream);
 
 /*
+ * Noise analysis for the overlap-add noise: the inverse of ddsp_noise_ola_forward.  That noise is
+ * stationary, so the model has no truncation weights, products may cross frame boundaries and any hop >= 1 is analysable.
+ * Arguments, layout, workspace rule and error order are ddsp_noise_analysis's.  F >= 2, M = 2 (F - 1), P = L = F - 1, N = T hop,
+ * x[n] = 0 for n >= N:
+ *   1. h[e], |e| <= P - 1: the even response ddsp_noise_ola_forward forms from H (its step 2),
+ *      h[e] = (1/2 + 1/2 cos(2 pi e / M)) (1/M) sum_{k<F} c_k H[k] cos(2 pi k e / M).
+ *   2. with H constant E[y[n] y[n + l]] = 1/3 rho(H)[l], rho(H)[l] = sum_e h[e] h[e + l] (both taps inside |e| <= P - 1); the model
+ *      is R_ola(H)[l] = (hop / 3) rho(H)[l], l in [0, L): no truncation weights, hop only a scale.
+ *   3. r_t[l] = (hop / c_t[l]) sum_{n < hop, t hop + n + l < N} x[t hop + n] x[t hop + n + l], c_t[l] = clamp(N - t hop - l, 0, hop)
+ *      the count of terms (r_t[l] = 0 where it is 0): the expectation is exact at the clip's end too.  A frame whose own samples
+ *      are all zero has r_t = 0 exactly.  rbar_t: the frame average of ddsp_noise_analysis (average odd; it may exceed T).
+ *   4. P: ddsp_noise_analysis's step 4 unchanged.
+ *   5. p = max(P(rbar_t), 0); H^0 = sqrt(3 p / hop); H^{i + 1} = H^i sqrt(p / max(P(R_ola(H^i)), FLT_MIN)); H = H^iterations >= 0.
+ *   6. a sample at n that is not finite reaches the frames t with t hop <= n < t hop + hop + L - 1, widened by the averaging
+ *      window, and nothing else.
+ * workspace: ddsp_noise_analysis_ola_workspace_bytes(B, T, F, hop) bytes (0 outside the range), 16-byte aligned.  Range:
+ * 2 <= F <= 257, 1 <= hop <= 1024, B T <= 2^31 - 1, T hop < 2^31 - 8192: anything else is DDSP_ERANGE.  A null x, H or workspace,
+ * T, F - 1, hop or iterations + 1 that is not positive, an average that is even or below 1: DDSP_EINVAL, before anything touches
+ * the device; B == 0 returns 0.  Three launches, no atomics on global memory, no allocation, no host synchronisation; every sum
+ * has one order: a row's results are the same bits from run to run and whatever else is in the batch.
+ */
+size_t ddsp_noise_analysis_ola_workspace_bytes(long B, long T, int F, int hop);
+int ddsp_noise_analysis_ola(const float *x, float *H, float *power, void *workspace, long B, long T, int F, int hop, int average,
+                            int iterations, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
