@@ -110,6 +110,8 @@ SIGNATURES = {
     "ddsp_harm_workspace_bytes": (_size, [_long, _long, _i32]),
     "ddsp_harm_analysis": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_harm_resynth": (_i32, [_vp] * 6 + [_long, _long, _i32, _i32, _i32, _u32, _vp]),
+    "ddsp_harm_refine_workspace_bytes": (_size, [_long, _long, _i32]),
+    "ddsp_harm_refine": (_i32, [_vp] * 8 + [_long, _long, _i32, _i32, _i32, _i32, _f32, _u32, _vp]),
     "ddsp_noise_analysis_workspace_bytes": (_size, [_long, _long, _i32, _i32]),
     "ddsp_noise_analysis": (_i32, [_vp] * 4 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_noise_analysis_ola_workspace_bytes": (_size, [_long, _long, _i32, _i32]),

@@ -4,11 +4,19 @@ Given audio [B, N] and its pitch track f0 [B, T, 1] (N = T hop), the per-frame c
 along the oscillator's own phase track, the bank's controls a = sum_k |C| and c = |C| / a, the harmonic part of the audio and
 the residual the harmonics do not explain:
 
-  harmonic_analysis(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False) -> dict(f0, a, c[, C])
+  harmonic_analysis(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False, refine=0,
+                    max_cents=50.0) -> dict(f0, a, c[, C])
   harmonic_resynthesis(C, f0, hop, sample_rate) -> harm [B, T hop]
-  harmonic_residual(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False)
-                                                                        -> (harm, resid, the dict of harmonic_analysis)
-  HarmonicAnalyzer(conf)  nn.Module without parameters over conf.n_harmonics / sample_rate / hop_length / n_fft (the window)
+  harmonic_residual(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False, refine=0,
+                    max_cents=50.0)                                     -> (harm, resid, the dict of harmonic_analysis)
+  refine_f0(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, iterations=2, max_cents=50.0) -> f0 [B, T, 1]
+  HarmonicAnalyzer(conf, refine=0)  nn.Module without parameters over conf.n_harmonics / sample_rate / hop_length / n_fft (the window)
+
+`refine_f0` reads the pitch back from the harmonics (ddsp_harm_refine): per step and per frame whose
+window lies inside the clip, the |C_k|^2-weighted least-squares fit of the harmonics' reassigned frequency deviations replaces the
+frame's f0 by the window mean of the track plus that deviation; every frame stays within `max_cents` of the track given.  A decoded
+track is up to half a 20-cent bin off, which puts high harmonics outside their analysis window; `refine=N` in the analysis
+functions runs N such steps first and demodulates with (and returns) the refined track.  refine=0 is the analysis as it was.
 
 The returned `f0` is the track the analysis demodulated with: the input with frames that are not finite or <= 0 set to 0, so
 that `OscillatorBank` on the dict runs the same phases.  CUDA fp32 tensors with an even win_length <= 4096 and n_harmonics <= 256
@@ -167,6 +175,53 @@ def _resynth_torch(C, f0, hop, sample_rate):
     return harm
 
 
+def _refine_torch(audio, f0, anchor, voiced, hop, sample_rate, H, W, max_cents):
+    """One refinement step as torch ops in f0's dtype (the phase track and the window mean in fp64): f0, anchor [B, T, 1] -> g."""
+    dt, dev = audio.dtype, audio.device
+    B, N = audio.shape
+    T = f0.shape[1]
+    lead = (W - hop) // 2
+    alive = torch.isfinite(f0) & (f0 > 0)
+    if voiced is not None:
+        alive = alive & voiced.bool()
+    inter = [t for t in range(T) if t * hop - lead >= 0 and t * hop - lead + W <= N]
+    g = f0.clone()
+    if inter:
+        t_lo, t_hi = inter[0], inter[-1]
+        theta = _theta(f0, hop, sample_rate)
+        j = torch.arange(W, device=dev)
+        w = 0.5 - 0.5 * torch.cos(2 * math.pi * j.double() / W)
+        wd = (math.pi / W) * torch.sin(2 * math.pi * j.double() / W)
+        k = torch.arange(1, H + 1, device=dev).double()
+        keep = _harmonic_mask(f0, voiced, sample_rate, H)
+        zero = torch.zeros((), dtype=dt, device=dev)
+        step = max(1, _CHUNK_ELEMENTS // max(1, B * W * H))
+        for t0 in range(t_lo, t_hi + 1, step):
+            t = torch.arange(t0, min(t_hi + 1, t0 + step), device=dev)
+            idx = (t * hop - lead)[:, None] + j[None, :]                              # [Tc, W], all inside the clip
+            x = audio[:, idx]                                                         # [B, Tc, W]
+            wx, wdx = w.to(dt) * x, wd.to(dt) * x
+            ang = (2 * math.pi * ((theta[:, idx][..., None] * k) % 1.0)).to(dt)       # [B, Tc, W, H]
+            cos, sin = torch.cos(ang), torch.sin(ang)
+            kept = keep[:, t0:t0 + len(t)]
+            cr, ci = (torch.where(kept, v, zero) for v in (torch.einsum('btw,btwh->bth', wx, cos), -torch.einsum('btw,btwh->bth', wx, sin)))
+            dr, di = (torch.where(kept, v, zero) for v in (torch.einsum('btw,btwh->bth', wdx, cos), -torch.einsum('btw,btwh->bth', wdx, sin)))
+            kk = k.to(dt)
+            num = (kk * (di * cr - dr * ci)).sum(-1, keepdim=True)
+            den = (kk * kk * (cr * cr + ci * ci)).sum(-1, keepdim=True)
+            mean = ((w[None, None, :] * _up(_clean_f0(f0).double(), idx.reshape(-1), hop).reshape(B, len(t), W)).sum(-1, keepdim=True)
+                    / w.sum()).to(dt)
+            value = mean - (sample_rate / (2 * math.pi)) * num / den
+            here = f0[:, t0:t0 + len(t)]
+            g[:, t0:t0 + len(t)] = torch.where(alive[:, t0:t0 + len(t)] & (den != 0) & torch.isfinite(value), value, here)
+        one = torch.ones((), dtype=dt, device=dev)
+        for edge, frames in ((t_lo, slice(0, t_lo)), (t_hi, slice(t_hi + 1, T))):
+            ratio = torch.where(alive[:, edge:edge + 1], g[:, edge:edge + 1] / f0[:, edge:edge + 1], one)
+            g[:, frames] = torch.where(alive[:, frames], f0[:, frames] * ratio, f0[:, frames])
+    clamped = torch.minimum(torch.maximum(g, anchor * 2.0 ** (-max_cents / 1200.0)), anchor * 2.0 ** (max_cents / 1200.0))
+    return torch.where(alive, clamped, f0)
+
+
 # -------------------------------------------------------------------------------------------------------------- device path
 
 def _workspace(B, T, hop, device):
@@ -200,7 +255,56 @@ def _resynth_device(C, f0, audio, hop, sample_rate, workspace, phase_ready):
     return harm, resid
 
 
+def _refine_device(audio, f0, voiced, hop, sample_rate, H, W, iterations, max_cents):
+    """`iterations` steps of ddsp_harm_refine from f0 [B, T, 1], anchored at f0."""
+    B, T = f0.shape[:2]
+    v = None if voiced is None else voiced.detach().to(torch.uint8).contiguous()
+    ws = torch.empty(_lib.lib().ddsp_harm_refine_workspace_bytes(B, T, hop), device=audio.device, dtype=torch.uint8)
+    track = f0
+    with torch.cuda.device(audio.device):
+        for _ in range(iterations):
+            out = torch.empty_like(f0)
+            rc = _lib.lib().ddsp_harm_refine(audio.data_ptr(), track.data_ptr(), f0.data_ptr(), None if v is None else v.data_ptr(),
+                                             out.data_ptr(), None, None, ws.data_ptr(), B, T, hop, W, H, sample_rate, max_cents, 0,
+                                             torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "ddsp_harm_refine")
+            track = out
+    return track
+
+
 # ------------------------------------------------------------------------------------------------------------------- public
+
+def _refined(audio, f0, voiced, hop, sample_rate, H, W, iterations, max_cents):
+    """f0 after `iterations` steps (prepared tensors, B > 0); iterations = 0 returns f0 itself and launches nothing."""
+    if iterations == 0:
+        return f0
+    if _in_kernel_range(audio, W, H):
+        return _refine_device(audio, f0, voiced, hop, sample_rate, H, W, iterations, max_cents)
+    track = f0
+    for _ in range(iterations):
+        track = _refine_torch(audio, track, f0, voiced, hop, sample_rate, H, W, max_cents)
+    return track
+
+
+def _check_refine(iterations, max_cents, what):
+    iterations, max_cents = int(iterations), float(max_cents)
+    if iterations < 0:
+        raise ValueError(f"{what}: the number of refinement steps must be at least 0, got {iterations}")
+    if not 0 < max_cents < math.inf:
+        raise ValueError(f"{what}: max_cents must be positive and finite, got {max_cents}")
+    return iterations, max_cents
+
+
+def refine_f0(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, iterations=2, max_cents=50.0):
+    """-> f0 [B, T, 1] after `iterations` refinement steps, every frame within `max_cents` of the track given; frames that are
+    not finite, not positive or not voiced come back as they are."""
+    B, T, hop, sample_rate, H = _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, "refine_f0")
+    iterations, max_cents = _check_refine(iterations, max_cents, "refine_f0")
+    audio, f0, voiced = _prepare(audio, f0, voiced)
+    if B == 0 or iterations == 0:
+        return f0.clone()
+    return _refined(audio, f0, voiced, hop, sample_rate, H, int(win_length), iterations, max_cents)
+
 
 def _controls(f0, a, c, C, return_complex):
     out = dict(f0=_clean_f0(f0), a=a, c=c)
@@ -222,14 +326,18 @@ def _prepare(audio, f0, voiced):
     return audio.contiguous(), f0.detach().to(audio.dtype).contiguous(), None if voiced is None else voiced.detach()
 
 
-def harmonic_residual(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False):
-    """-> (harm [B, N], resid = audio - harm, dict(f0, a, c[, C])): the harmonic part of `audio` along `f0` and what is left."""
+def harmonic_residual(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False, refine=0,
+                      max_cents=50.0):
+    """-> (harm [B, N], resid = audio - harm, dict(f0, a, c[, C])): the harmonic part of `audio` along `f0` (after `refine` steps of
+    `refine_f0`) and what is left."""
     B, T, hop, sample_rate, H = _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, "harmonic_residual")
+    refine, max_cents = _check_refine(refine, max_cents, "harmonic_residual")
     W = int(win_length)
     audio, f0, voiced = _prepare(audio, f0, voiced)
     if B == 0:
         C, a, c = _empty(f0, T, hop, H, audio.dtype)
         return torch.zeros_like(audio), torch.zeros_like(audio), _controls(f0, a, c, C, return_complex)
+    f0 = _refined(audio, f0, voiced, hop, sample_rate, H, W, refine, max_cents)
     if _in_kernel_range(audio, W, H):
         ws = _workspace(B, T, hop, audio.device)
         C, a, c = _analysis_device(audio, f0, voiced, hop, sample_rate, H, W, ws)
@@ -241,14 +349,19 @@ def harmonic_residual(audio, f0, hop, sample_rate, n_harmonics, win_length, voic
     return harm, resid, _controls(f0, a, c, C, return_complex)
 
 
-def harmonic_analysis(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False):
-    """-> dict(f0 [B, T, 1], a [B, T, 1], c [B, T, H]) as `OscillatorBank` reads it, plus C (complex [B, T, H]) when asked."""
+def harmonic_analysis(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced=None, return_complex=False, refine=0,
+                      max_cents=50.0):
+    """-> dict(f0 [B, T, 1], a [B, T, 1], c [B, T, H]) as `OscillatorBank` reads it, plus C (complex [B, T, H]) when asked.
+    refine: steps of `refine_f0` (each within `max_cents` of f0) before the analysis; the dict's f0 is then the refined track."""
     B, T, hop, sample_rate, H = _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, "harmonic_analysis")
+    refine, max_cents = _check_refine(refine, max_cents, "harmonic_analysis")
     W = int(win_length)
     audio, f0, voiced = _prepare(audio, f0, voiced)
     if B == 0:
         C, a, c = _empty(f0, T, hop, H, audio.dtype)
-    elif _in_kernel_range(audio, W, H):
+        return _controls(f0, a, c, C, return_complex)
+    f0 = _refined(audio, f0, voiced, hop, sample_rate, H, W, refine, max_cents)
+    if _in_kernel_range(audio, W, H):
         C, a, c = _analysis_device(audio, f0, voiced, hop, sample_rate, H, W, _workspace(B, T, hop, audio.device))
     else:
         C, a, c = _analysis_torch(audio, f0, voiced, hop, sample_rate, H, W)
@@ -274,17 +387,19 @@ def harmonic_resynthesis(C, f0, hop, sample_rate):
 
 class HarmonicAnalyzer(nn.Module):
     """forward(audio [B, T hop], f0 [B, T, 1], voiced=None) -> dict(f0, a, c): `harmonic_analysis` at the configuration's
-    n_harmonics, sample_rate, hop_length and n_fft (the window).  No parameters."""
+    n_harmonics, sample_rate, hop_length and n_fft (the window), after `refine` steps of `refine_f0`.  No parameters."""
 
-    def __init__(self, conf):
+    def __init__(self, conf, refine=0):
         super().__init__()
+        self.refine = _check_refine(refine, 50.0, "HarmonicAnalyzer")[0]
         self.n_harmonics = conf.n_harmonics
         self.sample_rate = conf.sample_rate
         self.hop_length = conf.hop_length
         self.win_length = conf.n_fft
 
     def forward(self, audio, f0, voiced=None):
-        return harmonic_analysis(audio, f0, self.hop_length, self.sample_rate, self.n_harmonics, self.win_length, voiced=voiced)
+        return harmonic_analysis(audio, f0, self.hop_length, self.sample_rate, self.n_harmonics, self.win_length, voiced=voiced,
+                                 refine=self.refine)
 
 
 # ------------------------------------------------------------------------------------------------------------ noise analysis

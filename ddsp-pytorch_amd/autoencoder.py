@@ -2,8 +2,10 @@
 
   forward(x)                 audio [B, L] -> audio: pads (p // 2, p - p // 2) with p = n_fft - hop so that the loudness frames
                              and the CREPE frames line up with the decoder's hop grid (autoencoder.py:17-22)
-  analyse(x, noise=False)    the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True
-                             (the truncated noise model) or noise='overlap_add', H by noise analysis of the residual (analysis.py)
+  analyse(x, noise=False, refine=0)
+                             the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True
+                             (the truncated noise model) or noise='overlap_add', H by noise analysis of the residual (analysis.py);
+                             refine=N first moves the decoded f0 off its 20-cent grid by N steps of analysis.refine_f0
   forward_live(x, hidden, delayed=False)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -39,7 +41,8 @@ class AutoEncoder(nn.Module):
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
         return self.decoder(self.encoder(x))
 
-    def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None) -> dict:
+    def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,
+                refine: int = 0) -> dict:
         """audio [B, L] -> the oscillator bank's control dict without the decoder's network: the encoder's pitch track (and its
         voicing, where that is on) of the clip padded as forward() pads it, then analysis.harmonic_analysis of the clip cropped to
         its T = L // hop whole frames.  `self.decoder.harmonics(self.analyse(x))` is the harmonic resynthesis of x.
@@ -48,7 +51,10 @@ class AutoEncoder(nn.Module):
         analysis.harmonic_residual leaves, so that `self.decoder.synthesize(self.analyse(x, noise=True))` is the parametric
         harmonic-plus-noise resynthesis of x.  noise=True and noise='truncated' invert the truncated noise model (16 iterations
         unless told otherwise), noise='overlap_add' the overlap-add one (8); each is refused on a decoder built with the other
-        form, whose synthesis would play its H at the wrong level."""
+        form, whose synthesis would play its H at the wrong level.
+
+        refine=N runs N steps of analysis.refine_f0 on the encoder's track before the analysis (a decoded track is a bin centre,
+        up to 10 cents off); the dict's f0 is then the refined track.  refine=0 is the analysis along the encoder's own track."""
         if noise not in (False, True, 'truncated', 'overlap_add'):
             raise ValueError(f"analyse: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
         overlap_add = noise == 'overlap_add'
@@ -68,8 +74,8 @@ class AutoEncoder(nn.Module):
             raise ValueError(f"the encoder returned {frames} frames of hop {self.hop_length} for {x.shape[-1]} samples")
         args = (x[:, :frames * self.hop_length], f0, self.hop_length, bank.sample_rate, bank.n_harmonics, self.padding + self.hop_length)
         if not noise:
-            return harmonic_analysis(*args, voiced=z.get('voiced'), return_complex=return_complex)
-        _, resid, ctrl = harmonic_residual(*args, voiced=z.get('voiced'), return_complex=return_complex)
+            return harmonic_analysis(*args, voiced=z.get('voiced'), return_complex=return_complex, refine=refine)
+        _, resid, ctrl = harmonic_residual(*args, voiced=z.get('voiced'), return_complex=return_complex, refine=refine)
         ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average,
                                    iterations=iterations, overlap_add=overlap_add)
         return ctrl

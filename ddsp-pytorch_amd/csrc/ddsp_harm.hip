@@ -11,6 +11,11 @@
 //                partial sums are added in wavefront order, a in a fixed butterfly: the same bits whatever the batch.
 //   resynthesis  one workgroup per (row, segment between two frame centres): all its samples interpolate one frame pair, staged
 //                in LDS as C[t] and C[t + 1] - C[t]; a lane owns a sample and walks the harmonics up to the last non-zero one.
+//   refinement   (section 14a) a sibling of the analysis over the frames whose window lies inside the clip: w audio, w' audio (w' the
+//                window's derivative per sample) and the phase words -> LDS, C_k and D_k by four FMAs behind the same cosine / sine,
+//                num = sum_k k Im(D_k conj C_k) and den = sum_k k^2 |C_k|^2 in the analysis' fixed butterfly, and
+//                g[t] = (window mean of up(f0*)) - (sr / 2 pi) num / den; a second launch of one thread per frame carries g to
+//                the frames at the clip's ends and clamps every frame around the anchor track.
 // The matrix cores are not used: the operand exp(-2 pi i k theta[j]) (H x W) is generated per frame and multiplies one vector,
 // so nothing is reused; the work is the sine / cosine pair per (harmonic, sample), which is VALU work.
 #include <hip/hip_runtime.h>
@@ -308,6 +313,231 @@ __global__ void __launch_bounds__(kThreads) harm_resynth_kernel(const float2 *__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- refinement (section 14a)
+
+// the periodic Hann window and its derivative per sample, (pi / W) sin(2 pi j / W), evaluated in fp64 and rounded once
+__global__ void harm_window_pair_kernel(float *__restrict__ win, float *__restrict__ dwin, int W)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < W) {
+        win[j] = (float)(0.5 - 0.5 * cospi(2.0 * (double)j / (double)W));
+        dwin[j] = (float)(M_PI / (double)W * sinpi(2.0 * (double)j / (double)W));
+    }
+}
+
+// up(f0*)[n] in fp64: the interpolation of phase_increment, before the division by the sample rate
+__device__ __forceinline__ double up_f0(const float *__restrict__ f, long T, long hop, long n, double inv_2hop)
+{
+    const long m = 2 * n + 1 - hop;
+    long i0 = 0, rem = 0;
+    if (m > 0) {
+        i0 = (long)((double)m * inv_2hop);
+        rem = m - 2 * hop * i0;
+        if (rem < 0) { --i0; rem += 2 * hop; }
+        if (rem >= 2 * hop) { ++i0; rem -= 2 * hop; }
+    }
+    if (i0 >= T - 1) { i0 = T - 1; rem = 0; }
+    const long i1 = i0 + 1 < T ? i0 + 1 : T - 1;
+    const double a = (double)live_f0(f[i0]), b = (double)live_f0(f[i1]);
+    return a + (b - a) * ((double)rem * inv_2hop);
+}
+
+// harm_window_sums with the second window beside the first: C = sum_j (w x)[j] e, D = sum_j (w' x)[j] e, e = exp(-2 pi i k theta[j])
+template <int LIVE>
+__device__ __forceinline__ void harm_refine_sums(const float *xs_, const float *ds_, const uint32_t *ps_, int chunk, int lane,
+                                                 float (&cr)[kSlots], float (&ci)[kSlots], float (&dr)[kSlots], float (&di)[kSlots])
+{
+    const float4 *xs = reinterpret_cast<const float4 *>(xs_);
+    const float4 *ds = reinterpret_cast<const float4 *>(ds_);
+    const uint4 *ps = reinterpret_cast<const uint4 *>(ps_);
+    for (int q = 0; q < chunk / 4; ++q) {
+        const float4 x4 = xs[q], d4 = ds[q];
+        const uint4 p4 = ps[q];
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
+        const float dv[4] = {d4.x, d4.y, d4.z, d4.w};
+        const uint32_t pv[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            uint32_t word = pv[e] * (uint32_t)(lane + 1);
+#pragma unroll
+            for (int sl = 0; sl < LIVE; ++sl, word += pv[e] << 6) {
+                const float ang = turns_of(word);
+                const float c = __builtin_amdgcn_cosf(ang), s = __builtin_amdgcn_sinf(ang);
+                cr[sl] = __fmaf_rn(xv[e], c, cr[sl]);
+                ci[sl] = __fmaf_rn(-xv[e], s, ci[sl]);
+                dr[sl] = __fmaf_rn(dv[e], c, dr[sl]);
+                di[sl] = __fmaf_rn(-dv[e], s, di[sl]);
+            }
+        }
+    }
+}
+
+// sum of v over the 256 threads in every thread: the butterfly inside a wavefront, then the wavefronts in order
+__device__ __forceinline__ float refine_block_sum(float v, float *wave_part, int lane, int wv)
+{
+    const float ws = wave_sum(v);
+    if (lane == 0) wave_part[wv] = ws;
+    __syncthreads();
+    float total = wave_part[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) total += wave_part[w];
+    __syncthreads();                                            // wave_part is rewritten by the next sum
+    return total;
+}
+
+// One workgroup per (row, frame).  raw [B, T] receives g[t] for a frame that is alive and whose window [t_lo, t_hi] lies inside the
+// clip, and the bits of f0[t] for every other one (and where den = 0 or g is not finite); num and den (nullable) the two sums, 0
+// where none were formed.
+__global__ void __launch_bounds__(kThreads) harm_refine_kernel(const float *__restrict__ audio, const float *__restrict__ f0,
+                                                               const uint8_t *__restrict__ voiced,
+                                                               const uint32_t *__restrict__ theta, const float *__restrict__ win,
+                                                               const float *__restrict__ dwin, float *__restrict__ raw,
+                                                               float *__restrict__ num_out, float *__restrict__ den_out, long T,
+                                                               long hop, long N, long lead, int W, int H, int chunk, float nyquist,
+                                                               long nframes, long t_lo, long t_hi, double inv_2hop, double hz_per_rad)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *wx = smem;                                           // [kWaves chunk] w[j] audio[s + j]
+    float *wdx = smem + kWaves * chunk;                         // [kWaves chunk] w'[j] audio[s + j]
+    uint32_t *ph = reinterpret_cast<uint32_t *>(smem + 2 * kWaves * chunk);     // [kWaves chunk] theta[s + j]
+    float *part = smem;                                         // [kWaves][C re, C im, D re, D im][kMaxH], over the staged window
+    __shared__ float wave_part[kWaves];
+    __shared__ double wave_mean[2 * kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int slots = (H + 63) / 64;
+
+    for (long fr = blockIdx.x; fr < nframes; fr += gridDim.x) {
+        const long row = fr / T, t = fr - row * T;
+        const float f = f0[fr];
+        const bool alive = fabsf(f) < INFINITY && f > 0.0f && (!voiced || voiced[fr] != 0);
+        int live = 0;
+        if (alive && t >= t_lo && t <= t_hi)
+            for (int sl = 0; sl < slots; ++sl)
+                if (!((float)(64 * sl + 1) * f > nyquist)) live = sl + 1;
+        live = __builtin_amdgcn_readfirstlane(live);
+        if (live == 0) {                                        // (the same for the whole workgroup)
+            if (tid == 0) {
+                reinterpret_cast<uint32_t *>(raw)[fr] = reinterpret_cast<const uint32_t *>(f0)[fr];
+                if (num_out) num_out[fr] = 0.0f;
+                if (den_out) den_out[fr] = 0.0f;
+            }
+            continue;
+        }
+
+        const long s = t * hop - lead;                          // 0 <= s and s + W <= N
+        double mw = 0.0, mf = 0.0;                              // sum_j w[j], sum_j w[j] up(f0*)[s + j], j ascending per thread
+        for (int j = tid; j < kWaves * chunk; j += kThreads) {
+            float x = 0.0f, d = 0.0f;
+            uint32_t p = 0;
+            if (j < W) {
+                const long n = row * N + s + j;
+                const float wj = win[j], a = audio[n];
+                x = __fmul_rn(wj, a);
+                d = __fmul_rn(dwin[j], a);
+                p = theta[n];
+                mw += (double)wj;
+                mf = fma((double)wj, up_f0(f0 + row * T, T, hop, s + j, inv_2hop), mf);
+            }
+            wx[j] = x;
+            wdx[j] = d;
+            ph[j] = p;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mw += __shfl_xor(mw, o);
+            mf += __shfl_xor(mf, o);
+        }
+        if (lane == 0) {
+            wave_mean[2 * wv] = mw;
+            wave_mean[2 * wv + 1] = mf;
+        }
+        __syncthreads();
+        double mean = 0.0;                                      // read here: the next frame's sums may be written before this one ends
+        if (tid == 0) {
+            double sw = wave_mean[0], sf = wave_mean[1];
+            for (int w = 1; w < kWaves; ++w) {                  // wavefront order
+                sw += wave_mean[2 * w];
+                sf += wave_mean[2 * w + 1];
+            }
+            mean = sf / sw;
+        }
+
+        float cr[kSlots], ci[kSlots], dr[kSlots], di[kSlots];
+#pragma unroll
+        for (int sl = 0; sl < kSlots; ++sl) cr[sl] = ci[sl] = dr[sl] = di[sl] = 0.0f;
+        const float *xs = wx + wv * chunk, *ds = wdx + wv * chunk;
+        const uint32_t *ps = ph + wv * chunk;
+        switch (live) {
+        case 1: harm_refine_sums<1>(xs, ds, ps, chunk, lane, cr, ci, dr, di); break;
+        case 2: harm_refine_sums<2>(xs, ds, ps, chunk, lane, cr, ci, dr, di); break;
+        case 3: harm_refine_sums<3>(xs, ds, ps, chunk, lane, cr, ci, dr, di); break;
+        case 4: harm_refine_sums<4>(xs, ds, ps, chunk, lane, cr, ci, dr, di); break;
+        default: break;
+        }
+        __syncthreads();                                        // every wavefront has read its share: part overwrites the window
+#pragma unroll
+        for (int sl = 0; sl < kSlots; ++sl) {
+            const int h = 64 * sl + lane;
+            if (h < H) {
+                part[(4 * wv) * kMaxH + h] = cr[sl];
+                part[(4 * wv + 1) * kMaxH + h] = ci[sl];
+                part[(4 * wv + 2) * kMaxH + h] = dr[sl];
+                part[(4 * wv + 3) * kMaxH + h] = di[sl];
+            }
+        }
+        __syncthreads();
+
+        float tn = 0.0f, td = 0.0f;
+        const int h = tid;                                      // a thread per harmonic
+        if (h < H && !((float)(h + 1) * f > nyquist)) {
+            float c_re = part[h], c_im = part[kMaxH + h], d_re = part[2 * kMaxH + h], d_im = part[3 * kMaxH + h];
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) {                  // wavefront order
+                c_re += part[(4 * w) * kMaxH + h];
+                c_im += part[(4 * w + 1) * kMaxH + h];
+                d_re += part[(4 * w + 2) * kMaxH + h];
+                d_im += part[(4 * w + 3) * kMaxH + h];
+            }
+            const float k = (float)(h + 1);
+            tn = __fmul_rn(k, __fmaf_rn(d_im, c_re, -__fmul_rn(d_re, c_im)));                  // k Im(D conj C)
+            td = __fmul_rn(__fmul_rn(k, k), __fmaf_rn(c_im, c_im, __fmul_rn(c_re, c_re)));     // k^2 |C|^2
+        }
+        const float num = refine_block_sum(tn, wave_part, lane, wv);
+        const float den = refine_block_sum(td, wave_part, lane, wv);    // (its last barrier also frees part for the next frame)
+        if (tid == 0) {
+            const float g = (float)(mean - hz_per_rad * ((double)num / (double)den));
+            raw[fr] = (den != 0.0f && fabsf(g) < INFINITY) ? g : f;
+            if (num_out) num_out[fr] = num;
+            if (den_out) den_out[fr] = den;
+        }
+    }
+}
+
+// One thread per frame: an alive frame before t_lo (after t_hi) moves by the ratio raw / f0 of frame t_lo (t_hi), where that one is
+// alive; every alive frame is clamped to anchor 2^(+-max_cents / 1200); a frame that is not alive keeps its bits.  t_lo > t_hi:
+// no window lies inside the clip.  f0_out must not overlap f0 or raw.
+__global__ void harm_refine_finish_kernel(const float *__restrict__ f0, const float *__restrict__ anchor,
+                                          const uint8_t *__restrict__ voiced, const float *__restrict__ raw, float *__restrict__ f0_out,
+                                          long T, long nframes, long t_lo, long t_hi, double down, double up)
+{
+    for (long fr = (long)blockIdx.x * blockDim.x + threadIdx.x; fr < nframes; fr += (long)gridDim.x * blockDim.x) {
+        const long row = fr / T, t = fr - row * T;
+        const float f = f0[fr];
+        if (!(fabsf(f) < INFINITY && f > 0.0f && (!voiced || voiced[fr] != 0))) {
+            reinterpret_cast<uint32_t *>(f0_out)[fr] = reinterpret_cast<const uint32_t *>(f0)[fr];
+            continue;
+        }
+        double g = (double)raw[fr];
+        if (t_lo <= t_hi && (t < t_lo || t > t_hi)) {
+            const long e = row * T + (t < t_lo ? t_lo : t_hi);
+            const float fe = f0[e];
+            if (fabsf(fe) < INFINITY && fe > 0.0f && (!voiced || voiced[e] != 0)) g = (double)f * ((double)raw[e] / (double)fe);
+        }
+        const double a = (double)anchor[fr];
+        f0_out[fr] = (float)fmin(fmax(g, a * down), a * up);
+    }
+}
+
 // N = T hop; false unless B N and B (T + 1) H are at most 2^56 elements (byte counts and indices then fit a long)
 bool harm_sizes(long B, long T, int hop, int H, long *N, long *total)
 {
@@ -397,5 +627,53 @@ extern "C" int ddsp_harm_resynth(const float *C, const float *f0, const float *a
     const int blocks = (int)(nseg < kMaxBlocks ? nseg : kMaxBlocks);
     hipLaunchKernelGGL(harm_resynth_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, reinterpret_cast<const float2 *>(C), theta,
                        audio, harm, resid, T, (long)hop, N, H, nseg);
+    return (int)hipGetLastError();
+}
+
+// the refinement's workspace: that of the analysis, then the derivative window [kMaxW], then raw [B, T]
+extern "C" size_t ddsp_harm_refine_workspace_bytes(long B, long T, int hop)
+{
+    const size_t base = ddsp_harm_workspace_bytes(B, T, hop);
+    return base ? base + kWindowBytes + align256((size_t)(B * T) * sizeof(float)) : 0;
+}
+
+extern "C" int ddsp_harm_refine(const float *audio, const float *f0_in, const float *f0_anchor, const uint8_t *voiced, float *f0_out,
+                                float *num_out, float *den_out, void *workspace, long B, long T, int hop, int W, int H,
+                                int sample_rate, float max_cents, unsigned flags, void *stream)
+{
+    if (B == 0) return 0;
+    if (!audio || !f0_in || !f0_anchor || !f0_out || !workspace || B < 0 || T <= 0 || hop <= 0 || W < 2 || (W & 1) || H <= 0 ||
+        sample_rate <= 0 || !(max_cents > 0.0f) || !(max_cents < INFINITY) || flags || f0_out == f0_in)
+        return DDSP_EINVAL;
+    if (((uintptr_t)workspace & 15) != 0) return DDSP_EINVAL;
+    long N, total;
+    if (W > kMaxW || H > kMaxH || !harm_sizes(B, T, hop, H, &N, &total)) return DDSP_ERANGE;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = harm_phase_pass(f0_in, workspace, B, T, hop, N, sample_rate, s);
+    if (rc) return rc;
+    char *after = static_cast<char *>(workspace) + ddsp_harm_workspace_bytes(B, T, hop);
+    float *win = static_cast<float *>(workspace), *dwin = reinterpret_cast<float *>(after);
+    float *raw = reinterpret_cast<float *>(after + kWindowBytes);
+    const uint32_t *theta = harm_theta(workspace, B, N);
+    hipLaunchKernelGGL(harm_window_pair_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, win, dwin, W);
+    if ((rc = (int)hipGetLastError())) return rc;
+    const long d = (long)W - hop;
+    const long lead = d >= 0 ? d / 2 : -((-d + 1) / 2);         // floor((W - hop) / 2)
+    const long t_lo = lead > 0 ? (lead + hop - 1) / hop : 0;    // the frames t_lo .. t_hi have 0 <= s_t and s_t + W <= N
+    const long room = N - W + lead;
+    const long t_hi = room < 0 ? -1 : (room / hop < T - 1 ? room / hop : T - 1);
+    const int chunk = ((W + 15) / 16) * 4;
+    const size_t staged = (size_t)3 * kWaves * chunk, sums = (size_t)4 * kWaves * kMaxH;        // the sums reuse the window's LDS
+    const size_t lds = (staged > sums ? staged : sums) * sizeof(float);
+    const long nframes = B * T;
+    const int blocks = (int)(nframes < kMaxBlocks ? nframes : kMaxBlocks);
+    hipLaunchKernelGGL(harm_refine_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, audio, f0_in, voiced, theta, win, dwin, raw,
+                       num_out, den_out, T, (long)hop, N, lead, W, H, chunk, (float)(sample_rate / 2), nframes, t_lo, t_hi,
+                       1.0 / (2.0 * (double)hop), (double)sample_rate / (2.0 * M_PI));
+    if ((rc = (int)hipGetLastError())) return rc;
+    const long per = (nframes + 255) / 256;
+    hipLaunchKernelGGL(harm_refine_finish_kernel, dim3((unsigned)(per < kMaxBlocks ? per : kMaxBlocks)), dim3(256), 0, s, f0_in,
+                       f0_anchor, voiced, raw, f0_out, T, nframes, t_lo, t_hi, exp2(-(double)max_cents / 1200.0),
+                       exp2((double)max_cents / 1200.0));
     return (int)hipGetLastError();
 }

@@ -547,6 +547,25 @@ int ddsp_harm_analysis(const float *audio, const float *f0, const uint8_t *voice
                        long B, long T, int hop, int W, int H, int sample_rate, void *stream);
 int ddsp_harm_resynth(const float *C, const float *f0, const float *audio, float *harm, float *resid, void *workspace, long B,
                       long T, int hop, int H, int sample_rate, unsigned flags, void *stream);
+/*
+ * One step of the f0 refinement by frequency reassignment, in the notation above.  Frame t is interior
+ * when 0 <= s_t and s_t + W <= N, and alive when f0_in[t] is finite and positive and voiced (nullable) is not 0 there.
+ *   For an interior, alive frame, over the harmonics k the mask of the analysis keeps, with w'[j] = (pi / W) sin(2 pi j / W):
+ *     C_k = sum_j w[j] audio[s_t + j] exp(-2 pi i k theta[s_t + j]), D_k the same sum with w' in place of w (theta from f0_in),
+ *     num = sum_k k Im(D_k conj(C_k)),  den = sum_k k^2 |C_k|^2,  mean = sum_j w[j] up(f0_in*)[s_t + j] / sum_j w[j],
+ *     g[t] = mean - (sample_rate / 2 pi) num / den, and g[t] = f0_in[t] where den = 0 or that is not finite.
+ *   An alive frame before the first interior frame t_lo gets f0_in[t] g[t_lo] / f0_in[t_lo], one after the last interior frame
+ *   t_hi f0_in[t] g[t_hi] / f0_in[t_hi] (the ratio is 1 where that frame is not alive); without an interior frame g = f0_in.
+ *   Every alive g[t] is then clamped to f0_anchor[t] 2^(+-max_cents / 1200); a frame that is not alive keeps its bits.
+ * -> f0_out [B, T] (not f0_in itself) and, where not NULL, num_out and den_out [B, T] (0 on the frames that are not measured).
+ * It runs the phase pass on f0_in and three more launches; same ranges, checks, determinism and capturability as
+ * ddsp_harm_analysis; max_cents > 0 and finite, flags = 0.  workspace: ddsp_harm_refine_workspace_bytes(B, T, hop) bytes, 16-byte
+ * aligned; its first ddsp_harm_workspace_bytes(B, T, hop) bytes are laid out as the analysis leaves them.
+ */
+size_t ddsp_harm_refine_workspace_bytes(long B, long T, int hop);
+int ddsp_harm_refine(const float *audio, const float *f0_in, const float *f0_anchor, const uint8_t *voiced, float *f0_out,
+                     float *num_out, float *den_out, void *workspace, long B, long T, int hop, int W, int H, int sample_rate,
+                     float max_cents, unsigned flags, void *stream);
 
 /*
  * Noise analysis: the inverse of ddsp_noise_forward_ws, exact in expectation for the filter that call
