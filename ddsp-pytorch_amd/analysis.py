@@ -38,6 +38,16 @@ stock torch ops in the input's dtype.  No backward.
 overlap_add=True inverts FilteredNoise's overlap-add mode instead (ddsp_noise_analysis_ola): that noise is
 stationary, so the model is (hop / 3) times the autocorrelation of the frame's whole response, the measured products cross frame
 boundaries and any hop >= 1 is analysable.  `iterations=None` is 16 for the truncated model and 8 for the overlap-add one.
+
+Control transformation: what makes the analysed dict worth having (include/ddsp_hip.h:
+ddsp_transform_controls).  Time stretch, transposition and formant shift of f0, a, c and the noise bands H between analysis and
+synthesis, the spectral envelope resampled in harmonic coordinates so that a transposition does not carry the formants along:
+
+  transform_controls(ctrl, sample_rate, stretch=1.0, transpose=0.0, formant=0.0, positions=None, n_harmonics=None) -> dict
+  ControlTransform(conf)                  nn.Module without parameters over conf.sample_rate
+
+CUDA fp32 controls with at most 256 harmonics (in and out) and 257 bands take the HIP kernel (csrc/ddsp_transform.hip), one
+launch; everything else the same definition as stock torch ops in the controls' dtype.  No backward.
 """
 from __future__ import annotations
 
@@ -59,6 +69,9 @@ NOISE_KERNEL_MAX_FRAMES = 2 ** 31 - 1
 NOISE_OLA_KERNEL_MAX_SAMPLES = 2 ** 31 - 8192   # (exclusive) samples of one row of the overlap-add analysis
 NOISE_ITERATIONS = 16                    # the defaults of `iterations`: the truncated model and the overlap-add one
 NOISE_OLA_ITERATIONS = 8
+TRANSFORM_KERNEL_MAX_FRAMES = 2 ** 47    # csrc/ddsp_transform.hip: rows x frames, in or out; kMaxBlocks and kWaves
+TRANSFORM_KERNEL_MAX_BLOCKS = 8192
+TRANSFORM_KERNEL_WAVES = 4
 
 
 def _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, what):
@@ -596,3 +609,204 @@ class NoiseAnalyzer(nn.Module):
     def forward(self, x, average=1, iterations=None):
         return noise_analysis(x, self.hop_length, self.n_filters, average=average, iterations=iterations,
                               overlap_add=self.overlap_add)
+
+
+# ------------------------------------------------------------------------------------------------------- control transformation
+
+def _per_frame(value, B, T_out, device, what, name):
+    """A tensor [T'], [B, T'] or [B, T', 1] -> fp64 [B, T'] on `device` (T_out None: taken from the tensor)."""
+    if value.device != device:
+        raise ValueError(f"{what}: {name} is on {value.device}, the controls on {device}")
+    _refuse_grad(value, what)
+    v = value.detach()
+    if v.dim() == 3 and v.shape[-1] == 1:
+        v = v[..., 0]
+    if v.dim() == 1:
+        v = v[None, :].expand(B, -1)
+    if v.dim() != 2 or v.shape[0] != B or v.shape[1] < 1 or (T_out is not None and v.shape[1] != T_out):
+        raise ValueError(f"{what}: {name} must be [T'], [B, T'] or [B, T', 1] with B = {B}"
+                         + ("" if T_out is None else f" and T' = {T_out}") + f", got {tuple(value.shape)}")
+    return v.double()
+
+
+def _semitone_ratio(value, B, T_out, device, what, name):
+    """Semitones (a float or a per-frame tensor) -> the ratio 2^(value / 12) as contiguous fp32 [B, T']."""
+    if torch.is_tensor(value):
+        return torch.exp2(_per_frame(value, B, T_out, device, what, name) / 12.0).float().contiguous()
+    semitones = float(value)
+    ratio = 2.0 ** (semitones / 12.0) if math.isfinite(semitones) and abs(semitones) < 12.0 * 1024 else math.nan
+    ratio = float(torch.tensor(ratio, dtype=torch.float32))     # as the kernel will see it
+    if not 0.0 < ratio < math.inf:
+        raise ValueError(f"{what}: {name} = {value!r} semitones is no finite, positive fp32 ratio")
+    return torch.full((B, T_out), ratio, dtype=torch.float32, device=device)
+
+
+def _transform_torch(f0, a, c, noise, pos, r, q, sample_rate, H_out):
+    """The definition as torch ops in c's dtype: f0, a [B, T], c [B, T, H], noise [B, T, F] or None; pos, r, q fp32 [B, T'].  The
+    masks, f0' and the weights' inputs are fp32 whatever the dtype, as the definition has them; u and v are formed in fp64."""
+    dt, dev = c.dtype, c.device
+    B, T, H = c.shape
+    T_out = pos.shape[1]
+    zero = torch.zeros((), dtype=dt, device=dev)
+    f32 = f0.float()
+    voiced = torch.isfinite(f32) & (f32 > 0)                                        # [B, T]
+    cm = torch.where(_harmonic_mask(f32[..., None], None, sample_rate, H), c, zero)
+    S = cm.sum(-1)
+    gain = torch.where(S == 0, zero, torch.where(voiced, a, zero) / torch.where(S == 0, torch.ones((), dtype=dt, device=dev), S))
+    A = cm * gain[..., None]                                                        # the amplitudes the bank plays
+    ok = torch.isfinite(r) & (r > 0) & torch.isfinite(q) & (q > 0)                  # [B, T']
+    one32 = torch.ones((), dtype=torch.float32, device=dev)
+    r, q = torch.where(ok, r, one32), torch.where(ok, q, one32)
+    p = torch.nan_to_num(pos.double(), nan=0.0, posinf=float(T - 1), neginf=0.0).clamp(0.0, float(T - 1))
+    i0 = p.floor().long()
+    i1 = (i0 + 1).clamp(max=T - 1)
+    lam64 = p - i0.double()
+    fa, fb = f32.gather(1, i0), f32.gather(1, i1)
+    va, vb = voiced.gather(1, i0), voiced.gather(1, i1)
+    live = ok & (va | vb)
+    f0s = torch.where(va & vb, ((1.0 - lam64) * fa.double() + lam64 * fb.double()).float(), torch.where(va, fa, fb))
+    f0o = torch.where(live, f0s * r, torch.zeros((), dtype=torch.float32, device=dev))             # fp32 [B, T']
+    rq = r.double() / q.double()
+    k_out = torch.arange(1, H_out + 1, device=dev)
+    F = 0 if noise is None else noise.shape[-1]
+    a_out = torch.empty((B, T_out), dtype=dt, device=dev)
+    c_out = torch.empty((B, T_out, H_out), dtype=dt, device=dev)
+    n_out = None if noise is None else torch.empty((B, T_out, F), dtype=dt, device=dev)
+    step = max(1, _CHUNK_ELEMENTS // max(1, B * max(H, H_out, F)))
+    for t0 in range(0, T_out, step):
+        sl = slice(t0, t0 + step)
+        lam = lam64[:, sl].to(dt)[..., None]                                        # [B, Tc, 1]
+        u = k_out.double() * rq[:, sl, None]                                        # [B, Tc, H']
+        m = u.clamp(max=float(H)).floor().long().clamp(1, max(1, H - 1))
+        mu = (u - m.double()).to(dt)
+        env = []
+        for idx in (i0[:, sl], i1[:, sl]):
+            Ai = A.gather(1, idx[..., None].expand(-1, -1, H))                      # [B, Tc, H]
+            between = (1 - mu) * Ai.gather(2, m - 1) + mu * Ai.gather(2, m.clamp(max=H - 1))
+            env.append(torch.where(u < 1, Ai[..., :1], torch.where(u < H, between, torch.where(u == H, Ai[..., H - 1:], zero))))
+        amp = (1 - lam) * env[0] + lam * env[1]
+        masked = k_out.float() * f0o[:, sl, None] > sample_rate // 2
+        amp = torch.where(live[:, sl, None] & ~masked, amp, zero)
+        total = amp.sum(-1)
+        a_out[:, sl] = total
+        c_out[:, sl] = torch.where(total[..., None] == 0, torch.full((), 1.0 / H_out, dtype=dt, device=dev), amp / total[..., None])
+        if noise is not None:
+            v = torch.arange(F, device=dev).double() / q[:, sl, None].double()      # [B, Tc, F]
+            n = v.clamp(max=float(F - 1)).floor().long()
+            nu = (v - n.double()).to(dt)
+            band = []
+            for idx in (i0[:, sl], i1[:, sl]):
+                Ni = noise.gather(1, idx[..., None].expand(-1, -1, F))
+                band.append((1 - nu) * Ni.gather(2, n) + nu * Ni.gather(2, (n + 1).clamp(max=F - 1)))
+            n_out[:, sl] = torch.where(ok[:, sl, None] & (v <= F - 1), (1 - lam) * band[0] + lam * band[1], zero)
+    return f0o.to(dt), a_out, c_out, n_out
+
+
+def _transform_in_kernel_range(c, noise, T_out, H_out) -> bool:
+    B, T, H = c.shape
+    return (c.is_cuda and c.dtype == torch.float32 and H <= KERNEL_MAX_HARMONICS and H_out <= KERNEL_MAX_HARMONICS
+            and (noise is None or noise.shape[-1] <= NOISE_KERNEL_MAX_FILTERS)
+            and B * max(T, T_out) <= TRANSFORM_KERNEL_MAX_FRAMES)
+
+
+def _transform_device(f0, a, c, noise, pos, r, q, sample_rate, H_out):
+    B, T, H = c.shape
+    T_out = pos.shape[1]
+    f0_out = torch.empty((B, T_out), device=c.device, dtype=torch.float32)
+    a_out = torch.empty_like(f0_out)
+    c_out = torch.empty((B, T_out, H_out), device=c.device, dtype=torch.float32)
+    n_out = None if noise is None else torch.empty((B, T_out, noise.shape[-1]), device=c.device, dtype=torch.float32)
+    with torch.cuda.device(c.device):
+        rc = _lib.lib().ddsp_transform_controls(f0.data_ptr(), a.data_ptr(), c.data_ptr(), None if noise is None else noise.data_ptr(),
+                                                pos.data_ptr(), r.data_ptr(), q.data_ptr(), f0_out.data_ptr(), a_out.data_ptr(),
+                                                c_out.data_ptr(), None if n_out is None else n_out.data_ptr(), B, T, T_out, H, H_out,
+                                                1 if noise is None else noise.shape[-1], sample_rate,
+                                                torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_transform_controls")
+    return f0_out, a_out, c_out, n_out
+
+
+def transform_controls(ctrl, sample_rate, stretch=1.0, transpose=0.0, formant=0.0, positions=None, n_harmonics=None) -> dict:
+    """The control dict of `harmonic_analysis` (f0 [B, T, 1], a [B, T, 1], c [B, T, H], optionally the noise bands H [B, T, F]; other
+    keys are dropped) stretched in time, transposed and formant-shifted -> a dict of the same keys with
+    T' frames and n_harmonics (None: H) harmonics, for `OscillatorBank` / `Decoder.synthesize`.
+
+    transpose, formant: semitones, a float or a tensor [T'], [B, T'] or [B, T', 1]; the pitch moves by r = 2^(transpose / 12), the
+    spectral envelope (and the noise bands) by q = 2^(formant / 12).  formant=0 keeps the formants where they are whatever the
+    transposition; formant=None lets them follow the pitch (q = r, every harmonic keeps its amplitude).
+    stretch > 0: T' = max(1, floor(T stretch + 1/2)) frames that read the input at pos[t'] = (t' + 1/2) T / T' - 1/2, clamped to
+    [0, T - 1].  positions ([T'] or [B, T'], in input frames) replaces it by any time map (freeze, reverse, ...).
+    A per-frame value that is not usable (a ratio that is not finite and positive) silences its frame; a position outside
+    [0, T - 1] is clamped.  CUDA fp32 controls with H, n_harmonics <= 256 and F <= 257 take the HIP kernel
+    (csrc/ddsp_transform.hip); CPU tensors, fp64 and larger sizes run the same definition as torch ops.  No backward."""
+    what = "transform_controls"
+    for key in ("f0", "a", "c"):
+        if key not in ctrl:
+            raise ValueError(f"{what}: the control dict has no '{key}'")
+    f0, a, c, noise = ctrl["f0"], ctrl["a"], ctrl["c"], ctrl.get("H")
+    if f0.dim() != 3 or f0.shape[-1] != 1:
+        raise ValueError(f"{what}: f0 must be [B, T, 1], got {tuple(f0.shape)}")
+    B, T = f0.shape[:2]
+    if tuple(a.shape) != (B, T, 1) or c.dim() != 3 or tuple(c.shape[:2]) != (B, T) or c.shape[-1] < 1 or T < 1:
+        raise ValueError(f"{what}: a must be [B, T, 1] and c [B, T, H] with f0's {B} x {T} >= 1 frames, got {tuple(a.shape)} and {tuple(c.shape)}")
+    if noise is not None and (noise.dim() != 3 or tuple(noise.shape[:2]) != (B, T) or noise.shape[-1] < 1):
+        raise ValueError(f"{what}: the noise bands H must be [B, T, F], got {tuple(noise.shape)}")
+    H = c.shape[-1]
+    H_out = H if n_harmonics is None else int(n_harmonics)
+    sample_rate = int(sample_rate)
+    if H_out < 1 or sample_rate < 1:
+        raise ValueError(f"{what}: n_harmonics and sample_rate must be positive, got {n_harmonics} and {sample_rate}")
+    dev = c.device
+    for name, v in (("f0", f0), ("a", a), ("H", noise)):
+        if v is not None and v.device != dev:
+            raise ValueError(f"{what}: {name} is on {v.device}, c on {dev}")
+    for v in (f0, a, c, noise):
+        if v is not None:
+            _refuse_grad(v, what)
+    dt = c.dtype if c.dtype in (torch.float32, torch.float64) else torch.float32
+    f0, a, c = (v.detach().to(dt).contiguous() for v in (f0[..., 0], a[..., 0], c))
+    noise = None if noise is None else noise.detach().to(dt).contiguous()
+
+    if positions is not None:
+        if not (isinstance(stretch, (int, float)) and float(stretch) == 1.0):
+            raise ValueError(f"{what}: positions replaces stretch; give one of them")
+        if not torch.is_tensor(positions) or positions.dim() not in (1, 2):
+            raise ValueError(f"{what}: positions must be a tensor [T'] or [B, T']")
+        pos = _per_frame(positions, B, None, dev, what, "positions").float().contiguous()
+        T_out = pos.shape[1]
+    else:
+        if torch.is_tensor(stretch):
+            raise ValueError(f"{what}: stretch is one factor; a time map goes into positions")
+        stretch = float(stretch)
+        if not 0.0 < stretch < math.inf:
+            raise ValueError(f"{what}: stretch must be positive and finite, got {stretch}")
+        T_out = max(1, int(math.floor(T * stretch + 0.5)))
+        pos = ((torch.arange(T_out, dtype=torch.float64, device=dev) + 0.5) * T / T_out - 0.5).clamp(0.0, float(T - 1))
+        pos = pos.float()[None, :].expand(B, -1).contiguous()
+    r = _semitone_ratio(transpose, B, T_out, dev, what, "transpose")
+    q = r if formant is None else _semitone_ratio(formant, B, T_out, dev, what, "formant")
+
+    if B == 0:
+        out = dict(f0=torch.zeros((0, T_out, 1), dtype=dt, device=dev), a=torch.zeros((0, T_out, 1), dtype=dt, device=dev),
+                   c=torch.zeros((0, T_out, H_out), dtype=dt, device=dev))
+        if noise is not None:
+            out["H"] = torch.zeros((0, T_out, noise.shape[-1]), dtype=dt, device=dev)
+        return out
+    path = _transform_device if _transform_in_kernel_range(c, noise, T_out, H_out) else _transform_torch
+    f0_out, a_out, c_out, n_out = path(f0, a, c, noise, pos, r, q, sample_rate, H_out)
+    out = dict(f0=f0_out[..., None], a=a_out[..., None], c=c_out)
+    if n_out is not None:
+        out["H"] = n_out
+    return out
+
+
+class ControlTransform(nn.Module):
+    """forward(ctrl, stretch=1.0, transpose=0.0, formant=0.0, positions=None, n_harmonics=None) -> dict: `transform_controls` at the
+    configuration's sample_rate.  No parameters."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.sample_rate = conf.sample_rate
+
+    def forward(self, ctrl, **keywords):
+        return transform_controls(ctrl, self.sample_rate, **keywords)

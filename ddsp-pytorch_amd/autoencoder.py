@@ -6,6 +6,9 @@
                              the control dict of x without the decoder's network: f0, a, c by harmonic analysis and, with noise=True
                              (the truncated noise model) or noise='overlap_add', H by noise analysis of the residual (analysis.py);
                              refine=N first moves the decoded f0 off its 20-cent grid by N steps of analysis.refine_f0
+  transform(x, stretch=1.0, transpose=0.0, formant=0.0, positions=None, noise=True, refine=0, reverb=False)
+                             analyse, analysis.transform_controls (time stretch, transposition, formant shift), synthesize:
+                             audio [B, T' hop]
   forward_live(x, hidden, delayed=False)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -23,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .analysis import harmonic_analysis, harmonic_residual, noise_analysis
+from .analysis import harmonic_analysis, harmonic_residual, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
 
@@ -79,6 +82,19 @@ class AutoEncoder(nn.Module):
         ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average,
                                    iterations=iterations, overlap_add=overlap_add)
         return ctrl
+
+    def transform(self, x: torch.Tensor, stretch=1.0, transpose=0.0, formant=0.0, positions=None, noise=True, refine: int = 0,
+                  reverb: bool = False) -> torch.Tensor:
+        """audio [B, L] -> audio [B, T' hop], stretched in time, transposed and formant-shifted (semitones) without the decoder's
+        network: `analyse(x, noise=noise, refine=refine)`, analysis.transform_controls on that dict (its `stretch`, `transpose`,
+        `formant` -- 0 keeps the formants in place, None lets them follow the pitch -- and `positions`), then
+        `decoder.synthesize`, and `decoder.reverb` only when asked.  noise follows analyse's rules (True / 'truncated' /
+        'overlap_add' must be the decoder's noise form); noise=False plays the harmonics alone (`decoder.harmonics`)."""
+        ctrl = transform_controls(self.analyse(x, noise=noise, refine=refine), self.decoder.harmonics.sample_rate, stretch=stretch,
+                                  transpose=transpose, formant=formant, positions=positions)
+        with torch.no_grad():
+            y = self.decoder.synthesize(ctrl) if noise else self.decoder.harmonics(ctrl)
+            return self.decoder.reverb(y) if reverb else y
 
     def live_window(self, x: np.ndarray) -> torch.Tensor:
         """The callback's window on the module's device, trimmed as autoencoder.py:28-30 trims it: [1, len - hop]."""

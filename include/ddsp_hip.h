@@ -620,6 +620,33 @@ int ddsp_noise_analysis_ola(const float *x, float *H, float *power, void *worksp
                             int iterations, void *stream);
 
 /*
+ * Transformation of analysed controls (DESIGN.md section 14b has the definition): time stretch, transposition and formant shift
+ * of what ddsp_harm_analysis and ddsp_noise_analysis return.  All fp32, dense row-major; rows are independent.
+ *   f0 [B, T] Hz, a [B, T], c [B, T, H], noise [B, T, F] or NULL;  per output frame t' in [0, T_out): pos [B, T_out] a source position
+ *   in input frames, ratio [B, T_out] the pitch ratio r, env [B, T_out] the envelope ratio q.
+ * Source frame i is voiced where f0[i] is finite and positive.  A[i, k] = a[i] c[i, k] / S_i where frame i is voiced and
+ * fl32(k f0[i]) > sample_rate / 2 (integer division, as the bank masks) is false, S_i the sum of c[i, k] over those k; A[i, k] = 0
+ * elsewhere and where S_i = 0.  E_i(u) = A[i, 1] for u < 1, (1 - mu) A[i, m] + mu A[i, m + 1] for 1 <= u < H (m = floor(u),
+ * mu = u - m), A[i, H] at u = H, 0 beyond.  Output frame t':
+ *   p = pos clamped to [0, T - 1] (a NaN counts as 0), i0 = floor(p), i1 = min(i0 + 1, T - 1), lambda = p - i0
+ *   f0_out = fl32(fl32(f0_s) r), f0_s = (1 - lambda) f0[i0] + lambda f0[i1] where both are voiced, else the voiced one's f0
+ *   A'[k'] = (1 - lambda) E_i0(u) + lambda E_i1(u), u = k' r / q in double, k' = 1 .. H_out; 0 where fl32(k' f0_out) > sample_rate / 2
+ *   a_out = sum_k' A', c_out = A' / a_out, and c_out = 1 / H_out where a_out = 0
+ *   noise_out[j] = the same two interpolations of noise over lambda and the bands floor(v), floor(v) + 1 at v = j / q, 0 for v > F - 1
+ * A frame whose neighbours are both unvoiced has f0_out = 0, a_out = 0, c_out = 1 / H_out (its noise is transformed all the same);
+ * a frame whose r or q is not finite or not positive has that and noise_out = 0.
+ * -> f0_out [B, T_out], a_out [B, T_out], c_out [B, T_out, H_out], noise_out [B, T_out, F] (NULL exactly when noise is).
+ * B == 0 returns 0; a null pointer, noise without noise_out (or the reverse) or a size that is not positive is DDSP_EINVAL;
+ * H or H_out > 256, F > 257 (F is ignored but must be positive without noise), B T or B T_out beyond 2^47 frames DDSP_ERANGE.  No
+ * workspace, one launch, one wavefront per output frame (grid-strided beyond 8192 workgroups of four), no atomics, no
+ * allocation, no host synchronisation; every sum has one order: a frame's results are the same bits from run to run and
+ * whatever else is in the batch.  No input, NaN or huge, makes the kernel read or write outside its arrays.
+ */
+int ddsp_transform_controls(const float *f0, const float *a, const float *c, const float *noise, const float *pos, const float *ratio,
+                            const float *env, float *f0_out, float *a_out, float *c_out, float *noise_out, long B, long T,
+                            long T_out, int H, int H_out, int F, int sample_rate, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
