@@ -117,6 +117,7 @@ SIGNATURES = {
     "ddsp_noise_analysis_ola_workspace_bytes": (_size, [_long, _long, _i32, _i32]),
     "ddsp_noise_analysis_ola": (_i32, [_vp] * 4 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_transform_controls": (_i32, [_vp] * 11 + [_long, _long, _long, _i32, _i32, _i32, _i32, _vp]),
+    "ddsp_morph_controls": (_i32, [_vp] * 17 + [_long, _long, _long, _long, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_loudness_supported": (_i32, [_i32]),
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),

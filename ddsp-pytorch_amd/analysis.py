@@ -48,6 +48,18 @@ synthesis, the spectral envelope resampled in harmonic coordinates so that a tra
 
 CUDA fp32 controls with at most 256 harmonics (in and out) and 257 bands take the HIP kernel (csrc/ddsp_transform.hip), one
 launch; everything else the same definition as stock torch ops in the controls' dtype.  No backward.
+
+Control morph: the operation between two analysed sounds (include/ddsp_hip.h: ddsp_morph_controls).  A
+sound whose pitch (in log frequency), spectral envelope (compared at equal frequency, or harmonic by harmonic) and noise bands
+each lie between those of two control dicts, by weights that may move over time; the two sounds may differ in frames and in
+harmonics, and `positions_a` / `positions_b` take any time alignment:
+
+  morph_controls(ctrl_a, ctrl_b, sample_rate, mix=0.5, mix_f0=None, mix_harmonics=None, mix_noise=None, coordinates='hz',
+                 frames=None, positions_a=None, positions_b=None, n_harmonics=None) -> dict
+  ControlMorph(conf)                      nn.Module without parameters over conf.sample_rate
+
+CUDA fp32 controls in the transformation's range take the HIP kernel (csrc/ddsp_morph.hip), one launch; everything else the same
+definition as stock torch ops.  No backward.
 """
 from __future__ import annotations
 
@@ -72,6 +84,10 @@ NOISE_OLA_ITERATIONS = 8
 TRANSFORM_KERNEL_MAX_FRAMES = 2 ** 47    # csrc/ddsp_transform.hip: rows x frames, in or out; kMaxBlocks and kWaves
 TRANSFORM_KERNEL_MAX_BLOCKS = 8192
 TRANSFORM_KERNEL_WAVES = 4
+MORPH_KERNEL_MAX_FRAMES = 2 ** 47        # csrc/ddsp_morph.hip: rows x frames of either sound or of the output; kMaxBlocks, kWaves
+MORPH_KERNEL_MAX_BLOCKS = 8192
+MORPH_KERNEL_WAVES = 4
+MORPH_COORDINATES = {'hz': 0, 'harmonic': 1}    # include/ddsp_hip.h: DDSP_MORPH_HZ, DDSP_MORPH_HARMONIC
 
 
 def _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, what):
@@ -641,12 +657,12 @@ def _semitone_ratio(value, B, T_out, device, what, name):
     return torch.full((B, T_out), ratio, dtype=torch.float32, device=device)
 
 
-def _transform_torch(f0, a, c, noise, pos, r, q, sample_rate, H_out):
-    """The definition as torch ops in c's dtype: f0, a [B, T], c [B, T, H], noise [B, T, F] or None; pos, r, q fp32 [B, T'].  The
-    masks, f0' and the weights' inputs are fp32 whatever the dtype, as the definition has them; u and v are formed in fp64."""
+def _source_frames(f0, a, c, pos, sample_rate):
+    """What the transformation and the morph read of one sound (rules 1 to 3): f0, a [B, T], c [B, T, H] in
+    one dtype, pos fp32 [B, T'] -> the amplitudes A [B, T, H] the bank plays, the frame pair i0, i1 and its weight lambda (fp64)
+    of every output frame, the fp32 pitch at the position (no glide from an unvoiced neighbour) and whether a neighbour is voiced."""
     dt, dev = c.dtype, c.device
     B, T, H = c.shape
-    T_out = pos.shape[1]
     zero = torch.zeros((), dtype=dt, device=dev)
     f32 = f0.float()
     voiced = torch.isfinite(f32) & (f32 > 0)                                        # [B, T]
@@ -654,17 +670,36 @@ def _transform_torch(f0, a, c, noise, pos, r, q, sample_rate, H_out):
     S = cm.sum(-1)
     gain = torch.where(S == 0, zero, torch.where(voiced, a, zero) / torch.where(S == 0, torch.ones((), dtype=dt, device=dev), S))
     A = cm * gain[..., None]                                                        # the amplitudes the bank plays
-    ok = torch.isfinite(r) & (r > 0) & torch.isfinite(q) & (q > 0)                  # [B, T']
-    one32 = torch.ones((), dtype=torch.float32, device=dev)
-    r, q = torch.where(ok, r, one32), torch.where(ok, q, one32)
     p = torch.nan_to_num(pos.double(), nan=0.0, posinf=float(T - 1), neginf=0.0).clamp(0.0, float(T - 1))
     i0 = p.floor().long()
     i1 = (i0 + 1).clamp(max=T - 1)
     lam64 = p - i0.double()
     fa, fb = f32.gather(1, i0), f32.gather(1, i1)
     va, vb = voiced.gather(1, i0), voiced.gather(1, i1)
-    live = ok & (va | vb)
     f0s = torch.where(va & vb, ((1.0 - lam64) * fa.double() + lam64 * fb.double()).float(), torch.where(va, fa, fb))
+    return A, i0, i1, lam64, f0s, va | vb
+
+
+def _envelope_at(Ai, u, m, mu):
+    """E(u) of the rows Ai [B, Tc, H] at u [B, Tc, H'] (fp64), m = floor(u) kept in [1, H - 1] and mu = u - m in Ai's dtype."""
+    H = Ai.shape[-1]
+    zero = torch.zeros((), dtype=Ai.dtype, device=Ai.device)
+    between = (1 - mu) * Ai.gather(2, m - 1) + mu * Ai.gather(2, m.clamp(max=H - 1))
+    return torch.where(u < 1, Ai[..., :1], torch.where(u < H, between, torch.where(u == H, Ai[..., H - 1:], zero)))
+
+
+def _transform_torch(f0, a, c, noise, pos, r, q, sample_rate, H_out):
+    """The definition as torch ops in c's dtype: f0, a [B, T], c [B, T, H], noise [B, T, F] or None; pos, r, q fp32 [B, T'].  The
+    masks, f0' and the weights' inputs are fp32 whatever the dtype, as the definition has them; u and v are formed in fp64."""
+    dt, dev = c.dtype, c.device
+    B, T, H = c.shape
+    T_out = pos.shape[1]
+    zero = torch.zeros((), dtype=dt, device=dev)
+    ok = torch.isfinite(r) & (r > 0) & torch.isfinite(q) & (q > 0)                  # [B, T']
+    one32 = torch.ones((), dtype=torch.float32, device=dev)
+    r, q = torch.where(ok, r, one32), torch.where(ok, q, one32)
+    A, i0, i1, lam64, f0s, present = _source_frames(f0, a, c, pos, sample_rate)
+    live = ok & present
     f0o = torch.where(live, f0s * r, torch.zeros((), dtype=torch.float32, device=dev))             # fp32 [B, T']
     rq = r.double() / q.double()
     k_out = torch.arange(1, H_out + 1, device=dev)
@@ -679,11 +714,7 @@ def _transform_torch(f0, a, c, noise, pos, r, q, sample_rate, H_out):
         u = k_out.double() * rq[:, sl, None]                                        # [B, Tc, H']
         m = u.clamp(max=float(H)).floor().long().clamp(1, max(1, H - 1))
         mu = (u - m.double()).to(dt)
-        env = []
-        for idx in (i0[:, sl], i1[:, sl]):
-            Ai = A.gather(1, idx[..., None].expand(-1, -1, H))                      # [B, Tc, H]
-            between = (1 - mu) * Ai.gather(2, m - 1) + mu * Ai.gather(2, m.clamp(max=H - 1))
-            env.append(torch.where(u < 1, Ai[..., :1], torch.where(u < H, between, torch.where(u == H, Ai[..., H - 1:], zero))))
+        env = [_envelope_at(A.gather(1, idx[..., None].expand(-1, -1, H)), u, m, mu) for idx in (i0[:, sl], i1[:, sl])]
         amp = (1 - lam) * env[0] + lam * env[1]
         masked = k_out.float() * f0o[:, sl, None] > sample_rate // 2
         amp = torch.where(live[:, sl, None] & ~masked, amp, zero)
@@ -726,6 +757,32 @@ def _transform_device(f0, a, c, noise, pos, r, q, sample_rate, H_out):
     return f0_out, a_out, c_out, n_out
 
 
+def _control_arrays(ctrl, what):
+    """The checks of a control dict -> f0, a [B, T], c [B, T, H], the noise bands [B, T, F] or None: detached, contiguous, in c's
+    dtype where that is fp32 or fp64 (else fp32)."""
+    for key in ("f0", "a", "c"):
+        if key not in ctrl:
+            raise ValueError(f"{what}: the control dict has no '{key}'")
+    f0, a, c, noise = ctrl["f0"], ctrl["a"], ctrl["c"], ctrl.get("H")
+    if f0.dim() != 3 or f0.shape[-1] != 1:
+        raise ValueError(f"{what}: f0 must be [B, T, 1], got {tuple(f0.shape)}")
+    B, T = f0.shape[:2]
+    if tuple(a.shape) != (B, T, 1) or c.dim() != 3 or tuple(c.shape[:2]) != (B, T) or c.shape[-1] < 1 or T < 1:
+        raise ValueError(f"{what}: a must be [B, T, 1] and c [B, T, H] with f0's {B} x {T} >= 1 frames, got {tuple(a.shape)} and {tuple(c.shape)}")
+    if noise is not None and (noise.dim() != 3 or tuple(noise.shape[:2]) != (B, T) or noise.shape[-1] < 1):
+        raise ValueError(f"{what}: the noise bands H must be [B, T, F], got {tuple(noise.shape)}")
+    dev = c.device
+    for name, v in (("f0", f0), ("a", a), ("H", noise)):
+        if v is not None and v.device != dev:
+            raise ValueError(f"{what}: {name} is on {v.device}, c on {dev}")
+    for v in (f0, a, c, noise):
+        if v is not None:
+            _refuse_grad(v, what)
+    dt = c.dtype if c.dtype in (torch.float32, torch.float64) else torch.float32
+    f0, a, c = (v.detach().to(dt).contiguous() for v in (f0[..., 0], a[..., 0], c))
+    return f0, a, c, None if noise is None else noise.detach().to(dt).contiguous()
+
+
 def transform_controls(ctrl, sample_rate, stretch=1.0, transpose=0.0, formant=0.0, positions=None, n_harmonics=None) -> dict:
     """The control dict of `harmonic_analysis` (f0 [B, T, 1], a [B, T, 1], c [B, T, H], optionally the noise bands H [B, T, F]; other
     keys are dropped) stretched in time, transposed and formant-shifted -> a dict of the same keys with
@@ -740,32 +797,13 @@ def transform_controls(ctrl, sample_rate, stretch=1.0, transpose=0.0, formant=0.
     [0, T - 1] is clamped.  CUDA fp32 controls with H, n_harmonics <= 256 and F <= 257 take the HIP kernel
     (csrc/ddsp_transform.hip); CPU tensors, fp64 and larger sizes run the same definition as torch ops.  No backward."""
     what = "transform_controls"
-    for key in ("f0", "a", "c"):
-        if key not in ctrl:
-            raise ValueError(f"{what}: the control dict has no '{key}'")
-    f0, a, c, noise = ctrl["f0"], ctrl["a"], ctrl["c"], ctrl.get("H")
-    if f0.dim() != 3 or f0.shape[-1] != 1:
-        raise ValueError(f"{what}: f0 must be [B, T, 1], got {tuple(f0.shape)}")
-    B, T = f0.shape[:2]
-    if tuple(a.shape) != (B, T, 1) or c.dim() != 3 or tuple(c.shape[:2]) != (B, T) or c.shape[-1] < 1 or T < 1:
-        raise ValueError(f"{what}: a must be [B, T, 1] and c [B, T, H] with f0's {B} x {T} >= 1 frames, got {tuple(a.shape)} and {tuple(c.shape)}")
-    if noise is not None and (noise.dim() != 3 or tuple(noise.shape[:2]) != (B, T) or noise.shape[-1] < 1):
-        raise ValueError(f"{what}: the noise bands H must be [B, T, F], got {tuple(noise.shape)}")
-    H = c.shape[-1]
+    f0, a, c, noise = _control_arrays(ctrl, what)
+    B, T, H = c.shape
+    dt, dev = c.dtype, c.device
     H_out = H if n_harmonics is None else int(n_harmonics)
     sample_rate = int(sample_rate)
     if H_out < 1 or sample_rate < 1:
         raise ValueError(f"{what}: n_harmonics and sample_rate must be positive, got {n_harmonics} and {sample_rate}")
-    dev = c.device
-    for name, v in (("f0", f0), ("a", a), ("H", noise)):
-        if v is not None and v.device != dev:
-            raise ValueError(f"{what}: {name} is on {v.device}, c on {dev}")
-    for v in (f0, a, c, noise):
-        if v is not None:
-            _refuse_grad(v, what)
-    dt = c.dtype if c.dtype in (torch.float32, torch.float64) else torch.float32
-    f0, a, c = (v.detach().to(dt).contiguous() for v in (f0[..., 0], a[..., 0], c))
-    noise = None if noise is None else noise.detach().to(dt).contiguous()
 
     if positions is not None:
         if not (isinstance(stretch, (int, float)) and float(stretch) == 1.0):
@@ -810,3 +848,185 @@ class ControlTransform(nn.Module):
 
     def forward(self, ctrl, **keywords):
         return transform_controls(ctrl, self.sample_rate, **keywords)
+
+
+# -------------------------------------------------------------------------------------------------------------- control morph
+
+def _morph_torch(src_a, src_b, wf, wh, wn, sample_rate, H_out, hz):
+    """The definition of DESIGN.md section 14c as torch ops in the controls' dtype.  src_X = (f0, a [B, T_X], c [B, T_X, H_X], noise
+    [B, T_X, F] or None, pos fp32 [B, T']); wf, wh, wn fp32 [B, T'].  f0', the masks and the weights are fp32 whatever the dtype,
+    u_X, exp2 and log2 fp64, as the definition has them."""
+    c_a, c_b = src_a[2], src_b[2]
+    dt, dev = c_a.dtype, c_a.device
+    B, T_out = wf.shape
+    zero, zero32 = torch.zeros((), dtype=dt, device=dev), torch.zeros((), dtype=torch.float32, device=dev)
+    sane = torch.isfinite(wf) & torch.isfinite(wh) & torch.isfinite(wn)            # [B, T']
+    wf, wh, wn = (torch.where(sane, w, zero32).clamp(0.0, 1.0) for w in (wf, wh, wn))
+    srcs = []
+    for f0, a, c, noise, pos in (src_a, src_b):
+        A, i0, i1, lam64, f, present = _source_frames(f0, a, c, pos, sample_rate)
+        present = present & sane
+        srcs.append(dict(A=A, i0=i0, i1=i1, lam64=lam64, present=present, noise=noise, H=c.shape[-1],
+                         f=torch.where(present, f, torch.ones((), dtype=torch.float32, device=dev))))
+    sa, sb = srcs
+    fa, fb, pa, pb = sa["f"], sb["f"], sa["present"], sb["present"]
+    w64 = wf.double()
+    mean = torch.exp2((1.0 - w64) * torch.log2(fa.double()) + w64 * torch.log2(fb.double())).float()
+    mean = torch.minimum(torch.maximum(mean, torch.minimum(fa, fb)), torch.maximum(fa, fb))
+    f0o = torch.where(pa & pb, torch.where(wf == 0, fa, torch.where(wf == 1, fb, mean)), torch.where(pa, fa, torch.where(pb, fb, zero32)))
+    live = pa | pb
+    for s in srcs:
+        s["scale"] = torch.where(s["present"], f0o.double() / s["f"].double(), torch.ones((), dtype=torch.float64, device=dev)) if hz \
+            else torch.ones((B, T_out), dtype=torch.float64, device=dev)
+    k_out = torch.arange(1, H_out + 1, device=dev)
+    F = 0 if sa["noise"] is None else sa["noise"].shape[-1]
+    a_out = torch.empty((B, T_out), dtype=dt, device=dev)
+    c_out = torch.empty((B, T_out, H_out), dtype=dt, device=dev)
+    n_out = None if sa["noise"] is None else torch.empty((B, T_out, F), dtype=dt, device=dev)
+    step = max(1, _CHUNK_ELEMENTS // max(1, B * max(sa["H"], sb["H"], H_out, F)))
+    for t0 in range(0, T_out, step):
+        sl = slice(t0, t0 + step)
+        env, band = [], []
+        for s in srcs:
+            H = s["H"]
+            lam = s["lam64"][:, sl].to(dt)[..., None]                               # [B, Tc, 1]
+            u = k_out.double() * s["scale"][:, sl, None]                            # [B, Tc, H']
+            m = u.clamp(max=float(H)).floor().long().clamp(1, max(1, H - 1))
+            mu = (u - m.double()).to(dt)
+            E = [_envelope_at(s["A"].gather(1, idx[..., None].expand(-1, -1, H)), u, m, mu) for idx in (s["i0"][:, sl], s["i1"][:, sl])]
+            env.append(torch.where(s["present"][:, sl, None], (1 - lam) * E[0] + lam * E[1], zero))
+            if n_out is not None:
+                N = [s["noise"].gather(1, idx[..., None].expand(-1, -1, F)) for idx in (s["i0"][:, sl], s["i1"][:, sl])]
+                band.append((1 - lam) * N[0] + lam * N[1])
+        w = wh[:, sl, None].to(dt)
+        amp = (1 - w) * env[0] + w * env[1]
+        masked = k_out.float() * f0o[:, sl, None] > sample_rate // 2
+        amp = torch.where(live[:, sl, None] & ~masked, amp, zero)
+        total = amp.sum(-1)
+        a_out[:, sl] = total
+        c_out[:, sl] = torch.where(total[..., None] == 0, torch.full((), 1.0 / H_out, dtype=dt, device=dev), amp / total[..., None])
+        if n_out is not None:
+            w = wn[:, sl, None].to(dt)
+            n_out[:, sl] = torch.where(sane[:, sl, None], (1 - w) * band[0] + w * band[1], zero)
+    return f0o.to(dt), a_out, c_out, n_out
+
+
+def _morph_in_kernel_range(src_a, src_b, T_out, H_out) -> bool:
+    c_a, c_b, noise = src_a[2], src_b[2], src_a[3]
+    B = c_a.shape[0]
+    return (c_a.is_cuda and c_a.dtype == torch.float32 and max(c_a.shape[-1], c_b.shape[-1], H_out) <= KERNEL_MAX_HARMONICS
+            and (noise is None or noise.shape[-1] <= NOISE_KERNEL_MAX_FILTERS)
+            and B * max(c_a.shape[1], c_b.shape[1], T_out) <= MORPH_KERNEL_MAX_FRAMES)
+
+
+def _morph_device(src_a, src_b, wf, wh, wn, sample_rate, H_out, hz):
+    c_a, c_b, noise = src_a[2], src_b[2], src_a[3]
+    B, T_out = wf.shape
+    F = 1 if noise is None else noise.shape[-1]
+    f0_out = torch.empty((B, T_out), device=c_a.device, dtype=torch.float32)
+    a_out = torch.empty_like(f0_out)
+    c_out = torch.empty((B, T_out, H_out), device=c_a.device, dtype=torch.float32)
+    n_out = None if noise is None else torch.empty((B, T_out, F), device=c_a.device, dtype=torch.float32)
+    ptr = lambda v: None if v is None else v.data_ptr()                                           # noqa: E731
+    with torch.cuda.device(c_a.device):
+        rc = _lib.lib().ddsp_morph_controls(*(ptr(v) for v in src_a), *(ptr(v) for v in src_b), wf.data_ptr(), wh.data_ptr(),
+                                            wn.data_ptr(), f0_out.data_ptr(), a_out.data_ptr(), c_out.data_ptr(), ptr(n_out), B,
+                                            c_a.shape[1], c_b.shape[1], T_out, c_a.shape[-1], c_b.shape[-1], H_out, F, sample_rate,
+                                            MORPH_COORDINATES['hz' if hz else 'harmonic'], torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_morph_controls")
+    return f0_out, a_out, c_out, n_out
+
+
+def _mix_weight(value, B, T_out, device, what, name):
+    """The weight of sound B (a float or a per-frame tensor) -> contiguous fp32 [B, T']; a float must be finite and is clamped to
+    [0, 1], a tensor's values are left to the definition (never synchronised on)."""
+    if torch.is_tensor(value):
+        return _per_frame(value, B, T_out, device, what, name).float().contiguous()
+    weight = float(value)
+    if not math.isfinite(weight):
+        raise ValueError(f"{what}: {name} = {value!r} is not finite")
+    return torch.full((B, T_out), min(1.0, max(0.0, weight)), dtype=torch.float32, device=device)
+
+
+def morph_controls(ctrl_a, ctrl_b, sample_rate, mix=0.5, mix_f0=None, mix_harmonics=None, mix_noise=None, coordinates='hz',
+                   frames=None, positions_a=None, positions_b=None, n_harmonics=None) -> dict:
+    """Two control dicts of `harmonic_analysis` (f0, a [B, T_x, 1], c [B, T_x, H_x], optionally the noise bands H [B, T_x, F] in both;
+    the same B, device and dtype; T_a != T_b and H_a != H_b are fine; other keys are dropped) -> the dict of a sound whose pitch,
+    spectral envelope and noise bands lie between theirs, with T' frames and n_harmonics (None: the
+    larger of H_a and H_b) harmonics, for `OscillatorBank` / `Decoder.synthesize`.
+
+    mix: the weight of sound B, 0 is sound A and 1 is sound B; a float (finite, clamped to [0, 1]) or a tensor [T'], [B, T'] or
+    [B, T', 1].  mix_f0, mix_harmonics and mix_noise replace it for the pitch (interpolated in log frequency), the harmonic
+    amplitudes and the noise bands; None means mix.  A frame with a weight that is not finite is silent.
+    coordinates: 'hz' compares the two envelopes at equal frequency (output harmonic k' reads each sound at k' f0' / f_x of its own
+    harmonics, so a formant both sounds have stays where it is whatever the pitches); 'harmonic' compares them harmonic by harmonic.
+    frames: T' (None: T_a); each sound is read at pos_x[t'] = (t' + 1/2) T_x / T' - 1/2 clamped to [0, T_x - 1].  positions_a and
+    positions_b ([T'] or [B, T'], in that sound's frames) replace a sound's map by any map -- an alignment found elsewhere goes in
+    here; T' is then their length.
+    CUDA fp32 controls with at most 256 harmonics (in and out) and 257 bands take the HIP kernel (csrc/ddsp_morph.hip), one
+    launch; CPU tensors, fp64 and larger sizes run the same definition as torch ops.  No backward."""
+    what = "morph_controls"
+    if coordinates not in MORPH_COORDINATES:
+        raise ValueError(f"{what}: coordinates must be 'hz' or 'harmonic', got {coordinates!r}")
+    src_a, src_b = _control_arrays(ctrl_a, what + " (sound A)"), _control_arrays(ctrl_b, what + " (sound B)")
+    c_a, c_b = src_a[2], src_b[2]
+    B, T_a, H_a = c_a.shape
+    dt, dev = c_a.dtype, c_a.device
+    if c_b.shape[0] != B or c_b.device != dev or ctrl_a["c"].dtype != ctrl_b["c"].dtype:
+        raise ValueError(f"{what}: the two sounds must have the same batch, device and dtype, got {tuple(c_a.shape)} {ctrl_a['c'].dtype} "
+                         f"on {dev} and {tuple(c_b.shape)} {ctrl_b['c'].dtype} on {c_b.device}")
+    if (src_a[3] is None) != (src_b[3] is None) or (src_a[3] is not None and src_a[3].shape[-1] != src_b[3].shape[-1]):
+        raise ValueError(f"{what}: the noise bands H must be in both dicts with the same number of bands, or in neither")
+    H_out = max(H_a, c_b.shape[-1]) if n_harmonics is None else int(n_harmonics)
+    sample_rate = int(sample_rate)
+    if H_out < 1 or sample_rate < 1:
+        raise ValueError(f"{what}: n_harmonics and sample_rate must be positive, got {n_harmonics} and {sample_rate}")
+
+    given = {}
+    for name, positions in (("positions_a", positions_a), ("positions_b", positions_b)):
+        if positions is not None:
+            if not torch.is_tensor(positions) or positions.dim() not in (1, 2):
+                raise ValueError(f"{what}: {name} must be a tensor [T'] or [B, T']")
+            given[name] = _per_frame(positions, B, None, dev, what, name).float().contiguous()
+    lengths = {v.shape[1] for v in given.values()}
+    if len(lengths) > 1:
+        raise ValueError(f"{what}: positions_a and positions_b have different lengths {sorted(lengths)}")
+    T_out = lengths.pop() if lengths else (T_a if frames is None else int(frames))
+    if T_out < 1 or (frames is not None and int(frames) != T_out):
+        raise ValueError(f"{what}: frames = {frames!r} must be positive and agree with the {T_out} positions given")
+    maps = []
+    for name, T in (("positions_a", T_a), ("positions_b", c_b.shape[1])):
+        if name in given:
+            maps.append(given[name])
+        else:
+            pos = ((torch.arange(T_out, dtype=torch.float64, device=dev) + 0.5) * T / T_out - 0.5).clamp(0.0, float(T - 1))
+            maps.append(pos.float()[None, :].expand(B, -1).contiguous())
+    overrides = (("mix_f0", mix_f0), ("mix_harmonics", mix_harmonics), ("mix_noise", mix_noise))
+    shared = _mix_weight(mix, B, T_out, dev, what, "mix") if any(v is None for _, v in overrides) else None   # expanded once
+    wf, wh, wn = (shared if v is None else _mix_weight(v, B, T_out, dev, what, name) for name, v in overrides)
+
+    if B == 0:
+        out = dict(f0=torch.zeros((0, T_out, 1), dtype=dt, device=dev), a=torch.zeros((0, T_out, 1), dtype=dt, device=dev),
+                   c=torch.zeros((0, T_out, H_out), dtype=dt, device=dev))
+        if src_a[3] is not None:
+            out["H"] = torch.zeros((0, T_out, src_a[3].shape[-1]), dtype=dt, device=dev)
+        return out
+    src_a, src_b = src_a + (maps[0],), src_b + (maps[1],)
+    path = _morph_device if _morph_in_kernel_range(src_a, src_b, T_out, H_out) else _morph_torch
+    f0_out, a_out, c_out, n_out = path(src_a, src_b, wf, wh, wn, sample_rate, H_out, coordinates == 'hz')
+    out = dict(f0=f0_out[..., None], a=a_out[..., None], c=c_out)
+    if n_out is not None:
+        out["H"] = n_out
+    return out
+
+
+class ControlMorph(nn.Module):
+    """forward(ctrl_a, ctrl_b, mix=0.5, mix_f0=None, mix_harmonics=None, mix_noise=None, coordinates='hz', frames=None,
+    positions_a=None, positions_b=None, n_harmonics=None) -> dict: `morph_controls` at the configuration's sample_rate.  No parameters."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.sample_rate = conf.sample_rate
+
+    def forward(self, ctrl_a, ctrl_b, **keywords):
+        return morph_controls(ctrl_a, ctrl_b, self.sample_rate, **keywords)

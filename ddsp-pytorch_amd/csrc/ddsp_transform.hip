@@ -17,25 +17,16 @@
 
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
+#include "ddsp_controls.h"
 
 namespace {
 
-constexpr int kMaxH = 256;                      // harmonics, in and out: four slots of 64 per lane
-constexpr int kMaxF = 257;                      // noise bands: five slots
-constexpr int kHSlots = kMaxH / 64;
-constexpr int kFSlots = (kMaxF + 63) / 64;
+using namespace ddsp_controls;                  // kMaxH, kMaxF, their slots; usable, convex, envelope_pair
+
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;           // output frames of one workgroup at a time
 constexpr int kMaxBlocks = 8192;                // (analysis.TRANSFORM_KERNEL_MAX_BLOCKS)
 constexpr int kNoisePitch = 260;                // pairs of one wavefront's noise stage
-
-__device__ __forceinline__ bool usable(float x) { return fabsf(x) < INFINITY && x > 0.0f; }     // finite and positive
-
-// (1 - w) x + w y, every operation rounded on its own: w = 0 selects x, w = 1 selects y
-__device__ __forceinline__ float convex(float w, float x, float y)
-{
-    return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, w), x), __fmul_rn(w, y));
-}
 
 __global__ void __launch_bounds__(kThreads) transform_kernel(const float *__restrict__ f0, const float *__restrict__ a,
                                                              const float *__restrict__ c, const float *__restrict__ noise,
@@ -113,18 +104,7 @@ __global__ void __launch_bounds__(kThreads) transform_kernel(const float *__rest
             const int ko = 64 * sl + lane;
             float v = 0.0f;
             if (live && ko < H_out) {
-                const double u = (double)(ko + 1) * rq;         // positive and finite
-                float2 e = make_float2(0.0f, 0.0f);             // u > H
-                if (u < 1.0) {
-                    e = amp[0];
-                } else if (u < (double)H) {
-                    const int m = (int)u;                       // 1 <= m <= H - 1
-                    const float mu = (float)(u - (double)m);
-                    const float2 lo = amp[m - 1], hi = amp[m];
-                    e = make_float2(convex(mu, lo.x, hi.x), convex(mu, lo.y, hi.y));
-                } else if (u == (double)H) {
-                    e = amp[H - 1];
-                }
+                const float2 e = envelope_pair(amp, H, (double)(ko + 1) * rq);  // u is positive and finite
                 v = convex(lam, e.x, e.y);
                 if (__fmul_rn((float)(ko + 1), f0o) > nyquist) v = 0.0f;
             }

@@ -647,6 +647,42 @@ int ddsp_transform_controls(const float *f0, const float *a, const float *c, con
                             long T_out, int H, int H_out, int F, int sample_rate, void *stream);
 
 /*
+ * Morph of two sets of analysed controls (DESIGN.md section 14c has the definition): pitch, spectral envelope and noise bands
+ * between those of sound A and sound B.  All fp32, dense row-major; rows are independent.  Per sound X in {a, b}:
+ *   f0_X [B, T_X] Hz, a_X [B, T_X], c_X [B, T_X, H_X], noise_X [B, T_X, F] or NULL, pos_X [B, T_out] the source position of every
+ *   output frame in X's frames;  mix_f0, mix_amp, mix_noise [B, T_out]: the weight of B for the pitch, the envelope, the bands.
+ * A_X[i, k], the amplitudes the bank plays, E_X,i(u), and of pos_X the pair i0, i1 and lambda_X are ddsp_transform_controls'.
+ * f_X = fl32((1 - lambda_X) f0_X[i0] + lambda_X f0_X[i1]) where both frames are voiced, else the voiced one's f0; X is present
+ * where one of them is voiced.  Output frame t', with the weights w_f, w_h, w_n clamped to [0, 1]:
+ *   f0_out = f_a at w_f = 0, f_b at w_f = 1, else fl32(exp2((1 - w_f) log2 f_a + w_f log2 f_b)) in double, kept within
+ *            [min(f_a, f_b), max(f_a, f_b)]; with one sound present that sound's f_X; with none 0
+ *   u_X = k' (coordinates DDSP_MORPH_HARMONIC) or (double)k' ((double)f0_out / (double)f_X) (DDSP_MORPH_HZ), k' = 1 .. H_out
+ *   e_X[k'] = (1 - lambda_X) E_X,i0(u_X) + lambda_X E_X,i1(u_X), 0 where X is not present
+ *   A'[k'] = (1 - w_h) e_a + w_h e_b; 0 where fl32(k' f0_out) > sample_rate / 2 (integer division, as the bank masks)
+ *   a_out = sum_k' A', c_out = A' / a_out, and c_out = 1 / H_out where a_out = 0
+ *   noise_out[j] = (1 - w_n) X_a[j] + w_n X_b[j], X_X[j] = (1 - lambda_X) noise_X[i0, j] + lambda_X noise_X[i1, j]
+ * Every combination is (1 - w) x + w y with each product and the sum rounded to fp32: a weight of 0 or 1 selects an input, and
+ * with all three at 0 (at 1) the outputs are, on finite and non-negative controls, the bits of ddsp_transform_controls on sound A
+ * (B) at pos_a (pos_b) and ratio = env = 1 -- but for f0_out of a frame where that sound is absent and the other present, which is
+ * the other's pitch at amplitude 0.  A frame with a weight that is not finite is silent: f0_out = 0, a_out = 0,
+ * c_out = 1 / H_out, noise_out = 0.
+ * -> f0_out [B, T_out], a_out [B, T_out], c_out [B, T_out, H_out], noise_out [B, T_out, F].  noise_a, noise_b and noise_out are all
+ * NULL or all set.  B == 0 returns 0; a null pointer, one or two of the noise pointers, a size that is not positive or
+ * coordinates that are neither constant: DDSP_EINVAL; H_a, H_b or H_out > 256, F > 257 (F is ignored but must be positive without
+ * noise), B T_a, B T_b or B T_out beyond 2^47 frames: DDSP_ERANGE.  No workspace, one launch, one wavefront per output frame
+ * (grid-strided beyond 8192 workgroups of four), no atomics, no allocation, no host synchronisation; every sum has one order: a
+ * frame's results are the same bits from run to run and whatever else is in the batch.  No input, NaN or huge, makes the kernel
+ * read or write outside its arrays.
+ */
+#define DDSP_MORPH_HZ 0
+#define DDSP_MORPH_HARMONIC 1
+int ddsp_morph_controls(const float *f0_a, const float *a_a, const float *c_a, const float *noise_a, const float *pos_a,
+                        const float *f0_b, const float *a_b, const float *c_b, const float *noise_b, const float *pos_b,
+                        const float *mix_f0, const float *mix_amp, const float *mix_noise, float *f0_out, float *a_out, float *c_out,
+                        float *noise_out, long B, long T_a, long T_b, long T_out, int H_a, int H_b, int H_out, int F, int sample_rate,
+                        int coordinates, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
