@@ -22,6 +22,7 @@ from .analysis import HarmonicAnalyzer, harmonic_analysis, harmonic_resynthesis,
 from .analysis import NoiseAnalyzer, noise_analysis  # noqa: F401
 from .analysis import ControlTransform, transform_controls  # noqa: F401
 from .analysis import ControlMorph, morph_controls  # noqa: F401
+from .analysis import ControlAlign, align_controls, control_features, dtw_align  # noqa: F401
 from .autoencoder import AutoEncoder  # noqa: F401
 from .dataset import AudioData, PLHDataset, load_audio, example_geometry  # noqa: F401
 from .spectral import griffinlim  # noqa: F401
@@ -35,6 +36,6 @@ from .training import MSSLoss, train_step, allreduce_gradients, OverlappedGradie
 __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "Crepe", "F0Encoder", "LoudnessEncoder", "Encoder", "pitch_voicing", "pitch_salience_yin", "AutoEncoder", "AudioData", "PLHDataset", "load_audio", "example_geometry", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency", "griffinlim",
            "normalize_audio", "prepare_spectra", "gram_matrix", "FeatureExtractor", "ContentLoss", "StyleLoss", "style_transfer",
            "analysis", "HarmonicAnalyzer", "harmonic_analysis", "harmonic_resynthesis", "harmonic_residual", "refine_f0", "NoiseAnalyzer", "noise_analysis",
-           "ControlTransform", "transform_controls", "ControlMorph", "morph_controls",
+           "ControlTransform", "transform_controls", "ControlMorph", "morph_controls", "ControlAlign", "align_controls", "control_features", "dtw_align",
            "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
            "latest_checkpoint"]

@@ -31,8 +31,8 @@ def build(force: bool = False, jobs: int = 4) -> str:
     return SO_PATH
 
 
-_vp, _i32, _u32, _u64, _long, _size, _f32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint64, ctypes.c_long,
-                                             ctypes.c_size_t, ctypes.c_float)
+_vp, _i32, _u32, _u64, _long, _size, _f32, _f64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint64, ctypes.c_long,
+                                                   ctypes.c_size_t, ctypes.c_float, ctypes.c_double)
 
 # The binding of every symbol include/ddsp_hip.h declares, in the header's order: name -> (restype, argtypes).
 # tests/test_host_abi.py checks it against the header's prototypes.
@@ -118,6 +118,8 @@ SIGNATURES = {
     "ddsp_noise_analysis_ola": (_i32, [_vp] * 4 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_transform_controls": (_i32, [_vp] * 11 + [_long, _long, _long, _i32, _i32, _i32, _i32, _vp]),
     "ddsp_morph_controls": (_i32, [_vp] * 17 + [_long, _long, _long, _long, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ddsp_dtw_workspace_bytes": (_size, [_long, _long, _long]),
+    "ddsp_dtw_align": (_i32, [_vp] * 8 + [_size, _long, _long, _long, _i32, _long, _long, _f32, _f64, _vp]),
     "ddsp_loudness_supported": (_i32, [_i32]),
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),

@@ -60,6 +60,18 @@ harmonics, and `positions_a` / `positions_b` take any time alignment:
 
 CUDA fp32 controls in the transformation's range take the HIP kernel (csrc/ddsp_morph.hip), one launch; everything else the same
 definition as stock torch ops.  No backward.
+
+Time alignment: which frame of one sound goes with which frame of the other (include/ddsp_hip.h:
+ddsp_dtw_align).  Dynamic time warping over per-frame features, the path resampled onto an output timeline as the
+`positions_a` / `positions_b` of `morph_controls`:
+
+  dtw_align(x_a, x_b, radius=None, penalty=0.0, timing=0.0, frames=None, return_path=False) -> positions_a, positions_b[, path, length, cost]
+  control_features(ctrl, sample_rate, n_bands=32, noise_groups=8, range_log2=10.0) -> [B, T, D]
+  align_controls(ctrl_a, ctrl_b, sample_rate, radius=None, penalty=0.0, timing=0.0, frames=None, return_path=False, **features)
+  ControlAlign(conf)                      nn.Module without parameters over conf.sample_rate
+
+CUDA fp32 features with D <= 64 and at most 2048 frames a sound take the HIP kernel (csrc/ddsp_align.hip), one launch for the
+recurrence, the walk back and the timeline; everything else the same definition as stock torch ops.  No backward.
 """
 from __future__ import annotations
 
@@ -88,6 +100,8 @@ MORPH_KERNEL_MAX_FRAMES = 2 ** 47        # csrc/ddsp_morph.hip: rows x frames of
 MORPH_KERNEL_MAX_BLOCKS = 8192
 MORPH_KERNEL_WAVES = 4
 MORPH_COORDINATES = {'hz': 0, 'harmonic': 1}    # include/ddsp_hip.h: DDSP_MORPH_HZ, DDSP_MORPH_HARMONIC
+DTW_KERNEL_MAX_FRAMES = 2048             # csrc/ddsp_align.hip: kMaxT, kMaxD
+DTW_KERNEL_MAX_FEATURES = 64
 
 
 def _check(audio, f0, hop, sample_rate, n_harmonics, win_length, voiced, what):
@@ -1030,3 +1044,231 @@ class ControlMorph(nn.Module):
 
     def forward(self, ctrl_a, ctrl_b, **keywords):
         return morph_controls(ctrl_a, ctrl_b, self.sample_rate, **keywords)
+
+
+# ----------------------------------------------------------------------------------------------------------- time alignment
+
+def _dtw_torch(x_a, x_b, radius, penalty):
+    """The recurrence of DESIGN.md section 14d as torch ops in the features' dtype, one anti-diagonal at a time, and the walk back
+    one step of all rows at a time (no host synchronisation): x_a [B, T_a, D], x_b [B, T_b, D] -> path int32 [B, T_a + T_b - 1, 2]
+    (-1 beyond length), length int32 [B], cost [B].  radius: an int or None."""
+    dt, dev = x_a.dtype, x_a.device
+    B, T_a, D = x_a.shape
+    T_b = x_b.shape[1]
+    inf = torch.full((), math.inf, dtype=dt, device=dev)
+    d = torch.zeros((B, T_a, T_b), dtype=dt, device=dev)
+    for k in range(D):                                          # ascending k, one accumulator
+        t = x_a[:, :, None, k] - x_b[:, None, :, k]
+        d = d + t * t
+    d = torch.where(d < inf, d, inf)                            # a NaN too
+    if radius is not None:
+        p, q = T_a - 1, T_b - 1
+        i, j = torch.arange(T_a, device=dev)[:, None], torch.arange(T_b, device=dev)[None, :]
+        d = torch.where((i * q - j * p).abs() <= radius * max(p, q), d, inf)
+    pen = torch.full((), penalty, dtype=dt, device=dev)
+    total = torch.empty_like(d)
+    back = torch.zeros((B, T_a, T_b), dtype=torch.uint8, device=dev)
+    total[:, 0, 0] = d[:, 0, 0]
+    for n in range(1, T_a + T_b - 1):
+        i = torch.arange(max(0, n - T_b + 1), min(n, T_a - 1) + 1, device=dev)
+        j = n - i
+        im, jm = (i - 1).clamp(min=0), (j - 1).clamp(min=0)
+        best, up, left = total[:, im, jm], total[:, im, j] + pen, total[:, i, jm] + pen
+        code = torch.zeros_like(best, dtype=torch.uint8)
+        take = up < best
+        best, code = torch.where(take, up, best), torch.where(take, 1, code)
+        take = left < best
+        best, code = torch.where(take, left, best), torch.where(take, 2, code)
+        first_row, first_col = (i == 0)[None, :], (j == 0)[None, :]
+        best = torch.where(first_row, left, torch.where(first_col, up, best))
+        code = torch.where(first_row, 2, torch.where(first_col, 1, code)).to(torch.uint8)
+        total[:, i, j] = d[:, i, j] + best
+        back[:, i, j] = code
+    longest = T_a + T_b - 1
+    rows = torch.arange(B, device=dev)
+    i = torch.full((B,), T_a - 1, dtype=torch.long, device=dev)
+    j = torch.full((B,), T_b - 1, dtype=torch.long, device=dev)
+    active = torch.ones((B,), dtype=torch.bool, device=dev)
+    length = torch.zeros((B,), dtype=torch.long, device=dev)
+    backwards = torch.full((B, longest, 2), -1, dtype=torch.long, device=dev)
+    for n in range(longest):
+        backwards[:, n, 0], backwards[:, n, 1] = torch.where(active, i, -1), torch.where(active, j, -1)
+        length = length + active
+        code = back[rows, i, j]
+        active = active & ((i > 0) | (j > 0))
+        di = torch.where(i == 0, 0, torch.where(j == 0, 1, (code != 2).long()))
+        dj = torch.where(i == 0, 1, torch.where(j == 0, 0, (code != 1).long()))
+        i, j = torch.where(active, i - di, i), torch.where(active, j - dj, j)
+    k = torch.arange(longest, device=dev)[None, :]
+    src = (length[:, None] - 1 - k).clamp(min=0)
+    path = torch.where((k < length[:, None])[..., None], backwards.gather(1, src[..., None].expand(-1, -1, 2)), -1)
+    return path.int(), length.int(), total[:, T_a - 1, T_b - 1]
+
+
+def _timeline_torch(path, length, T_a, T_b, tau, T_out):
+    """The path resampled onto T' frames in fp64 -> positions_a, positions_b fp32 [B, T']."""
+    dev = path.device
+    pi, pj = path[..., 0].double(), path[..., 1].double()
+    wa, wb = 1.0 - tau, tau
+    on = torch.arange(path.shape[1], device=dev)[None, :] < length[:, None]
+    s_k = torch.where(on, wa * pi + wb * pj, torch.full((), math.inf, dtype=torch.float64, device=dev))
+    S = wa * float(T_a - 1) + wb * float(T_b - 1)
+    t = torch.arange(T_out, dtype=torch.float64, device=dev)
+    s = (t * S / float(T_out - 1)).clamp(max=S) if T_out > 1 else torch.zeros_like(t)
+    s = s[None, :].expand(path.shape[0], -1).contiguous()
+    k = (torch.searchsorted(s_k, s, right=True) - 1).clamp(min=0)          # the largest k with s_k <= s
+    nxt = torch.minimum(k + 1, length[:, None].long() - 1)
+    s0, s1 = s_k.gather(1, k), s_k.gather(1, nxt)
+    lam = torch.where(nxt > k, (s - s0) / torch.where(nxt > k, s1 - s0, torch.ones_like(s)), torch.zeros_like(s))
+    out = []
+    for v in (pi, pj):
+        v0 = v.gather(1, k)
+        out.append((v0 + lam * (v.gather(1, nxt) - v0)).float())
+    return out[0], out[1]
+
+
+def _dtw_in_kernel_range(x_a, x_b, T_out) -> bool:
+    return (x_a.is_cuda and x_a.dtype == torch.float32 and max(x_a.shape[1], x_b.shape[1]) <= DTW_KERNEL_MAX_FRAMES
+            and x_a.shape[2] <= DTW_KERNEL_MAX_FEATURES and max(x_a.shape[0], T_out) <= 2 ** 31 - 1)
+
+
+def _dtw_device(x_a, x_b, radius, penalty, tau, T_out):
+    B, T_a, D = x_a.shape
+    T_b = x_b.shape[1]
+    dev = x_a.device
+    L = _lib.lib()
+    pos_a = torch.empty((B, T_out), dtype=torch.float32, device=dev)
+    pos_b = torch.empty_like(pos_a)
+    path = torch.empty((B, T_a + T_b - 1, 2), dtype=torch.int32, device=dev)
+    length = torch.empty((B,), dtype=torch.int32, device=dev)
+    cost = torch.empty((B,), dtype=torch.float32, device=dev)
+    nbytes = L.ddsp_dtw_workspace_bytes(B, T_a, T_b)
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.ddsp_dtw_align(x_a.data_ptr(), x_b.data_ptr(), pos_a.data_ptr(), pos_b.data_ptr(), path.data_ptr(), length.data_ptr(),
+                              cost.data_ptr(), workspace.data_ptr(), nbytes, B, T_a, T_b, D, T_out, 0 if radius is None else radius,
+                              penalty, tau, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_dtw_align")
+    return pos_a, pos_b, path, length, cost
+
+
+def dtw_align(x_a, x_b, radius=None, penalty=0.0, timing=0.0, frames=None, return_path=False):
+    """Dynamic time warping of two feature sequences x_a [B, T_a, D] and x_b [B, T_b, D] (any features; `control_features` makes
+    them of control dicts) -> positions_a, positions_b fp32 [B, T'], which frame of each sound every output frame reads: what
+    `morph_controls` takes.  With return_path=True also path int32 [B, T_a + T_b - 1, 2] (the cells (i, j)
+    from (0, 0) to the end cell, -1 beyond length), length int32 [B] and cost [B].
+
+    The local cost of frames i and j is the squared distance of their rows; a value that is not finite counts as +inf.  The path
+    steps diagonally, or by one frame of either sound at `penalty` (>= 0, finite) on top of the cost, which discourages long runs
+    that freeze one sound; ties go to the diagonal, then to the step in A.  radius (an integer >= 1, None: no band) keeps the path
+    within `radius` frames of the longer sound around the straight diagonal (a Sakoe-Chiba band in integer arithmetic).
+    timing in [0, 1] (clamped) chooses whose clock the output follows: 0 is A's (T' = T_a: positions_a = 0, 1, 2, ...), 1 is B's,
+    between them both are warped; frames sets T' (None: floor((1 - timing) T_a + timing T_b + 1/2), at least 1).
+    CUDA fp32 features with D <= 64 and T_a, T_b <= 2048 take the HIP kernel (csrc/ddsp_align.hip), one launch; CPU tensors, fp64
+    and larger sizes run the same definition as torch ops, one anti-diagonal at a time.  No backward."""
+    what = "dtw_align"
+    for name, v in (("x_a", x_a), ("x_b", x_b)):
+        if not torch.is_tensor(v) or v.dim() != 3 or v.shape[1] < 1 or v.shape[2] < 1 or not v.is_floating_point():
+            raise ValueError(f"{what}: {name} must be a floating-point tensor [B, T, D] with T, D >= 1")
+        _refuse_grad(v, what)
+    if x_a.shape[0] != x_b.shape[0] or x_a.shape[2] != x_b.shape[2] or x_a.device != x_b.device or x_a.dtype != x_b.dtype:
+        raise ValueError(f"{what}: the two sequences must have the same batch, feature count, device and dtype, got "
+                         f"{tuple(x_a.shape)} {x_a.dtype} on {x_a.device} and {tuple(x_b.shape)} {x_b.dtype} on {x_b.device}")
+    if radius is not None and (isinstance(radius, bool) or not isinstance(radius, int) or radius < 1):
+        raise ValueError(f"{what}: radius must be an integer >= 1 or None, got {radius!r}")
+    penalty, timing = float(penalty), float(timing)
+    if not (0.0 <= penalty < math.inf):
+        raise ValueError(f"{what}: penalty must be finite and >= 0, got {penalty}")
+    if not math.isfinite(timing):
+        raise ValueError(f"{what}: timing must be finite, got {timing}")
+    tau = min(1.0, max(0.0, timing))
+    B, T_a, D = x_a.shape
+    T_b = x_b.shape[1]
+    T_out = max(1, int(math.floor((1.0 - tau) * T_a + tau * T_b + 0.5))) if frames is None else int(frames)
+    if T_out < 1:
+        raise ValueError(f"{what}: frames must be positive, got {frames!r}")
+    if radius is not None and radius > max(T_a, T_b) - 1:
+        radius = None                                           # such a band holds every cell
+    dt = x_a.dtype if x_a.dtype in (torch.float32, torch.float64) else torch.float32
+    x_a, x_b = x_a.detach().to(dt).contiguous(), x_b.detach().to(dt).contiguous()
+    if B == 0:
+        dev = x_a.device
+        out = (torch.zeros((0, T_out), dtype=torch.float32, device=dev), torch.zeros((0, T_out), dtype=torch.float32, device=dev))
+        return out + (torch.zeros((0, T_a + T_b - 1, 2), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev),
+                      torch.zeros((0,), dtype=dt, device=dev)) if return_path else out
+    if _dtw_in_kernel_range(x_a, x_b, T_out):
+        pos_a, pos_b, path, length, cost = _dtw_device(x_a, x_b, radius, penalty, tau, T_out)
+    else:
+        path, length, cost = _dtw_torch(x_a, x_b, radius, penalty)
+        pos_a, pos_b = _timeline_torch(path, length, T_a, T_b, tau, T_out)
+    return (pos_a, pos_b, path, length, cost) if return_path else (pos_a, pos_b)
+
+
+def _level(x, range_log2):
+    """l(x) = (log2(max(x, 2^-L)) + L) / L: 0 at and below 2^-L, 1 at 1."""
+    return (torch.log2(x.clamp(min=2.0 ** -range_log2)) + range_log2) / range_log2
+
+
+def _over_row_max(x):
+    """x [B, ...] over its row's largest value; a row whose largest value is 0 stays 0."""
+    top = x.flatten(1).amax(1)
+    return x / torch.where(top > 0, top, torch.ones_like(top)).reshape((-1,) + (1,) * (x.dim() - 1))
+
+
+def control_features(ctrl, sample_rate, n_bands=32, noise_groups=8, range_log2=10.0):
+    """What makes two control dicts comparable frame by frame: [B, T, D] in the controls' dtype,
+    D = n_bands + 2 (+ noise_groups where the dict has the noise bands H), every value in [0, 1] over `range_log2` octaves of level:
+      the spectral envelope the bank plays, sampled at m (sample_rate // 2) / n_bands Hz, m = 1 .. n_bands -- on a frequency grid
+      that does not move with the pitch, so a phrase aligns with the same phrase sung a fifth higher; relative to the row's
+      largest sample, in log2, over sqrt(n_bands);
+      the noise bands pooled by their mean into `noise_groups` groups, the same way, over sqrt(noise_groups);
+      the level a relative to the row's largest voiced a, in log2 (0 on unvoiced frames); and 1 on voiced frames, 0 on unvoiced."""
+    what = "control_features"
+    f0, a, c, noise = _control_arrays(ctrl, what)
+    n_bands, noise_groups, range_log2, sample_rate = int(n_bands), int(noise_groups), float(range_log2), int(sample_rate)
+    if n_bands < 1 or noise_groups < 1 or sample_rate < 2 or not 0.0 < range_log2 < math.inf:
+        raise ValueError(f"{what}: n_bands, noise_groups and range_log2 must be positive and sample_rate at least 2")
+    dt = c.dtype
+    spacing = (sample_rate // 2) / n_bands
+    voiced = torch.isfinite(f0) & (f0 > 0)
+    semitones = 12.0 * torch.log2(spacing / f0.double())       # unvoiced: no usable ratio, and the frame comes out silent
+    on_grid = transform_controls(dict(f0=f0[..., None], a=a[..., None], c=c), sample_rate, transpose=semitones, formant=0.0,
+                                 n_harmonics=n_bands)
+    parts = [_level(_over_row_max(on_grid["a"] * on_grid["c"]), range_log2) / math.sqrt(n_bands)]
+    if noise is not None:
+        F = noise.shape[-1]
+        edges = [(g * F) // noise_groups for g in range(noise_groups + 1)]
+        pooled = torch.stack([noise[..., lo:hi].mean(-1) if hi > lo else torch.zeros_like(a) for lo, hi in zip(edges, edges[1:])], -1)
+        parts.append(_level(_over_row_max(pooled), range_log2) / math.sqrt(noise_groups))
+    zero = torch.zeros((), dtype=dt, device=c.device)
+    parts.append(torch.where(voiced, _level(_over_row_max(torch.where(voiced, a, zero)), range_log2), zero)[..., None])
+    parts.append(voiced.to(dt)[..., None])
+    return torch.cat(parts, -1)
+
+
+def align_controls(ctrl_a, ctrl_b, sample_rate, radius=None, penalty=0.0, timing=0.0, frames=None, return_path=False, **features):
+    """`control_features` of two control dicts (the same B and device; the noise bands H in both with one F, or in neither) and
+    `dtw_align` of the two -> positions_a, positions_b [B, T'] for `morph_controls` (and the path, its length and its cost with
+    return_path=True).  `features`: control_features' n_bands, noise_groups and range_log2."""
+    what = "align_controls"
+    src_a, src_b = _control_arrays(ctrl_a, what + " (sound A)"), _control_arrays(ctrl_b, what + " (sound B)")
+    c_a, c_b = src_a[2], src_b[2]
+    if c_a.shape[0] != c_b.shape[0] or c_a.device != c_b.device or c_a.dtype != c_b.dtype:
+        raise ValueError(f"{what}: the two sounds must have the same batch, device and dtype, got {tuple(c_a.shape)} {c_a.dtype} on "
+                         f"{c_a.device} and {tuple(c_b.shape)} {c_b.dtype} on {c_b.device}")
+    if (src_a[3] is None) != (src_b[3] is None) or (src_a[3] is not None and src_a[3].shape[-1] != src_b[3].shape[-1]):
+        raise ValueError(f"{what}: the noise bands H must be in both dicts with the same number of bands, or in neither")
+    return dtw_align(control_features(ctrl_a, sample_rate, **features), control_features(ctrl_b, sample_rate, **features),
+                     radius=radius, penalty=penalty, timing=timing, frames=frames, return_path=return_path)
+
+
+class ControlAlign(nn.Module):
+    """forward(ctrl_a, ctrl_b, radius=None, penalty=0.0, timing=0.0, frames=None, return_path=False, **features): `align_controls`
+    at the configuration's sample_rate.  No parameters."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.sample_rate = conf.sample_rate
+
+    def forward(self, ctrl_a, ctrl_b, **keywords):
+        return align_controls(ctrl_a, ctrl_b, self.sample_rate, **keywords)

@@ -10,9 +10,10 @@
                              analyse, analysis.transform_controls (time stretch, transposition, formant shift), synthesize:
                              audio [B, T' hop]
   morph(x, y, mix=0.5, mix_f0=None, mix_harmonics=None, mix_noise=None, coordinates='hz', frames=None, positions_a=None,
-        positions_b=None, noise=True, refine=0, reverb=False)
+        positions_b=None, noise=True, refine=0, reverb=False, align=False, timing=0.0, radius=None, penalty=0.0)
                              analyse both clips, analysis.morph_controls (pitch, envelope and noise between the two), synthesize:
-                             audio [B, T' hop]
+                             audio [B, T' hop]; align=True first finds which frame of x goes with which frame of y
+                             (analysis.align_controls: dynamic time warping) instead of stretching both linearly
   forward_live(x, hidden, delayed=False)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -30,7 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .analysis import harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
+from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
 
@@ -101,14 +102,23 @@ class AutoEncoder(nn.Module):
             return self.decoder.reverb(y) if reverb else y
 
     def morph(self, x: torch.Tensor, y: torch.Tensor, mix=0.5, mix_f0=None, mix_harmonics=None, mix_noise=None, coordinates='hz',
-              frames=None, positions_a=None, positions_b=None, noise=True, refine: int = 0, reverb: bool = False) -> torch.Tensor:
+              frames=None, positions_a=None, positions_b=None, noise=True, refine: int = 0, reverb: bool = False, align: bool = False,
+              timing=0.0, radius=None, penalty=0.0) -> torch.Tensor:
         """audio x [B, L_x] and y [B, L_y] (the lengths may differ) -> audio [B, T' hop] between the two, without the decoder's
         network: `analyse` of both (noise and refine as in `transform`), analysis.morph_controls on the two dicts (`mix`, 0 is x and
         1 is y, a float or per output frame; `mix_f0`, `mix_harmonics`, `mix_noise`, `coordinates`, `frames` -- None: x's frames --,
         `positions_a`, `positions_b`), then `decoder.synthesize`, and `decoder.reverb` only when asked.  noise=False plays the
-        harmonics alone (`decoder.harmonics`)."""
-        ctrl = morph_controls(self.analyse(x, noise=noise, refine=refine), self.analyse(y, noise=noise, refine=refine),
-                              self.decoder.harmonics.sample_rate, mix=mix, mix_f0=mix_f0, mix_harmonics=mix_harmonics, mix_noise=mix_noise,
+        harmonics alone (`decoder.harmonics`).  align=True finds the two positions by analysis.align_controls (dynamic time warping
+        of the two analysed dicts; `timing`, 0 is x's clock and 1 is y's, `radius`, `penalty`; `frames` is then the timeline's T')
+        instead of stretching both clips linearly; positions_a / positions_b must then be left out."""
+        if align and (positions_a is not None or positions_b is not None):
+            raise ValueError("morph: align=True finds positions_a and positions_b; give one or the other")
+        ctrl_x, ctrl_y = self.analyse(x, noise=noise, refine=refine), self.analyse(y, noise=noise, refine=refine)
+        if align:
+            positions_a, positions_b = align_controls(ctrl_x, ctrl_y, self.decoder.harmonics.sample_rate, radius=radius, penalty=penalty,
+                                                      timing=timing, frames=frames)
+            frames = None
+        ctrl = morph_controls(ctrl_x, ctrl_y, self.decoder.harmonics.sample_rate, mix=mix, mix_f0=mix_f0, mix_harmonics=mix_harmonics, mix_noise=mix_noise,
                               coordinates=coordinates, frames=frames, positions_a=positions_a, positions_b=positions_b)
         with torch.no_grad():
             out = self.decoder.synthesize(ctrl) if noise else self.decoder.harmonics(ctrl)

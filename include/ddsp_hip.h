@@ -683,6 +683,32 @@ int ddsp_morph_controls(const float *f0_a, const float *a_a, const float *c_a, c
                         int coordinates, void *stream);
 
 /*
+ * Dynamic time warping of two feature sequences (DESIGN.md section 14d has the definition): which frame of A goes with which
+ * frame of B, and that path resampled onto an output timeline as the positions ddsp_morph_controls takes.  Rows are independent.
+ *   x_a [B, T_a, D], x_b [B, T_b, D] fp32 feature rows.  Every product and sum below is rounded to fp32 on its own.
+ *   d(i, j) = sum_k (x_a[i, k] - x_b[j, k])^2, ascending k, one accumulator; a value that is not < +inf (a NaN too) counts as +inf
+ *   band: with p = T_a - 1, q = T_b - 1 (64-bit integers), d(i, j) = +inf where |i q - j p| > radius max(p, q); radius 0: no band
+ *   D(0, 0) = d(0, 0); D(i, j) = d(i, j) + best, best the first of D(i - 1, j - 1), D(i - 1, j) + penalty, D(i, j - 1) + penalty
+ *   (those that exist, in this order) that no later one is strictly below; the chosen one is the cell's back-pointer
+ *   path: the back-pointers from (T_a - 1, T_b - 1) to (0, 0), in forward order; cost = D(T_a - 1, T_b - 1)
+ *   timeline (fp64): tau = timing clamped to [0, 1], s_k = (1 - tau) i_k + tau j_k, S = s of the end cell; output frame t' targets
+ *   s = min(t' S / (T_out - 1), S) (0 for T_out = 1); with k the largest index with s_k <= s the positions are the end cell where
+ *   k is the last point, else (i_k, j_k) + lambda (i_k+1 - i_k, j_k+1 - j_k), lambda = (s - s_k) / (s_k+1 - s_k), rounded once to fp32
+ * -> pos_a, pos_b [B, T_out] fp32 (monotone, inside [0, T_X - 1]), path [B, T_a + T_b - 1, 2] int32 (entries beyond length are -1),
+ * length [B] int32 in [max(T_a, T_b), T_a + T_b - 1], cost [B] fp32.
+ * workspace: ddsp_dtw_workspace_bytes(B, T_a, T_b) bytes of device memory for the back-pointers (0 outside the range below).
+ * B == 0 returns 0; a null pointer, B < 0, T_a, T_b, D or T_out that is not positive, radius < 0, a penalty that is negative or
+ * not finite, a timing that is not finite or a workspace that is too small is DDSP_EINVAL, before anything touches the device;
+ * T_a or T_b > 2048, D > 64, B or T_out beyond 2^31 - 1: DDSP_ERANGE.  One launch, one wavefront per row, no atomics, no allocation,
+ * no host synchronisation; a row's results are the same bits from run to run and whatever else is in the batch.  No feature
+ * value, NaN or huge, reaches an index: the kernel reads and writes inside its arrays whatever they hold.
+ */
+size_t ddsp_dtw_workspace_bytes(long B, long T_a, long T_b);
+int ddsp_dtw_align(const float *x_a, const float *x_b, float *pos_a, float *pos_b, int *path, int *length, float *cost,
+                   void *workspace, size_t workspace_bytes, long B, long T_a, long T_b, int D, long T_out, long radius, float penalty,
+                   double timing, void *stream);
+
+/*
  * A-weighted loudness (model/autoencoder/encoder.py:131-156): x [B, L] -> out [B, F], F = 1 + (L - n_fft) / hop,
  *   out[b, f] = mean over k = 0 .. n_fft/2 of (20 log10(|X_f[k]| + 1e-20) + a_weight[k]) / 90 + 1
  * with X_f the un-windowed DFT of x[b, f * hop .. f * hop + n_fft) (torch.stft center=False, no window); a_weight [n_fft/2 + 1]
