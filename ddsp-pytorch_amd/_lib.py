@@ -57,6 +57,7 @@ SIGNATURES = {
     "ddsp_osc_clock": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_double), _vp]),
     "ddsp_noise_set_residency": (_i32, [_i32]),
     "ddsp_noise_get_residency": (_i32, []),
+    "ddsp_noise_conv_probe": (_i32, [_vp, _vp, _vp, _vp]),
     "ddsp_noise_set_generic": (_i32, [_i32]),
     "ddsp_profile_enable": (_i32, [_i32]),
     "ddsp_profile_select": (_i32, [_u32]),

@@ -2,12 +2,12 @@
 // Same arithmetic contract as ddsp_noise.hip (model/ddsp/filtered_noise.py:7-53); different organisation (noise section):
 //
 //   * ONE WAVEFRONT owns a group of 16 frames at a time and shares nothing with other wavefronts: no workgroup barrier anywhere
-//     (64-thread workgroups, 17.4 KB of LDS each, four per CU by default -- launch_noise_wave says why not eight; LDS operations of one wavefront execute in order,
+//     (64-thread workgroups, 17.7 KB of LDS each, four per CU by default -- launch_noise_wave says why not eight; LDS operations of one wavefront execute in order,
 //     which is all the hand-offs between the stages need).  Persistent: a wavefront walks groups g, g + grid, ...
 //   * software pipeline over the groups, written so that every global access sits in straight-line code (the compiler's
 //     `s_waitcnt vmcnt` are then exact counts, not drains): the NEXT group's filter magnitudes (16 x 65 contiguous floats) are
 //     fetched into registers before this group's noise draw and convolution; when accumulating, this group's 8 KB of y is read
-//     (whole lines) between the two convolution passes and added + stored inside the next group's impulse-response step.
+//     (whole lines) between the two halves of the convolution and added + stored inside the next group's impulse-response step.
 //   * impulse responses (:8-20): z = irfft(H) is a product with ONE cosine matrix shared by every frame,
 //         E'[f][n] = sum_{k even} w_k H[f][k] cos(2 pi k n / 128)   (w = 1/2 for k in {0, 64}),   O[f][n] = sum_{k odd} H[f][k] cos(2 pi k n / 128),
 //         z[n] = (E' + O) / 64,  z[64 - n] = (E' - O) / 64,  n = 0..31   (cos(2 pi k (64 - n) / 128) = (-1)^k cos(2 pi k n / 128)),
@@ -23,12 +23,18 @@
 //     fixed tap index n on every lane: the PRODUCING lane windows z (periodic Hann, :15) and stores it at both of its wrapped
 //     positions (:14,:19-20) -- no scatter pass, no table.  n = 32 is one signed sum.
 //   * noise (:44-48): the injected draw or Philox4x32-10, counter layout of ddsp_noise_common.h (streams identical to every other form).
-//   * truncated convolution (:25-32), register blocked 8 outputs x 8 taps (6 ds_read_b128 per 64 multiply-adds), operands of the
-//     next block read while this one is multiplied.  Lanes are (frame, quarter): the lanes that share a ds_read_b128 service
-//     group are 16 DIFFERENT frames of the same quarter, and the row strides are 4 x odd, so every read is bank-conflict-free
-//     whatever the quarters are working on.  A quarter owns the output chunks {15-s, s} then {8+s, 7-s}: 17 blocks per pass for
-//     every lane (uniform trip count); the switch between a pass's two chunks is the only divergent instruction group.
-//   * output: the group's 16 x 128 results are contiguous in y; staged through LDS (over the noise tile) and stored as whole lines.
+//   * truncated convolution (:25-32) on the matrix cores in exact fp32: v_mfma_f32_4x4x1_16b_f32 is sixteen independent 4 x 4 outer
+//     products, one per frame of the group; with four consecutive taps as A and four noise samples four apart as B, the sixteen
+//     products of a frame are sixteen different outputs of one 16-sample window, each a (tap, source) pair of the convolution.  No
+//     operand is built: A and B are single dwords read from the tap and noise tiles (emitted in pairs, as ds_read2_b32), whose
+//     zero padding is the causal truncation
+//     (ddsp_noise_conv_plan.h has the index plan, the tile layouts and why the reads are bank-conflict-free).  576 instructions per
+//     group, 90 % of their products useful, into eight 4-register accumulators (one per window); every output is ONE fused
+//     multiply-add chain over its taps, in the order mu = tap mod 16 first.  A wavefront alone on its SIMD issues these at the
+//     pipe's full rate, which it cannot do with v_fma_f32 (8.2-8.5 cycles per instruction = 30-31 multiply-adds per cycle and SIMD
+//     against 16: tools/microbench/int_mfma_rates.hip, profiles/noise_conv_mfma_rates.txt).
+//   * output: lane 4 b + j ends up with y_b[16 o + 4 j .. + 3] in accumulator o: staged as float4 through LDS (over the noise tile)
+//     and stored as whole lines; the group's 16 x 128 results are contiguous in y.
 //
 // Only whole groups: the entry point hands a remainder of fewer than 16 frames to the batched kernel (same Philox counters).
 #include <hip/hip_runtime.h>
@@ -39,6 +45,7 @@
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
 #include "ddsp_noise_common.h"
+#include "ddsp_noise_conv_plan.h"
 
 using namespace ddsp_noise;
 
@@ -51,7 +58,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // (v4f, the compiler's own vector type, not HIP's float4 class: aggregates of the latter are not split into registers)
 struct Tile { v4f v[5]; };           // a group's 16 x 65 filter magnitudes, 260 x 16 bytes over 64 lanes
 struct Lines { v4f v[8]; };          // a group's 16 x 128 outputs, 512 x 16 bytes over 64 lanes
-struct Pass { float v[16]; };        // a lane's two output chunks of one convolution pass
+struct Acc { v4f d[8]; };            // the convolution's accumulators: window o of frame lane >> 2, samples 16 o + 4 (lane & 3) .. + 3
 struct Spectra { v4f e[2], o[2], h64; float z32; };
 
 // the one shape this form is built for (ddsp_noise_plan.h plans it for no other)
@@ -59,19 +66,21 @@ constexpr int R = kWaveHop;          // hop = samples per frame
 constexpr int F = kWaveBands;        // bands; S = 2 (F - 1) = 128 = R: the impulse response fills the frame exactly
 constexpr int FG = kWaveGroupFrames; // frames per group
 static_assert(R == 128 && F == 65 && FG == 16 && 2 * (F - 1) == R, "the kernel's register and LDS layouts are written for these");
-constexpr int KS = 132;           // kern / staging row stride (4 x 33)
-constexpr int XS = 140;           // noise row stride: 8 leading zeros + 128 samples + 4 (4 x 35)
-constexpr int kLdsFloats = FG * KS + FG * XS;
+namespace cp = ddsp_noise::conv;  // the convolution's index plan and the layouts of its two operand tiles
+constexpr int KS = cp::kTapStride;   // kern / staging row stride: 4 leading zeros + 128 taps
+constexpr int KP = cp::kTapPad;
+static_assert(cp::kFrames == FG && cp::kSamples == R && cp::kSrcFloats >= FG * KS, "the staging tile lies over the noise tile");
+constexpr int kLdsFloats = cp::kTapFloats + cp::kSrcFloats;
 
-// DDSP_NOISE_ABL (tools/build_variant.sh): timing-only ablation builds (results wrong): 1 = one convolution block per pass
-// instead of 17, 2 = no Philox rounds, 3 = no matrix-core products, 4 = no read / write of y
+// DDSP_NOISE_ABL (tools/build_variant.sh): timing-only ablation builds (results wrong): 1 = one residue mu per half of the
+// convolution instead of 8, 2 = no Philox rounds, 3 = no matrix-core products, 4 = no read / write of y
 #ifndef DDSP_NOISE_ABL
 #define DDSP_NOISE_ABL 0
 #endif
 
 // DDSP_NOISE_STAMPS (tools/build_variant.sh ... -DDDSP_NOISE_STAMPS): per-phase cycle counts of every wavefront, summed over its
-// groups, written to the buffer passed as the (then unused) injected draw: [grid][8] uint64 = setup, first convolution pass,
-// second pass, staging, H->LDS + operand reads + products, pending output, taps, noise.  tools/microbench/noise_stamps.py reads them.
+// groups, written to the buffer passed as the (then unused) injected draw: [grid][8] uint64 = setup, first half of the convolution,
+// second half, staging, H->LDS + operand reads + products, pending output, taps, noise.  tools/microbench/noise_stamps.py reads them.
 #ifdef DDSP_NOISE_STAMPS
 #define DDSP_STAMP(i) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
                            stamp_sum[i] += now_ - stamp_last; stamp_last = now_; } while (0)
@@ -79,12 +88,60 @@ constexpr int kLdsFloats = FG * KS + FG * XS;
 #define DDSP_STAMP(i) do { } while (0)
 #endif
 
+// Half of a group's convolution: the residues mu0 .. mu0 + 7 of ddsp_noise_conv_plan.h, 36 instructions each, added to acc.  The
+// operands of residue mu + 1 are read while residue mu is multiplied.  Within a residue the windows go 7 .. r for a = a_first + r, so
+// that no instruction of a residue waits for the accumulator of the one before it; only a residue's first instruction follows the
+// previous residue's last on window 7 (one dependent pair per 36; the compiler orders the 36 among themselves anyway).  kern, xs: the
+// tap and noise tiles of the plan.
+__device__ __forceinline__ Acc conv_half(const float *kern, const float *xs, int ln, int mu0, Acc acc)
+{
+    const int b = ln >> 2, q = ln & 3;
+    const float *ka = kern + b * cp::kTapStride + q;
+    const float *xb = xs + b * cp::kSrcRow + q;
+    float A[cp::kOperands], B[cp::kOperands], An[cp::kOperands], Bn[cp::kOperands];
+    auto fetch = [&](float (&a)[cp::kOperands], float (&bb)[cp::kOperands], int mu) {
+#pragma unroll
+        for (int r = 0; r < cp::kOperands; ++r) {
+            a[r] = ka[cp::tap_offset(mu, cp::a_first(mu) + r)];
+            bb[r] = xb[cp::src_offset(mu, cp::beta_first(mu) + r)];
+        }
+    };
+    fetch(A, B, mu0);
+#pragma unroll
+    for (int m = 0; m < (DDSP_NOISE_ABL == 1 ? 1 : cp::kMu / 2); ++m) {
+        if (m + 1 < cp::kMu / 2) fetch(An, Bn, mu0 + m + 1);
+#pragma unroll
+        for (int r = 0; r < cp::kOperands; ++r)
+#pragma unroll
+            for (int s = cp::kOperands - 1 - r; s >= 0; --s)
+                acc.d[cp::window_of(r, s)] = __builtin_amdgcn_mfma_f32_4x4x1f32(A[r], B[s], acc.d[cp::window_of(r, s)], 0, 0, 0);
+        // the next residue's reads lead, a whole residue (~300 cycles) ahead of their use, and this one's products follow (spreading
+        // the reads over the first 8, 16 or 24 products instead measured the same: 0.1250 / 0.1259 / 0.1260 / 0.1258 ms)
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * cp::kOperands, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, cp::kStepsPerMu, 0);
+        if (m + 1 < cp::kMu / 2) {
+#pragma unroll
+            for (int r = 0; r < cp::kOperands; ++r) { A[r] = An[r]; B[r] = Bn[r]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);                        // one residue ahead, not eight
+    }
+    return acc;
+}
+
+// the accumulators -> the staging tile [FG][KS]: four consecutive samples per lane and window
+__device__ __forceinline__ void stage_acc(float *ys, int ln, const Acc acc)
+{
+    float *row = ys + (ln >> 2) * KS + 4 * (ln & 3);
+#pragma unroll
+    for (int o = 0; o < cp::kWindows; ++o) *reinterpret_cast<v4f *>(row + cp::kWindow * o) = acc.d[o];
+}
+
 template <bool ACC>   // ACC: add to the output buffer's contents (harmonics + noise, decoder.py:132) instead of overwriting them
 __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long ngroups)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *kern = smem;                       // [FG][KS]; its first FG*F floats double as the H tile between two groups
-    float *xs = smem + FG * KS;               // [FG][XS]; doubles as the output staging tile [FG][KS] between two groups
+    float *xs = smem + cp::kTapFloats;        // [4][FG][36] by phase; doubles as the output staging tile [FG][KS] between two groups
     float *Hs = kern, *ys = xs;
     const int lane = threadIdx.x;
 #ifdef DDSP_NOISE_STAMPS
@@ -184,8 +241,10 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
     };
 
     // taps: lane (n = 16 t + mi) holds frames 4 mq + r.  z[n] -> kern[n], kern[128 - n]; z[64 - n] -> kern[64 - n], kern[64 + n]
+    // (rows start with KP zeros, the taps below 0 of the convolution's first steps: the H tile overwrote those of the first rows)
     auto taps = [&](const Spectra sp) {
         const int ln = opaque_lane(), mi = ln & 15, mq = ln >> 4;
+        kern[(ln >> 2) * KS + (ln & 3)] = 0.0f;
         const v4f (&accE)[2] = sp.e, (&accO)[2] = sp.o;
         const float z32 = sp.z32;
 #pragma unroll
@@ -193,7 +252,7 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
             const int n = 16 * t + mi;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float *kr = kern + (4 * mq + r) * KS;
+                float *kr = kern + (4 * mq + r) * KS + KP;
                 const float ev = accE[t][r] + ((mi & 1) ? -sp.h64[r] : sp.h64[r]);      // bin 64: cos(pi n) / 2
                 const float v1 = (ev + accO[t][r]) * w1[t];
                 const float v2 = (ev - accO[t][r]) * w2[t];
@@ -202,21 +261,26 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
                 kr[64 + n] = v2;                                  // n = 0: win(64) = 0, the reference's hann[0]
             }
         }
-        if (mq == 0) { kern[mi * KS + 32] = z32; kern[mi * KS + 96] = z32; }
+        if (mq == 0) { kern[mi * KS + KP + 32] = z32; kern[mi * KS + KP + 96] = z32; }
         DDSP_WAVE_ORDER();
     };
 
-    // noise -> xs[frame][8 + m], and the causal padding xs[frame][0..8) (the staging tile of the previous group overwrote it)
+    // noise -> the four phase planes of xs (sample 4 q + r of a frame: plane r, index 4 + q), and the causal padding, the first four
+    // floats of every (plane, frame) row (the staging tile of the previous group overwrote it): lane = (plane, frame)
+    auto put = [&](int fr, int q, const float4 v) {
+        float *d = xs + cp::src_slot(fr, 0) + q;
+        d[0] = v.x; d[cp::kSrcPlane] = v.y; d[2 * cp::kSrcPlane] = v.z; d[3 * cp::kSrcPlane] = v.w;
+    };
     auto draw = [&](long frame0) {
         const int ln = opaque_lane();
-        for (int e = ln; e < FG * 8; e += 64) xs[(e >> 3) * XS + (e & 7)] = 0.0f;
+        *reinterpret_cast<v4f *>(xs + (ln >> 4) * cp::kSrcPlane + (ln & 15) * cp::kSrcRow) = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
         if (p.u) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int qi = ln + 64 * j, fr = qi >> 5, q = qi & 31;
                 float4 v = *reinterpret_cast<const float4 *>(p.u + (frame0 + fr) * R + 4 * q);
                 v.x = v.x * 2.0f - 1.0f; v.y = v.y * 2.0f - 1.0f; v.z = v.z * 2.0f - 1.0f; v.w = v.w * 2.0f - 1.0f;
-                *reinterpret_cast<float4 *>(xs + fr * XS + 8 + 4 * q) = v;
+                put(fr, q, v);
             }
         } else {
             const uint64_t c0 = base_off + (uint64_t)frame0 * 32u + (uint64_t)ln;
@@ -229,86 +293,17 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
                 else philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)p.seed, (uint32_t)(p.seed >> 32), rr);
                 float4 v;
                 v.x = philox_to_sample(rr[0]); v.y = philox_to_sample(rr[1]); v.z = philox_to_sample(rr[2]); v.w = philox_to_sample(rr[3]);
-                *reinterpret_cast<float4 *>(xs + fr * XS + 8 + 4 * q) = v;
+                put(fr, q, v);
             }
         }
         DDSP_WAVE_ORDER();
     };
 
-    // One convolution pass: 17 blocks; the lane's output chunk cA (cA + 1 blocks) then cB = 15 - cA (cB + 1 blocks).  Fully
-    // unrolled: the operands of block t + 1 are read while block t is multiplied; block t reads k at kq + 8 t and the noise
-    // window at xq + 8 (16 - t), where the per-lane bases switch from chunk A's to chunk B's at t = tsw (9..16).
-    auto conv_pass = [&](int pass) {
-        const int ln = opaque_lane();
-        // convolution lanes: (quarter cs, frame cf) with the 16 lanes of a ds_read_b128 service group = 16 frames of one quarter
-        const int l5 = ln & 31, seg = l5 >> 2;
-        const int cf = ((seg >> 1) << 2) | (l5 & 3);
-        const int cs = 2 * (ln >> 5) + ((0x96 >> seg) & 1);
-        const float *krow = kern + cf * KS;
-        const float *xrow = xs + cf * XS + 8;
-        const int cA = pass ? 8 + cs : 15 - cs, cB = 15 - cA;
-        const int tsw = cA + 1;
-        const float *kq_a = krow, *kq_b = krow - 8 * tsw;
-        const float *xq_a = xrow + 8 * cA - 8 - 128, *xq_b = xrow + 8 * cB - 8 + 8 * tsw - 128;
-        float acc[8], first[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { acc[u] = 0.0f; first[u] = 0.0f; }
-        float4 cur[6], nxt[6];
-        auto fetch = [&](float4 (&d)[6], const float *kq, const float *xq, int t) {
-            d[0] = *reinterpret_cast<const float4 *>(kq + 8 * t);
-            d[1] = *reinterpret_cast<const float4 *>(kq + 8 * t + 4);
-            d[2] = *reinterpret_cast<const float4 *>(xq + 8 * (16 - t));
-            d[3] = *reinterpret_cast<const float4 *>(xq + 8 * (16 - t) + 4);
-            d[4] = *reinterpret_cast<const float4 *>(xq + 8 * (16 - t) + 8);
-            d[5] = *reinterpret_cast<const float4 *>(xq + 8 * (16 - t) + 12);
-        };
-        fetch(cur, kq_a, xq_a, 0);
-#pragma unroll
-        for (int t = 0; t < (DDSP_NOISE_ABL == 1 ? 1 : 17); ++t) {
-            if (t < 16) {
-                if (t + 1 < 9) fetch(nxt, kq_a, xq_a, t + 1);                    // every lane is still in its first chunk
-                else { const bool b = t + 1 >= tsw; fetch(nxt, b ? kq_b : kq_a, b ? xq_b : xq_a, t + 1); }
-            }
-            if (t >= 9 && t == tsw) {                             // chunk A done for this lane: park it, chunk B starts at zero
-                asm volatile("" ::: "memory");                    // (a real branch: taken by a quarter of the lanes at one t each)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { first[u] = acc[u]; acc[u] = 0.0f; }
-            }
-            asm volatile("" ::"v"(cur[2].x));                     // keep the window as 4 x ds_read_b128
-            const float kv[8] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w};
-            const float xw[16] = {cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w,
-                                  cur[4].x, cur[4].y, cur[4].z, cur[4].w, cur[5].x, cur[5].y, cur[5].z, cur[5].w};
-#pragma unroll
-            for (int v = 0; v < 8; ++v)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc[u] = __fmaf_rn(kv[v], xw[8 + u - v], acc[u]);
-#pragma unroll
-            for (int e = 0; e < 6; ++e) cur[e] = nxt[e];
-            __builtin_amdgcn_sched_barrier(0);                    // one block ahead, not seventeen
-        }
-        Pass out;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { out.v[u] = first[u]; out.v[8 + u] = acc[u]; }
-        return out;
-    };
-
-    // both passes' results -> the staging tile (over the noise tile: the convolution is done with it)
-    auto stage = [&](const Pass r0, const Pass r1) {
-        const int ln = opaque_lane();
-        const int l5 = ln & 31, seg = l5 >> 2;
-        const int cf = ((seg >> 1) << 2) | (l5 & 3);
-        const int cs = 2 * (ln >> 5) + ((0x96 >> seg) & 1);
+    // the convolution's two halves (conv_half) and the staging of its result (over the noise tile: the convolution is done with it)
+    auto conv = [&](int half, const Acc acc) { return conv_half(kern, xs, opaque_lane(), half * (cp::kMu / 2), acc); };
+    auto stage = [&](const Acc acc) {
         DDSP_WAVE_ORDER();
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const float (&r)[16] = pass ? r1.v : r0.v;
-            const int cA = pass ? 8 + cs : 15 - cs, cB = 15 - cA;
-            float *ya = ys + cf * KS + 8 * cA, *yb = ys + cf * KS + 8 * cB;
-            *reinterpret_cast<float4 *>(ya) = make_float4(r[0], r[1], r[2], r[3]);
-            *reinterpret_cast<float4 *>(ya + 4) = make_float4(r[4], r[5], r[6], r[7]);
-            *reinterpret_cast<float4 *>(yb) = make_float4(r[8], r[9], r[10], r[11]);
-            *reinterpret_cast<float4 *>(yb + 4) = make_float4(r[12], r[13], r[14], r[15]);
-        }
+        stage_acc(ys, opaque_lane(), acc);
         DDSP_WAVE_ORDER();
     };
 
@@ -334,8 +329,8 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
     };
 
     // ---- the pipeline -------------------------------------------------------------------------------------------------------
-    // Global reads are issued between a group's two convolution passes -- the next group's H tile, then (ACC) this group's y lines --
-    // and consumed after the second pass: some 8000 cycles later, which is what an HBM read takes under this kernel's own load
+    // Global reads are issued between the two halves of a group's convolution -- the next group's H tile, then (ACC) this group's y lines --
+    // and consumed after the second half: some thousands of cycles later, which is what an HBM read takes under this kernel's own load
     // (measured with the DDSP_NOISE_STAMPS build: reads issued 3000 cycles ahead still stalled the wavefront for 3000 more).
     long g = blockIdx.x;
     if (g >= ngroups) return;
@@ -356,13 +351,16 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
         }
         const long frame0 = g * FG;
         const long gn = g + gridDim.x;
-        const Pass r0 = conv_pass(0);
+        Acc acc;
+#pragma unroll
+        for (int o = 0; o < cp::kWindows; ++o) acc.d[o] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+        acc = conv(0, acc);
         DDSP_STAMP(1);
         hreg = load_tile(gn < ngroups ? gn : g);                  // (the last group re-reads its own tile: no branch around the loads)
         if (ACC && DDSP_NOISE_ABL != 4) yv = read_y(frame0);
-        const Pass r1 = conv_pass(1);
+        acc = conv(1, acc);
         DDSP_STAMP(2);
-        stage(r0, r1);
+        stage(acc);
         DDSP_STAMP(3);
         if (gn >= ngroups) break;
         const Spectra sp = products(hreg);                        // next group's impulse responses
@@ -381,6 +379,31 @@ __global__ void __launch_bounds__(64, 2) noise_wave_kernel(NoiseParams p, long n
     if (lane == 0)
         for (int i = 0; i < 8; ++i) stamp_out[i] = stamp_sum[i];
 #endif
+}
+
+// Test hook (ddsp_noise_conv_probe): the convolution stage of ONE group on the caller's taps and noise, k, x, y [FG][R].  The taps and
+// the samples go to the two tiles at the plan's slots, the padding is zero, and conv_half and stage_acc are the kernel's own.
+__global__ void __launch_bounds__(64) noise_conv_probe_kernel(const float *__restrict__ k, const float *__restrict__ x, float *__restrict__ y)
+{
+    __shared__ __attribute__((aligned(16))) float smem[kLdsFloats];
+    float *kern = smem, *xs = smem + cp::kTapFloats;
+    const int lane = threadIdx.x;
+    for (int e = lane; e < kLdsFloats; e += 64) smem[e] = 0.0f;
+    DDSP_WAVE_ORDER();
+    for (int e = lane; e < FG * R; e += 64) {
+        kern[cp::tap_slot(e / R, e % R)] = k[e];
+        xs[cp::src_slot(e / R, e % R)] = x[e];
+    }
+    DDSP_WAVE_ORDER();
+    Acc acc;
+#pragma unroll
+    for (int o = 0; o < cp::kWindows; ++o) acc.d[o] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+    acc = conv_half(kern, xs, lane, 0, acc);
+    acc = conv_half(kern, xs, lane, cp::kMu / 2, acc);
+    DDSP_WAVE_ORDER();
+    stage_acc(xs, lane, acc);
+    DDSP_WAVE_ORDER();
+    for (int e = lane; e < FG * R; e += 64) y[e] = xs[(e / R) * KS + e % R];
 }
 
 constexpr int kDefaultWavesPerCu = 4;
@@ -402,6 +425,14 @@ extern "C" int ddsp_noise_get_residency(void)
     return v >= 1 && v <= 8 ? v : kDefaultWavesPerCu;
 }
 
+extern "C" int ddsp_noise_conv_probe(const float *k, const float *x, float *y, void *stream)
+{
+    if (!ddsp_hooks_on()) return DDSP_EPERM;
+    if (!k || !x || !y) return DDSP_EINVAL;
+    hipLaunchKernelGGL(noise_conv_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, k, x, y);
+    return (int)hipGetLastError();
+}
+
 namespace ddsp_noise {
 
 hipError_t launch_noise_wave(const NoiseParams &p, long frames, hipStream_t s)
@@ -411,11 +442,14 @@ hipError_t launch_noise_wave(const NoiseParams &p, long frames, hipStream_t s)
     const hipError_t e = ddsp_device_cus(&cus);
     if (e != hipSuccess) return e;
     constexpr size_t lds = sizeof(float) * kLdsFloats;
-    // FOUR wavefronts per CU by default (17.4 KB of LDS each), not the eight that fit two per SIMD: at eight, this kernel's FMA + LDS +
-    // HBM activity makes the chip's power management drop the shader clock (2.41 -> ~2.1 GHz; it takes ~25 ms of load to come back), so
-    // the oscillator's kernels of the NEXT step pay 0.15 ms for the 0.04 ms saved here.  Where the clock gives way differs between
-    // boxes of the same model (below 8, below 6, below 5 wavefronts per CU on the three kinds measured); one wavefront per SIMD held it
-    // on all of them.  ddsp_noise_set_residency lets a caller that has measured ITS box take more (ddsp_pytorch_amd.
+    // FOUR wavefronts per CU by default (17.7 KB of LDS each), not the eight that fit two per SIMD: at eight, this kernel's activity makes
+    // the chip's power management drop the shader clock (it takes ~25 ms of load to come back), so the oscillator's kernels of the NEXT
+    // step pay more than is saved here.  Measured with the convolution as a v_fma_f32 + LDS stream (2.41 -> ~2.1 GHz; 0.15 ms paid for
+    // 0.04 saved; the clock gave way below 8, below 6, below 5 wavefronts per CU on the three kinds of box measured, and one wavefront
+    // per SIMD held it on all of them).  With the convolution on the matrix cores the same shows on the one box measured so far (forced
+    // to eight: the synth kernel 731 -> 766 us at 2.26-2.30 GHz), and the supposition -- from the kernel's wall time against its cycle
+    // count, not from a clock read inside it -- is that four busy matrix pipes per CU already lower the clock DURING this kernel (three
+    // per CU run its cycles at 2.4 GHz).  The calibration measures the step, so it sees either effect.  ddsp_noise_set_residency lets a caller that has measured ITS box take more (ddsp_pytorch_amd.
     // calibrate_noise_residency does the measuring; profiles/r04_clock_ramp.txt, tools/microbench/noise_residency_sweep.sh).
     const int asked = g_residency.load(std::memory_order_relaxed);
     const long per_cu = asked >= 1 && asked <= 8 ? asked : kDefaultWavesPerCu;

@@ -203,6 +203,12 @@ int ddsp_osc_clock(const void *scratch, int B, int T, int H, int hop, int sample
  * calibrate_noise_residency) and set more.  Results are bit-identical whatever the value.  Process-global, read once per launch. */
 int ddsp_noise_set_residency(int waves_per_cu);
 int ddsp_noise_get_residency(void);
+/* Test hook (DDSP_EPERM unless DDSP_TEST_HOOKS=1 was set when the library was loaded): the convolution stage of that kernel alone, on
+ * one group of 16 frames, for tests/test_gpu_noise_conv_stage.py.  k (taps), x (noise) and y are device memory, [16][128] floats:
+ * y[b][n] = sum_{m <= n} k[b][m] x[b][n - m], every output one fused multiply-add chain in fp32 (csrc/ddsp_noise_conv_plan.h).  The
+ * kernel puts k and x into the two LDS tiles, runs the production kernel's own convolution and staging code and copies the staging
+ * tile out; it does no arithmetic of its own.  A null pointer: DDSP_EINVAL.  One launch of one wavefront on `stream`. */
+int ddsp_noise_conv_probe(const float *k, const float *x, float *y, void *stream);
 
 /* Test / tuning hook (process-global, read once per launch): bit 0 forces the generic one-frame-per-workgroup noise kernels
  * (any hop) instead of the batched ones (hop % 8 == 0, tile fits LDS); bit 1 keeps the direct (time-domain) forms where the

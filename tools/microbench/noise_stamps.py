@@ -25,7 +25,7 @@ for acc in (True, False):
         torch.cuda.synchronize()
     st = buf.view(torch.int64).reshape(-1)[:2048 * 8].reshape(2048, 8).cpu().numpy().astype(np.float64)
     groups = np.full(2048, B * T / 16 / 2048)                    # groups per wavefront (7 or 8)
-    names = ["setup+first group's impulse responses and draw", "convolution pass 0", "convolution pass 1 (+ y read issue)", "staging",
+    names = ["setup+first group's impulse responses and draw", "convolution, first half", "convolution, second half (+ y read issue)", "staging",
              "H->LDS + operand reads + products", "pending output (add + store)", "taps", "noise draw (+ next H tile issue)"]
     per_group = {n: round(float(st[:, i].sum() / groups.sum()), 1) for i, n in enumerate(names)}
     per_group[names[0]] = round(float(st[:, 0].mean()), 1)       # once per wavefront
