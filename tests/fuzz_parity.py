@@ -6,13 +6,14 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder | griffinlim]   (`training`: the loss-side kernels against
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder | griffinlim | mss]   (`training`: the loss-side kernels against
 fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
 backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
 fp64 reference of tests/noise_grad_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
 reference of tests/gru_reference.py; `encoder`: the encoder's loudness and resampler kernels against the fp64 references of
 tests/encoder_reference.py; `griffinlim`: Griffin-Lim's synthesis, overlap-add and analysis kernels one at a time through
-ddsp_griffinlim_stage against the fp64 reference and the criteria of tests/griffinlim_reference.py)"""
+ddsp_griffinlim_stage against the fp64 reference and the criteria of tests/griffinlim_reference.py; `mss`: one spectral-loss
+scale through ddsp_mss_scale, every bin of its gradient spectrum against the fp64 reference and bounds of tests/mss_reference.py)"""
 import os
 import sys
 
@@ -31,6 +32,7 @@ import noise_grad_reference as R_noise  # noqa: E402
 import gru_reference as R_gru  # noqa: E402
 import encoder_reference as R_enc  # noqa: E402
 import griffinlim_reference as R_gl  # noqa: E402
+import mss_reference as R_mss  # noqa: E402
 
 
 def bits(a):
@@ -741,9 +743,33 @@ def sweep_griffinlim_stages(cases: int, seed: int, verbose: bool = True):
     return bad, report
 
 
+def sweep_mss_stages(cases: int, seed: int, verbose: bool = True):
+    """Random cases of ONE spectral-loss scale through ddsp_mss_scale directly (R_mss.random_case: random n_fft, hop 1 .. n_fft, B, L,
+    alpha, eps and, in half the cases, hop-long segments at their own levels) under the criteria of tests/mss_reference.py: every
+    bin of every frame of the gradient spectrum within its derived bound (or CPU_FACTOR times the stock fp32 formulation's error),
+    undecided bins against the candidate signs and at most 0.5 % of a case's bins, lin and log each within 2e-5, the same three
+    floats without grad_frames.  -> (failed, worst error / bound)"""
+    rng = np.random.default_rng(seed)
+    bad, worst = 0, 0.0
+    for i in range(cases):
+        case = R_mss.random_case(rng)
+        xp, xt = R_mss.case_inputs(case)
+        lines = []
+        okay, w, _, _ = R_mss.run_case(xp, xt, case["n_fft"], case["hop"], case["alpha"], case["eps"], f"case {i}", lines)
+        bad += not okay
+        worst = max(worst, w)
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} case {i}: {case}\n  " + "\n  ".join(lines), flush=True)
+    return bad, worst
+
+
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2026
+    if len(sys.argv) > 3 and sys.argv[3] == "mss":
+        bad, worst = sweep_mss_stages(cases, seed, verbose=True)
+        print(f"spectral-loss scale, bin by bin: cases {cases}, seed {seed}, failed {bad}, worst error / bound {worst:.3f}")
+        sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "griffinlim":
         bad, _ = sweep_griffinlim_stages(cases, seed, verbose=True)
         print(f"Griffin-Lim stages: cases {cases}, seed {seed}, failed {bad}")

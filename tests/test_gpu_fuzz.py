@@ -1,13 +1,14 @@
 """A fixed-seed slice of the randomised parity sweep (tests/fuzz_parity.py) in the GPU suite: 150 random shapes of the
 oscillator bank and the filtered noise through the C ABI against the CPU oracle -- phases bit-exact, audio <= 1e-5, noise <= 2e-6 --
 plus the chunked oscillator form, the loss-side kernels, the backward of the oscillator and of the filtered noise, the GRU
-recurrence step by step against fp64, the encoder's loudness and resampler kernels against fp64, and Griffin-Lim's three kernels
-one at a time against fp64."""
+recurrence step by step against fp64, the encoder's loudness and resampler kernels against fp64, Griffin-Lim's three kernels
+one at a time against fp64, and one spectral-loss scale bin by bin against fp64."""
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 import fuzz_parity  # noqa: E402
+import mss_reference  # noqa: E402
 
 
 @pytest.mark.parametrize("seed", [11, 12, 13])
@@ -72,3 +73,14 @@ def test_random_cases_of_the_griffinlim_stages_match_fp64(seed):
     under the derived ceiling, the overlap-add bit for bit its fp32 restatement and within the summation bound."""
     bad, report = fuzz_parity.sweep_griffinlim_stages(40, seed, verbose=False)
     assert bad == 0, (bad, report)
+
+
+
+@pytest.mark.parametrize("seed", mss_reference.SWEEP_SEEDS)
+def test_random_cases_of_one_spectral_loss_scale_match_fp64_bin_by_bin(seed):
+    """30 random cases of ddsp_mss_scale called directly (random n_fft, hop 1 .. n_fft, B, L, alpha, eps, segment levels) under the
+    criteria of tests/mss_reference.py: every bin of the gradient spectrum within its derived bound or CPU_FACTOR times the stock
+    fp32 formulation's error, undecided bins against the candidate signs and under their cap, lin and log each within 2e-5."""
+    bad, worst = fuzz_parity.sweep_mss_stages(mss_reference.SWEEP_CASES, seed, verbose=False)
+    print(f"MSS sweep seed {seed}: worst error / bound {worst:.4f}")
+    assert bad == 0 and worst <= 1.0, (bad, worst)
