@@ -107,6 +107,11 @@ SIGNATURES = {
     "ddsp_pitch_viterbi": (_i32, [_vp] * 6 + [_long, _long, _vp]),
     "ddsp_pitch_voicing_workspace_bytes": (_size, [_long, _long]),
     "ddsp_pitch_voicing": (_i32, [_vp] * 11 + [_long, _long, _i32, _i32, _f32, _f32, _f32, _i32, _vp]),
+    "ddsp_condition_accum_bytes": (_size, [_long, _i32]),
+    "ddsp_condition_launch_shape": (_i32, [_i32, _long, _long, ctypes.POINTER(_i32), ctypes.POINTER(_long)]),
+    "ddsp_condition_stats": (_i32, [_vp] * 5 + [_long, _long, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
+    "ddsp_condition_tables": (_i32, [_vp] * 5 + [_long, _i32, _i32, _f32, _f32, _vp]),
+    "ddsp_condition_apply": (_i32, [_vp] * 14 + [_long] * 4 + [_i32] * 4 + [_f32, _long, _vp]),
     "ddsp_yin_salience": (_i32, [_vp] * 3 + [_long, _long, _i32, _long, _vp]),
     "ddsp_harm_workspace_bytes": (_size, [_long, _long, _i32]),
     "ddsp_harm_analysis": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),

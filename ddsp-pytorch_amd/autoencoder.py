@@ -14,10 +14,15 @@
                              analyse both clips, analysis.morph_controls (pitch, envelope and noise between the two), synthesize:
                              audio [B, T' hop]; align=True first finds which frame of x goes with which frame of y
                              (analysis.align_controls: dynamic time warping) instead of stretching both linearly
-  forward_live(x, hidden, delayed=False)
+  transfer(x, target, **fit_options)
+                             forward with conditioning.fit_conditioning between encoder and decoder: the clip's register moved by
+                             whole octaves towards, and its loudness quantile-mapped onto, `target` (the ConditioningStatistics of
+                             the decoder's training set)
+  forward_live(x, hidden, delayed=False, conditioning=None)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
-                             encoder, then Decoder.forward_live -> (audio as numpy, hidden)
+                             encoder, then Decoder.forward_live -> (audio as numpy, hidden); conditioning=(target, source) maps
+                             the block (one launch) between the two
 
 State-dict keys are the reference's (`encoder.f0_encoder.model.*`, `encoder.loudness_encoder.a_weight`, `decoder.*`).  CREPE
 weights come from `weights` or `conf.crepe_weights` (see encoder.F0Encoder); `voicing` and `tracker` are handed to `Encoder`.
@@ -31,6 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .conditioning import fit_conditioning
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
@@ -48,6 +54,15 @@ class AutoEncoder(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
         return self.decoder(self.encoder(x))
+
+    def transfer(self, x: torch.Tensor, target, **fit_options) -> torch.Tensor:
+        """audio [B, L] -> audio: `forward` with the encoder's controls brought into `target`'s range on the way
+        (conditioning.fit_conditioning and its options: source, octaves, max_octaves, strength, min_frames).  Without a
+        `source` every clip is measured by itself, over its whole length."""
+        if fit_options.get('return_info'):
+            raise ValueError("transfer returns audio; ask fit_conditioning itself for the info")
+        x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
+        return self.decoder(fit_conditioning(self.encoder(x), target, **fit_options))
 
     def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,
                 refine: int = 0) -> dict:
@@ -130,8 +145,14 @@ class AutoEncoder(nn.Module):
         audio_in = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).unsqueeze(0).to(device, non_blocking=False)
         return audio_in[:, self.hop_length // 2:-(self.hop_length - self.hop_length // 2)]
 
-    def forward_live(self, x: np.ndarray, hidden: torch.Tensor, delayed: bool = False):
-        """`delayed`: Decoder.forward_live's (the overlap-add noise as a stream, the audio n_noise_filters - 2 samples late)."""
+    def forward_live(self, x: np.ndarray, hidden: torch.Tensor, delayed: bool = False, conditioning=None):
+        """`delayed`: Decoder.forward_live's (the overlap-add noise as a stream, the audio n_noise_filters - 2 samples late).
+        `conditioning`: None, or (target, source) ConditioningStatistics on the module's device -- the block's controls go
+        through fit_conditioning(z, target, source=source), one launch, before the decoder (calibrate `source` once on a few
+        seconds of the player; a source of None would measure each short block by itself)."""
         self.decoder.check_live(delayed, "forward_live")
         z = self.encoder(self.live_window(x))
+        if conditioning is not None:
+            target, source = conditioning
+            z = fit_conditioning(z, target, source=source)
         return self.decoder.forward_live(z, hidden, delayed=delayed)

@@ -503,6 +503,59 @@ int ddsp_pitch_voicing(const float *f0, const float *normalized, const float *pe
                        float lower, float silence, int fill, void *stream);
 
 /*
+ * Conditioning statistics and auto-adjust: the loudness distribution and the mean pitch of the
+ * note-on frames of a set of rows, and the map of one performance's loudness and register onto another's.  Dense [rows, T]
+ * fp32 inputs; `voiced` [rows, T] bytes or NULL.
+ *   on      |loudness| < 2^15 and |cents| < 2^15 (so: both finite) and loudness > silence (-inf: no gate) and
+ *           harmonicity >= confidence and (no voiced or voiced != 0); a NaN compares false
+ *   cell    floorf(fl32(fl32(loudness - lo) * scale)) clamped to [0, bins - 1], scale = fl32(bins) / fl32(hi - lo)
+ *   accum   ddsp_condition_accum_bytes(groups, bins) bytes, 8-byte aligned: uint32 counts [groups, bins], then (at the next
+ *           multiple of 8 bytes) int64 sums [groups, 2] = {sum llrintf(cents 2^24), sum llrintf(loudness 2^24)} over the on
+ *           frames.  groups = rows (pooled = 0: one workgroup per row, plain stores) or 1 (pooled != 0: workgroups take 1024
+ *           frames at a time and merge with integer atomicAdd; the entry point zeroes accum with one hipMemsetAsync first).
+ *           Only integers are accumulated: the result does not depend on the order of arrival.
+ * ddsp_condition_tables, per group with counts c_b, inclusive cumulative counts C_b and N = C_last, for k = 0 .. Q:
+ *   b = the smallest cell with c_b > 0 and Q C_b >= k N;  f = clamp((k N - Q (C_b - c_b)) / (Q c_b), 0, 1) in fp64;
+ *   tables[g, k] = fl32(lo + (b + f) (hi - lo) / bins) in fp64, rounded once;  N = 0: NaN.
+ *   mean_pitch[g] = sum_cents / (N 2^24), mean_loudness[g] likewise (fp64; NaN for N = 0);  frames[g] = N.
+ * ddsp_condition_apply, per row with source tables S (source_groups = 1 or B) and target tables T (target_groups = 1 or B):
+ *   a row whose source_frames < min_frames, or whose S or T holds a NaN, is copied through (octave 0);
+ *   k = octave_mode OFF: 0, FORCED: `octaves`, AUTO: rint((target_mean_pitch - source_mean_pitch) 7180 / 1200) in fp64 (ties to
+ *       even; 0 where that is not finite) clamped to +- max_octaves;
+ *   f0_out = ldexpf(f0, k);  cents_out = cents + fl32(k 1200 / 7180);
+ *   loudness l: not finite: l.  l < S[0]: m = l + (T[0] - S[0]).  l >= S[Q]: m = l + (T[Q] - S[Q]).  Otherwise with j the largest
+ *       index with S[j] <= l (at most Q - 1), d = S[j + 1] - S[j], w = d > 0 ? (l - S[j]) / d : 0.5, m = T[j] + w (T[j + 1] - T[j]).
+ *       loudness_out = l + s (m - l), s = strength_rows[row] (when given) or strength.  All fp32, nothing fused, the division
+ *       correctly rounded.  S is expected non-decreasing.
+ *   octaves_out [B] (int) and frames_out [B] (the row's source_frames) may be NULL.  No output may alias an input.
+ * Launches: stats one (and the memset when pooled), tables one, apply one; no allocation, no host synchronisation.
+ * DDSP_EINVAL: a missing pointer, bins outside 1 .. 8192, quantiles outside 1 .. 1024, hi <= lo (or a cell scale that is not
+ * finite), T <= 0, group counts other than 1 or B, |octaves| or max_octaves beyond 32.  DDSP_ERANGE: rows T >= 2^32, a group of
+ * more than 2^24 frames (with |value| < 2^15 that keeps every fixed-point sum below 2^63), or B ceil(T / 256) > 2^23 in apply.  rows = 0 (groups = 0, B = 0)
+ * returns 0 without a launch.  ddsp_condition_launch_shape: the statistics pass's grid for this shape (workgroups, and the
+ * frames of one unit of work).
+ */
+#define DDSP_CONDITION_MAX_BINS 8192
+#define DDSP_CONDITION_MAX_QUANTILES 1024
+#define DDSP_CONDITION_MAX_OCTAVES 32
+#define DDSP_CONDITION_OCTAVES_OFF 0
+#define DDSP_CONDITION_OCTAVES_AUTO 1
+#define DDSP_CONDITION_OCTAVES_FORCED 2
+size_t ddsp_condition_accum_bytes(long groups, int bins);
+int ddsp_condition_launch_shape(int pooled, long rows, long T, int *blocks, long *unit_frames);
+int ddsp_condition_stats(const float *loudness, const float *cents, const float *harmonicity, const uint8_t *voiced,
+                         void *accum, long rows, long T, int pooled, int bins, float lo, float hi, float silence,
+                         float confidence, void *stream);
+int ddsp_condition_tables(const void *accum, float *tables, double *mean_pitch, double *mean_loudness, long *frames,
+                          long groups, int bins, int quantiles, float lo, float hi, void *stream);
+int ddsp_condition_apply(const float *f0, const float *cents, const float *loudness, const float *source_tables,
+                         const double *source_mean_pitch, const long *source_frames, const float *target_tables,
+                         const double *target_mean_pitch, const float *strength_rows, float *f0_out, float *cents_out,
+                         float *loudness_out, int *octaves_out, long *frames_out, long B, long T, long source_groups,
+                         long target_groups, int quantiles, int octave_mode, int octaves, int max_octaves, float strength,
+                         long min_frames, void *stream);
+
+/*
  * YIN salience on CREPE's bin grid: a second source of the [B, T, 360] array the pitch decoders read.
  * y [B, Lr] fp32 at 16 kHz (what ddsp_resample returns) -> probs [B, T, 360]; frame t of row b is x = y[b, t hop .. t hop + 1024),
  * CREPE's framing without its normalisation.  Per frame, all fp32:
