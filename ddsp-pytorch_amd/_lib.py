@@ -112,6 +112,11 @@ SIGNATURES = {
     "ddsp_condition_stats": (_i32, [_vp] * 5 + [_long, _long, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "ddsp_condition_tables": (_i32, [_vp] * 5 + [_long, _i32, _i32, _f32, _f32, _vp]),
     "ddsp_condition_apply": (_i32, [_vp] * 14 + [_long] * 4 + [_i32] * 4 + [_f32, _long, _vp]),
+    "ddsp_tuning_accum_bytes": (_size, [_long]),
+    "ddsp_tuning_stats": (_i32, [_vp] * 5 + [_long, _long, _i32, _f32, _f32, _vp]),
+    "ddsp_tuning_estimate": (_i32, [_vp] * 5 + [_long, _i32, _i32, _vp]),
+    "ddsp_tuning_workspace_bytes": (_size, [_long, _long]),
+    "ddsp_tuning_apply": (_i32, [_vp] * 13 + [_long, _long, _long, _i32, _i32, _long, _long, _long, _i32, _f32, _f32, _f32, _vp]),
     "ddsp_yin_salience": (_i32, [_vp] * 3 + [_long, _long, _i32, _long, _vp]),
     "ddsp_harm_workspace_bytes": (_size, [_long, _long, _i32]),
     "ddsp_harm_analysis": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),

@@ -37,6 +37,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .conditioning import fit_conditioning
+from .tuning import tune_pitch
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
@@ -58,11 +59,21 @@ class AutoEncoder(nn.Module):
     def transfer(self, x: torch.Tensor, target, **fit_options) -> torch.Tensor:
         """audio [B, L] -> audio: `forward` with the encoder's controls brought into `target`'s range on the way
         (conditioning.fit_conditioning and its options: source, octaves, max_octaves, strength, min_frames).  Without a
-        `source` every clip is measured by itself, over its whole length."""
+        `source` every clip is measured by itself, over its whole length.  One more keyword is taken out of the options:
+        tune=True, or a dict of tuning.tune_pitch's options, moves the fitted controls' notes onto a scale before the decoder
+        (the chain's last step: octave shift, loudness match, auto-tune); tune=None is the path without it."""
+        tune = fit_options.pop('tune', None)
         if fit_options.get('return_info'):
             raise ValueError("transfer returns audio; ask fit_conditioning itself for the info")
+        if tune is not None and tune is not True and tune is not False and not isinstance(tune, dict):
+            raise ValueError(f"transfer: tune must be None, a bool or a dict of tune_pitch options, got {type(tune).__name__}")
+        if isinstance(tune, dict) and tune.get('return_info'):
+            raise ValueError("transfer returns audio; ask tune_pitch itself for the info")
         x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
-        return self.decoder(fit_conditioning(self.encoder(x), target, **fit_options))
+        z = fit_conditioning(self.encoder(x), target, **fit_options)
+        if tune:
+            z = tune_pitch(z, **(tune if isinstance(tune, dict) else {}))
+        return self.decoder(z)
 
     def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,
                 refine: int = 0) -> dict:

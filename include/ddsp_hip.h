@@ -556,6 +556,65 @@ int ddsp_condition_apply(const float *f0, const float *cents, const float *loudn
                          long min_frames, void *stream);
 
 /*
+ * Auto-tune: how a performance is tuned -- its offset from A440 equal temperament and its key --, and
+ * its notes moved onto a scale with vibrato and inflection kept.  Dense [rows, T] fp32 inputs; `voiced` [rows, T] bytes.
+ * All positions are int64 counts of 2^-16 cent on the MIDI scale: note m is m S, S = 100 * 65536; A4 is note 69.
+ *   1. Position of a frame: u = llrint(fl64(fl64(7180 (double)n) + K) 65536), n the frame's normalized_cents,
+ *      K = 1997.3794084376191 - 1200 log2(44) + 6900 = 2346.0614660728625.  The product is exact in fp64: u carries one rounding.
+ *   2. A frame is on iff |n| <= 4 (so: finite, and |u| < 2^31), voiced != 0 (where given), harmonicity >= confidence (where
+ *      harmonicity is given) and loudness > silence (where loudness is given); a NaN compares false.  Off frames are never
+ *      counted, never moved, and end a note.
+ *   3. Statistics (pooled: groups = 1; per row: groups = rows): uint32 H[1200], one-cent pitch-class cells each centred on a whole
+ *      cent, cell = floor_mod(u + 32768, 12 S) div 65536.  Only integers are accumulated: the same bits for any order, grid or
+ *      row permutation.  accum is ddsp_tuning_accum_bytes(groups) = 4800 groups bytes, 8-byte aligned; pooled, the entry point
+ *      zeroes it with one hipMemsetAsync and workgroups merge with integer atomicAdd; per row, plain stores.
+ *   4. Estimate, per group.  Folded histogram D[d] = sum_p H[100 p + d].  Offset: o in -50 .. 49 minimises
+ *      cost(o) = sum_d D[d] min((d - o) mod 100, (o - d) mod 100) (exact int64: the circular median of the deviations from the
+ *      semitone grid); ties go to the smaller |o|, then to the non-negative one.  Pitch-class profile
+ *      P[p] = sum_{j = -50}^{49} H[(100 p + o + j) mod 1200].  Root: with a scale mask (12 bits, bit i = the degree i semitones
+ *      above the root is allowed), root = argmax_r sum_p P[p] bit((p - r) mod 12), ties to the smallest r; forced_root >= 0 is
+ *      that root instead.  An empty group (N = 0) gives offset 0, root 0 (or the forced one), frames 0.  Masks: chromatic 0xFFF,
+ *      major 0xAB5, minor (natural) 0x5AD, pentatonic 0x295; a zero mask is refused.
+ *   5. Snapping, per row, given o, root, mask: v = u - 65536 o; q_t = the allowed note nearest to v_t, ties to the lower note;
+ *      note_t = note_{t-1} if frames t and t - 1 are both on and |v_t - note_{t-1} S| <= |v_t - q_t S| + h, else q_t.  h is
+ *      `hysteresis` in units, 0 .. 1200 * 65536; equality stays on the old note.
+ *   6. A note is a maximal run of on frames with the same note_t, of length L.  With L < min_note_frames its frames get
+ *      correction 0.  Otherwise, with DDSP_TUNING_VIBRATO, every frame of the note gets rdiv(note S L - sum v, L) (the note's
+ *      centre moves onto the pitch, its vibrato and inflection stay); without, frame t gets note S - v_t (the hard snap).
+ *      rdiv(a, b) = floor((2 a + b) / (2 b)).  With DDSP_TUNING_CONCERT the correction of every frame of such a note is
+ *      reduced by 65536 o: it lands on A440's grid instead of the performance's own.
+ *   7. Glide: for an on frame t the smoothed correction is rdiv(sum of the corrections, count) over the frames |u - t| <= glide
+ *      of t's own run of consecutive on frames; glide = 0 gives the correction itself; it never reaches across an off frame.
+ *   8. d_t = llrint((double)amount (double)smoothed_t), amount = amount_rows[row] (when given) or `amount`, clamped to [0, 1]
+ *      (a NaN: 0).  cents_out = n + fl32((double)d / (65536 * 7180)); f0_out = fl32((double)f0 exp2((double)d / (65536 * 1200)));
+ *      frames with d = 0, every off frame included, return n and f0 bit for bit.  notes_out (int, may be NULL) = note_t, or
+ *      INT32_MIN for an off frame; correction_out (int, may be NULL) = d_t.
+ * ddsp_tuning_apply reads offset and root [groups] (groups = 1 or B) from device memory: what ddsp_tuning_estimate wrote, or
+ * hand-made values (an offset is clamped to +-50, a root taken mod 12).  One wavefront per row; a row's intermediates (32 bytes
+ * per frame) stay in LDS while T <= DDSP_TUNING_LDS_FRAMES, longer rows need `workspace` of ddsp_tuning_workspace_bytes(B, T)
+ * bytes (0 while they fit; 8-byte aligned).  No output may alias an input.
+ * Launches: stats one (and the memset when pooled), estimate one, apply one; no allocation, no host synchronisation.
+ * DDSP_EINVAL: a missing pointer, T <= 0, a mask outside 1 .. 0xFFF, a forced root outside -1 .. 11, hysteresis outside
+ * 0 .. 1200 * 65536, a negative min_note_frames or glide, unknown flags, a NaN silence or confidence, an `amount` outside [0, 1]
+ * without amount_rows, group counts other than 1 or B.  DDSP_ERANGE: rows T >= 2^32 or a group of more than 2^24 frames
+ * (statistics); T >= 2^24 or B T >= 2^31 (apply).  rows = 0 (groups = 0, B = 0) returns 0 without a launch.
+ */
+#define DDSP_TUNING_CELLS 1200
+#define DDSP_TUNING_LDS_FRAMES 1536
+#define DDSP_TUNING_VIBRATO 1
+#define DDSP_TUNING_CONCERT 2
+size_t ddsp_tuning_accum_bytes(long groups);
+int ddsp_tuning_stats(const float *cents, const float *harmonicity, const float *loudness, const uint8_t *voiced, void *accum,
+                      long rows, long T, int pooled, float silence, float confidence, void *stream);
+int ddsp_tuning_estimate(const void *accum, int *offset, int *root, long *profile, long *frames, long groups, int mask,
+                         int forced_root, void *stream);
+size_t ddsp_tuning_workspace_bytes(long B, long T);
+int ddsp_tuning_apply(const float *f0, const float *cents, const float *harmonicity, const float *loudness, const uint8_t *voiced,
+                      const int *offset, const int *root, const float *amount_rows, float *f0_out, float *cents_out, int *notes_out,
+                      int *correction_out, void *workspace, long B, long T, long groups, int mask, int forced_root, long hysteresis,
+                      long min_note_frames, long glide, int flags, float amount, float silence, float confidence, void *stream);
+
+/*
  * YIN salience on CREPE's bin grid: a second source of the [B, T, 360] array the pitch decoders read.
  * y [B, Lr] fp32 at 16 kHz (what ddsp_resample returns) -> probs [B, T, 360]; frame t of row b is x = y[b, t hop .. t hop + 1024),
  * CREPE's framing without its normalisation.  Per frame, all fp32:
