@@ -31,6 +31,30 @@ static_assert(kPlanERange == DDSP_ERANGE, "the planner's status is the ABI's");
 
 inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr % 16) == 0; }
 
+// Accuracy of the forward's direct kernels.  A frame's peak is 0.2 % .. 3 % of the sum of the magnitudes that enter it, so a single
+// chain of fp32 multiply-adds over 1 000 bins or taps -- rounding ~ eps sqrt(length) of the partial sums -- reaches the noise
+// contract of 2e-6 of the frame's own peak (tests/test_gpu_noise_forward.py, measured with single chains: frame kernel 2.1e-6 at 1025
+// bands / hop 1024, batched kernel 3.1e-6 at 973 bands).  The chains are therefore cut into blocks of kSumBlock terms whose totals
+// are added up: eps (sqrt(block) + sqrt(length / block)); 6.4e-7 and 3.9e-7 at 1025 bands.  Sums of at most kSumBlock terms are
+// evaluated exactly as before.
+constexpr int kSumBlock = 128;
+
+// ct[m] = cos(2 pi m / S), m in [0, S), an fp64 cosine rounded once to fp32, as the reference's torch.hann_window rounds it.  The
+// window 0.5 - 0.5 cos is ~1e-5 at the edge of a long window, where one fp32 ulp of the cosine is 1 % of it, and cospif is only
+// accurate to an ulp; a frame cropped to a short hop uses nothing but that edge.  One fp64 cosine per four entries: the values at
+// m, S/2 - m, S/2 + m and S - m differ in sign only (S is even; S/2 may be odd).
+template <int Threads>
+__device__ __forceinline__ void fill_cos_table(float *ct, int S, int tid)
+{
+    const int half = S >> 1;
+    for (int m = tid; 2 * m <= half; m += Threads) {
+        const float c = (float)cospi((double)(2 * m) / (double)S);
+        ct[half - m] = -c;
+        ct[m] = c;                                          // (last: 2 m == S/2 is one entry, +0)
+        if (m > 0) { ct[half + m] = -c; ct[S - m] = c; }
+    }
+}
+
 __global__ void __launch_bounds__(256) noise_frame_kernel(NoiseParams p)
 {
     extern __shared__ float smem[];
@@ -43,7 +67,7 @@ __global__ void __launch_bounds__(256) noise_frame_kernel(NoiseParams p)
     const int S = p.S, R = p.R, F = p.F, half = S >> 1;
 
     for (int k = tid; k < F; k += 256) Hs[k] = p.Hm[frame * F + k];
-    for (int m = tid; m < S; m += 256) ct[m] = cospif((float)(2 * m) / (float)S);
+    fill_cos_table<256>(ct, S, tid);
     for (int j = tid; j < R; j += 256) kern[j] = 0.0f;
     if (p.u) {
         for (int m = tid; m < R; m += 256) x[m] = p.u[frame * R + m] * 2.0f - 1.0f;
@@ -66,14 +90,29 @@ __global__ void __launch_bounds__(256) noise_frame_kernel(NoiseParams p)
     for (int src = tid; src < taps; src += 256) {
         const int n = (src + half) % S;  // roll(+S/2): a1[src] = z[(src - S/2) mod S]
         float v = Hs[0] + ((n & 1) ? -Hs[F - 1] : Hs[F - 1]);
-        float acc = 0.0f;
         int idx = 0;
-        for (int k = 1; k < F - 1; ++k) {
-            idx += n;
-            if (idx >= S) idx -= S;
-            acc = __fmaf_rn(Hs[k], ct[idx], acc);
+        if (S > R) {
+            // A cropped frame keeps the taps next to n = S/2, where the cosine sum of an all-positive H cancels to a small part of its
+            // terms and the rounding of an fp32 chain -- relative to the partial sums -- is 2e-6 .. 5e-6 of the frame's peak at hops
+            // 3 and 5 with 26 .. 46 bands (tests/fuzz_parity.py: sweep_noise_forward).  The sum is kept in fp64 there (same table).
+            double acc = 0.0;
+            for (int k = 1; k < F - 1; ++k) {
+                idx += n;
+                if (idx >= S) idx -= S;
+                acc = fma((double)Hs[k], (double)ct[idx], acc);
+            }
+            v = (float)(2.0 * acc + (double)v) * invS;
+        } else {
+            float acc = 0.0f, part = 0.0f;
+            for (int k = 1; k < F - 1; ++k) {
+                idx += n;
+                if (idx >= S) idx -= S;
+                part = __fmaf_rn(Hs[k], ct[idx], part);
+                if ((k & (kSumBlock - 1)) == 0) { acc += part; part = 0.0f; }
+            }
+            acc += part;
+            v = __fmaf_rn(2.0f, acc, v) * invS;
         }
-        v = __fmaf_rn(2.0f, acc, v) * invS;
         const float win = 0.5f - 0.5f * ct[src];   // torch.hann_window(S) (periodic)
         int j = (src - half) % R;                  // roll(-S/2) on the length-R buffer
         if (j < 0) j += R;
@@ -82,8 +121,12 @@ __global__ void __launch_bounds__(256) noise_frame_kernel(NoiseParams p)
     __syncthreads();
 
     for (int n = tid; n < R; n += 256) {
-        float acc = 0.0f;
-        for (int m = 0; m <= n; ++m) acc = __fmaf_rn(x[m], kern[n - m], acc);
+        float acc = 0.0f, part = 0.0f;
+        for (int m = 0; m <= n; ++m) {
+            part = __fmaf_rn(x[m], kern[n - m], part);
+            if ((m & (kSumBlock - 1)) == kSumBlock - 1) { acc += part; part = 0.0f; }
+        }
+        acc += part;
         float *dst = p.y + frame * R + n;
         *dst = p.accumulate ? (*dst + acc) : acc;
     }
@@ -128,7 +171,7 @@ __global__ void __launch_bounds__(kNT) noise_batched_kernel(NoiseParams p)
     // phase 0: a wavefront per frame row (coalesced global read, transposed padded LDS write; no index division)
     for (int f = tid >> 6; f < FB; f += kNT / 64)
         for (int k = tid & 63; k < F; k += 64) Hs[k * HS + f] = (f < nf) ? p.Hm[(frame0 + f) * F + k] : 0.0f;
-    for (int m = tid; m < S; m += kNT) ct[m] = cospif((float)(2 * m) / (float)S);
+    fill_cos_table<kNT>(ct, S, tid);
     if (S < R)                                          // otherwise phase 1 writes every tap
         for (int e = tid; e < FB * KS; e += kNT) kern[e] = 0.0f;
     __syncthreads();
@@ -188,12 +231,17 @@ __global__ void __launch_bounds__(kNT) noise_batched_kernel(NoiseParams p)
         for (int item = tid; item < nmain * (FB / 4); item += kNT) {
             const int fq = item / nmain, n = 1 + item - fq * nmain;  // n fastest: a wavefront's H reads broadcast
             float ev[4] = {0, 0, 0, 0}, ov[4] = {0, 0, 0, 0};
+            float evt[4] = {0, 0, 0, 0}, ovt[4] = {0, 0, 0, 0};      // totals of the finished blocks of kSumBlock bins per parity
             int idx = 0;
             const float *hp = &Hs[HS + 4 * fq];                      // bin k = 1
             int k = 1;
             // eight bins per trip: the eight table reads and the eight H reads (immediate offsets) are in flight together
 #pragma unroll 1
             for (; k + 7 < half; k += 8, hp += 8 * HS) {
+                if (k > 1 && ((k - 1) & (2 * kSumBlock - 1)) == 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { evt[q] += ev[q]; ev[q] = 0.0f; ovt[q] += ov[q]; ov[q] = 0.0f; }
+                }
                 float c[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -219,6 +267,8 @@ __global__ void __launch_bounds__(kNT) noise_batched_kernel(NoiseParams p)
                 if (k & 1) { ov[0] = __fmaf_rn(h.x, c, ov[0]); ov[1] = __fmaf_rn(h.y, c, ov[1]); ov[2] = __fmaf_rn(h.z, c, ov[2]); ov[3] = __fmaf_rn(h.w, c, ov[3]); }
                 else       { ev[0] = __fmaf_rn(h.x, c, ev[0]); ev[1] = __fmaf_rn(h.y, c, ev[1]); ev[2] = __fmaf_rn(h.z, c, ev[2]); ev[3] = __fmaf_rn(h.w, c, ev[3]); }
             }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { ev[q] += evt[q]; ov[q] += ovt[q]; }
             const float4 h0 = *reinterpret_cast<const float4 *>(&Hs[4 * fq]);
             const float4 hn = *reinterpret_cast<const float4 *>(&Hs[half * HS + 4 * fq]);
             const float h0v[4] = {h0.x, h0.y, h0.z, h0.w}, hnv[4] = {hn.x, hn.y, hn.z, hn.w};
@@ -271,10 +321,14 @@ __global__ void __launch_bounds__(kNT) noise_batched_kernel(NoiseParams p)
             const int c = q * LPF + sub;
             if (c >= C) continue;
             const int n0 = c << 3;
-            float acc[8];
+            float acc[8], tot[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) acc[u] = 0.0f;
+            for (int u = 0; u < 8; ++u) acc[u] = tot[u] = 0.0f;
             for (int j = 0; j <= n0; j += 8) {
+                if (j > 0 && (j & (kSumBlock - 1)) == 0) {           // a block of kSumBlock taps is finished
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { tot[u] += acc[u]; acc[u] = 0.0f; }
+                }
                 const float4 ka = *reinterpret_cast<const float4 *>(krow + j);
                 const float4 kb = *reinterpret_cast<const float4 *>(krow + j + 4);
                 const float4 xa = *reinterpret_cast<const float4 *>(xrow + n0 - j - 8);
@@ -289,6 +343,8 @@ __global__ void __launch_bounds__(kNT) noise_batched_kernel(NoiseParams p)
 #pragma unroll
                     for (int u = 0; u < 8; ++u) acc[u] = __fmaf_rn(kv[v], xw[8 + u - v], acc[u]);
             }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc[u] += tot[u];
             if (fr < nf) {
                 float4 lo = make_float4(acc[0], acc[1], acc[2], acc[3]), hi = make_float4(acc[4], acc[5], acc[6], acc[7]);
                 float4 *dst = reinterpret_cast<float4 *>(yrow + n0);

@@ -39,7 +39,7 @@ static_assert(sizeof(bf16x8) * 64 == kIrFragmentBytes, "a fragment is one 16-byt
 // Fragment (nt, parity, kt, term) of the cosine operand, B[i = 32 kt + 8 (lane >> 4) + j][o = 16 nt + (lane & 15)], j = 0..7 in one
 // 16-byte word per lane; i = contraction index, o = output index.  Forward (transpose == 0): i = k' (bin 2 k' + parity), o = tap n;
 // backward: i = tap n, o = k'.  Value c_bin cos(2 pi bin n / S) for bin <= S/2 and n <= S/4, else 0.  cos(2 pi m / S) =
-// cospif(2 m / S): the values of the direct kernels' table (ddsp_noise_fft.hip: ctab).
+// cospif(2 m / S): the values of the FFT form's own cosine-sum table (ddsp_noise_fft.hip: ctab), which this product replaces.
 __global__ void __launch_bounds__(64) noise_ir_table_kernel(bf16x8 *table, int F, int transpose)
 {
     const int nt = blockIdx.x / (2 * KT), par = (blockIdx.x / KT) & 1, kt = blockIdx.x % KT, lane = threadIdx.x;

@@ -6,10 +6,11 @@ random batch / frames / harmonics / hop / sample rate / noise bands, both f0 kin
 counts, the in-kernel draw, and -- in a third of the cases -- loudness / filter levels spread over seven decades from frame to
 frame.  Prints one line per case and a summary; exit code 1 if any case exceeds the tolerances the tests assert, taken LOCALLY:
 audio 1e-5 of the loudness around each sample, noise 2e-6 of each frame's own level (or peak), phases bit-exact.
-usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | gru | encoder | griffinlim | mss]   (`training`: the loss-side kernels against
+usage: fuzz_parity.py [cases] [seed] [training | chunked | backward | noise_backward | noise_forward | gru | encoder | griffinlim | mss]   (`training`: the loss-side kernels against
 fp64 torch instead; `chunked`: the chunked oscillator form with forced tilings and chunk lengths; `backward`: the oscillator's
 backward against the fp64 reference of tests/osc_grad_reference.py; `noise_backward`: the filtered noise's backward against the
-fp64 reference of tests/noise_grad_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
+fp64 reference of tests/noise_grad_reference.py; `noise_forward`: the filtered noise's forward, every kernel form, against the fp64
+reference and yardsticks of tests/noise_fwd_reference.py; `gru`: the GRU recurrence, fp32 and bf16 kernels, step by step against the fp64
 reference of tests/gru_reference.py; `encoder`: the encoder's loudness and resampler kernels against the fp64 references of
 tests/encoder_reference.py; `griffinlim`: Griffin-Lim's synthesis, overlap-add and analysis kernels one at a time through
 ddsp_griffinlim_stage against the fp64 reference and the criteria of tests/griffinlim_reference.py; `mss`: one spectral-loss
@@ -29,6 +30,7 @@ from oracle import oracle  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import osc_grad_reference as R  # noqa: E402
 import noise_grad_reference as R_noise  # noqa: E402
+import noise_fwd_reference as R_nfwd  # noqa: E402
 import gru_reference as R_gru  # noqa: E402
 import encoder_reference as R_enc  # noqa: E402
 import griffinlim_reference as R_gl  # noqa: E402
@@ -508,6 +510,232 @@ def sweep_noise_backward(cases: int, seed: int, verbose: bool = True):
     return bad, worst
 
 
+# ---- the filtered noise's forward (csrc/ddsp_noise.hip: ddsp_noise_forward_ws) against the fp64 reference -----------------------
+# Per sample |y - fp64| <= TOL_SAMPLE x Y[n] (the direct forms: Batched, Frame, Wave), per frame max |err| <= TOL_FRAME x Yframe
+# (every form) and max |err| <= FRAME_REL x the frame's own fp64 peak (exempt: frames with peak < FRAME_FLOOR x Yframe).  The yardsticks
+# and the tolerances are tests/noise_fwd_reference.py's, derived on the host in tests/test_noise_fwd_reference_host.py.
+def noise_fwd_lpf_log(F, hop, mode=0):
+    """pick_lpf_log (csrc/ddsp_noise_plan.h): log2 lanes per frame of the batched forward kernel, -1 when no tile fits in LDS; a
+    mode of (l + 1) << 8 forces l."""
+    if mode >> 8:
+        return (mode >> 8) - 1
+    S = 2 * (F - 1)
+    for limit in (40 * 1024, 80 * 1024, 160 * 1024):
+        for l in range(4):
+            fb = 64 >> l
+            if 4 * (((S + 3) & ~3) + fb * (hop + 4) + max((fb + 4) * F, fb * (hop + 12))) <= limit:
+                return l
+    return -1
+
+
+def noise_ir_product_shape(F, hop):
+    """ir_product_shape (csrc/ddsp_noise_plan.h): the band range the whole-batch matrix product is built for."""
+    S, NQ = 2 * (F - 1), (F - 1) // 2 + 1
+    return hop == 512 and S < hop and 96 < NQ <= 112
+
+
+def noise_fwd_form(B, T, F, hop, mode=0, y_aligned=True, hm_aligned=True, u_given=False, u_aligned=True, workspace=True):
+    """The kernel form ddsp_noise_forward_ws takes: 'FFT' (in-LDS FFT form, cosine sums or the packed inverse FFT), 'FFT+IR' (the
+    impulse responses from the split-bf16 matrix product first), 'WAVE' (wavefront-private form, whole groups of 16 frames),
+    'WAVE+Cl' (... and the remainder in the batched kernel), 'C0'..'C3' (batched direct kernel, log2 lanes per frame), 'D' (one frame
+    per workgroup) -- by the conditions of plan_noise_forward (csrc/ddsp_noise_plan.h); tests/test_noise_plan_host.py holds the two
+    against each other.  `workspace`: a whole 16-byte-aligned workspace of ddsp_noise_workspace_bytes is passed (noise_forward does)."""
+    S, frames = 2 * (F - 1), B * T
+    u_ok = not u_given or u_aligned
+
+    def direct():
+        lpf = noise_fwd_lpf_log(F, hop, mode)
+        return f"C{lpf}" if not mode & 1 and hop % 8 == 0 and lpf >= 0 and y_aligned else "D"
+    if not mode & 3 and 4 <= S <= hop and y_aligned and u_ok and (hop == 512 or (hop == 256 and mode & 4)):
+        product = not mode & 16 and noise_ir_product_shape(F, hop) and frames >= 4096 and workspace
+        return "FFT+IR" if product else "FFT"
+    if not mode & 9 and hop == 128 and F == 65 and y_aligned and hm_aligned and u_ok and frames >= 16:
+        return "WAVE" if frames % 16 == 0 else "WAVE+" + direct()
+    return direct()
+
+
+def noise_forward_run(H, hop, uniform=None, seed=0, offset=0, counter=None, mode=0, misalign=(), base=None):
+    """Two launches of ddsp.noise_forward under ddsp_noise_set_generic(mode), each into an output pre-filled with NaN (a path that
+    writes nothing cannot pass) or, accumulating, with `base` -> (y, repeat) as NumPy.  `misalign`: the names of the arguments ('y',
+    'uniform', 'Hmag') passed as views 4 bytes into their storage."""
+    L = ddsp._lib.lib()
+    B, T, F = H.shape
+
+    def put(a, name):
+        return misaligned(a) if name in misalign else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    Hd = put(H, "Hmag")
+    kw = dict(uniform=put(uniform, "uniform")) if uniform is not None else dict(seed=seed, offset=offset)
+    if counter is not None:
+        kw["counter"] = torch.tensor([counter], dtype=torch.int64, device="cuda")
+    fill = np.full((B, T * hop), np.nan, np.float32) if base is None else np.ascontiguousarray(base, np.float32).reshape(B, T * hop)
+    outs = [put(fill, "y"), put(fill, "y")]
+    try:
+        ddsp._lib.check(L.ddsp_noise_set_generic(mode), "ddsp_noise_set_generic")
+        for out in outs:
+            ddsp.noise_forward(Hd, hop, out=out, accumulate=base is not None, **kw)
+        torch.cuda.synchronize()
+    finally:
+        L.ddsp_noise_set_generic(0)
+    return tuple(o.cpu().numpy().reshape(B, T, hop) for o in outs)
+
+
+def compare_noise_forward(got, y, Y, H, paired=False, base=None):
+    """Device audio [B,T,hop] against the fp64 reference (y, Y) -> dict of the measured figures and the checks the tests assert,
+    with the per-frame arrays under 'per_frame' (sample, frame, rel: [B*T], NaN where not judged).
+    `paired`: the kernel transforms frames 2p and 2p + 1 as one complex sequence (the Fft forms, ddsp_noise_fft.hip), so the partner
+    of a frame with a non-finite H may come out entirely non-finite; never finite and wrong.  `base`: the output's earlier contents
+    (accumulate): the reference is base + y and every bound gains the sum's own rounding, 2^-24 (|base| + |y|) per sample."""
+    B, T, F = H.shape
+    n, hop = B * T, y.shape[-1]
+    got = np.asarray(got, np.float64).reshape(n, hop)
+    y, Y, Hf = y.reshape(n, hop), Y.reshape(n, hop), H.reshape(n, F)
+    bad = ~np.isfinite(Hf).all(axis=1)
+    partner = np.zeros_like(bad)
+    if paired:
+        idx = np.flatnonzero(bad)
+        partner[np.minimum(idx ^ 1, n - 1)] = True              # (an odd last frame is paired with itself)
+        partner &= ~bad
+    lost = partner & ~np.isfinite(got).any(axis=1)              # partners that came out entirely non-finite
+    judged = ~bad & ~lost
+    r = {"frames": n, "bad_frames": int(bad.sum()), "partners_lost": int(lost.sum())}
+    r["nonfinite_ok"] = bool((~np.isfinite(got[bad])).all() and np.isfinite(got[judged]).all())
+    want, extra = y, 0.0
+    if base is not None:
+        b = np.asarray(base, np.float64).reshape(n, hop)
+        with np.errstate(invalid="ignore"):
+            want, extra = b + y, 2.0 ** -24 * (np.abs(b) + np.abs(y))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        err = np.maximum(np.abs(got - want) - extra, 0.0)
+        err[~np.isfinite(got)] = np.inf
+        Yf, peak = Y.max(axis=1), np.abs(y).max(axis=1)
+        sample = np.where(err == 0.0, 0.0, err / Y).max(axis=1)
+        emax = err.max(axis=1)
+        frame = np.where(emax == 0.0, 0.0, emax / Yf)
+        rel = np.where(emax == 0.0, 0.0, emax / peak)
+    keep = judged & ((peak >= R_nfwd.FRAME_FLOOR * Yf) | (emax == 0.0))
+    for a in (sample, frame):
+        a[~judged] = np.nan
+        a[judged & np.isnan(a)] = np.inf
+    rel[~keep] = np.nan
+    rel[keep & np.isnan(rel)] = np.inf
+    worst = lambda a: float(np.nanmax(a)) if np.isfinite(a).any() or np.isinf(a).any() else 0.0      # noqa: E731
+    r.update(ratio_sample=worst(sample), ratio_frame=worst(frame), frame_rel=worst(rel),
+             exempt_frames=int((judged & ~keep).sum()))
+    zero = ~Hf.any(axis=1) & ~partner
+    r["zero_frames"] = int(zero.sum())
+    r["zero_exact"] = bool((got[zero] == (0.0 if base is None else np.asarray(base, np.float64).reshape(n, hop)[zero])).all())
+    r["per_frame"] = dict(sample=sample, frame=frame, rel=rel)
+    return r
+
+
+def noise_forward_meets(r, direct):
+    """The numeric contract as one bool: every form per frame, the direct forms per sample as well."""
+    ok = r["ratio_frame"] <= R_nfwd.TOL_FRAME and (not direct or r["ratio_sample"] <= R_nfwd.TOL_SAMPLE)
+    return bool(ok and r["frame_rel"] <= R_nfwd.FRAME_REL and r["nonfinite_ok"] and r["zero_exact"])
+
+
+def noise_forward_case(H, hop, uniform=None, seed=0, offset=0, counter=None, mode=0, misalign=(), accumulate=None, against_d=True,
+                       same_as=None):
+    """ddsp.noise_forward twice (bit-identical repeat) against noise_fwd_reference.noise_fwd_fp64 of the same draw (the Philox offset
+    includes the counter's value).  accumulate: the output's earlier contents [B, T*hop].  against_d: also the same call under mode 1
+    (the one-frame-per-workgroup kernel), which must meet the same contract and -- when the default took another form -- differ from
+    it bitwise.  same_as: also the same call under that mode; r['same_as'] tells whether the two results are bit-identical.
+    -> dict (+ 'form', 'direct', and 'parts': {family: (ratio_sample, ratio_frame, frame_rel)} -- one family per kernel that ran:
+    the remainder of a 'WAVE+Cl' call is judged as its own family)."""
+    H = np.ascontiguousarray(H, np.float32)
+    B, T, F = H.shape
+    form = noise_fwd_form(B, T, F, hop, mode, y_aligned="y" not in misalign, hm_aligned="Hmag" not in misalign,
+                          u_given=uniform is not None, u_aligned="uniform" not in misalign)
+    direct = not form.startswith("FFT")
+    y, Y = R_nfwd.noise_fwd_fp64(H, hop, uniform=uniform, seed=seed, offset=offset + (counter or 0))
+    got, again = noise_forward_run(H, hop, uniform, seed, offset, counter, mode, misalign, accumulate)
+    r = compare_noise_forward(got, y, Y, H, paired=not direct, base=accumulate)
+    r.update(form=form, direct=direct, F=F, repeat_same=bool(np.array_equal(bits(got), bits(again))))
+    pf = r.pop("per_frame")
+
+    def part(sl):
+        w = lambda a: float(np.nanmax(a[sl])) if (~np.isnan(a[sl])).any() else 0.0      # noqa: E731
+        return (w(pf["sample"]) if direct else 0.0, w(pf["frame"]), w(pf["rel"]))
+    if form.startswith("WAVE+"):
+        done = (B * T) - (B * T) % 16
+        r["parts"] = {"WAVE": part(slice(0, done)), form: part(slice(done, None))}
+    else:
+        r["parts"] = {form: part(slice(None))}
+    r["ok"] = noise_forward_meets(r, direct)
+    if same_as is not None:
+        other, _ = noise_forward_run(H, hop, uniform, seed, offset, counter, same_as, misalign, accumulate)
+        r["same_as"] = bool(np.array_equal(bits(got), bits(other)))
+    if against_d and form != "D":
+        d, _ = noise_forward_run(H, hop, uniform, seed, offset, counter, 1, misalign, accumulate)
+        rd = compare_noise_forward(d, y, Y, H, base=accumulate)
+        rd.pop("per_frame")
+        r["differs_from_d"] = not np.array_equal(bits(got), bits(d))
+        r["d_ok"] = noise_forward_meets(rd, True)
+        r["d_ratio"] = rd["ratio_sample"]
+        r["d_figures"] = {k: rd[k] for k in ("ratio_sample", "ratio_frame", "frame_rel", "nonfinite_ok", "zero_exact")}
+    return r
+
+
+def noise_forward_ok(r):
+    """The assertions every noise forward case makes, as one bool (the tests assert the fields one by one)."""
+    return bool(r["ok"] and r["repeat_same"] and r.get("d_ok", True) and r.get("differs_from_d", True))
+
+
+def sweep_noise_forward(cases: int, seed: int, verbose: bool = True):
+    """Random shapes of the noise forward against the fp64 reference: the backward sweep's pool of shapes (odd hops, multiples of 8,
+    256, 512; the matrix-product band range below its 4 096 frames, which 1.5 M samples leave no room for), hop 128 / 65 bands at 1 .. 200 frames (the wavefront form and its
+    remainder) and the FFT form at hop 256 (mode 4); H at frame levels over seven decades, a zero frame in some; the injected draw or
+    the in-kernel one at 64-bit offsets (a device counter in some); modes 0 / 1 / 2 / 4 / 8 / 16 / forced lane counts.  B*T*hop <= 1.5 M
+    per case.  -> (failed, {form: worst error / yardstick: Y[n] for the direct forms, Yframe for the Fft forms})"""
+    rng = np.random.default_rng(seed)
+    worst = {}
+    bad = 0
+    for i in range(cases):
+        kind = rng.random()
+        mode = int(rng.choice([0, 0, 0, 1, 2, 8, 16]))
+        if kind < 0.04:                                              # the matrix-product form's band range just below its 4 096 frames (1.5 M samples): declined
+            hop, F, n = 512, int(rng.integers(193, 225)), int(rng.integers(2900, 2930))
+        elif kind < 0.2:
+            hop, F = 512, int(rng.choice([257, 195, 129, 256, 3, int(rng.integers(2, 400))]))
+            n = int(rng.integers(1, 60))
+        elif kind < 0.4:
+            hop, F, n = 128, 65, int(rng.integers(1, 201))
+        elif kind < 0.5:
+            hop, F, n, mode = 256, int(rng.integers(3, 130)), int(rng.integers(1, 60)), 4
+        else:
+            hop = int(rng.choice([1, 3, 5, 7, 12, 100, 441, 8, 16, 40, 64, 128, 160, 256, 480, 1024]))
+            F = int(rng.integers(2, min(1100, 2 * hop + 40) + 1))
+            n = int(rng.integers(1, max(2, min(200, 1_500_000 // hop))))
+            if rng.random() < 0.3 and hop % 8 == 0:
+                l = int(rng.integers(0, 4))
+                fb = 64 >> l
+                if 4 * (((2 * F + 1) & ~3) + fb * (hop + 4) + max((fb + 4) * F, fb * (hop + 12))) <= 160 * 1024:
+                    mode = (l + 1) << 8                              # a forced lane count whose tile fits in LDS
+        B = int(rng.choice([d for d in (1, 2, 3, 4) if n % d == 0])) if n > 3 else 1
+        T = n // B
+        H = syn.controller_range(rng.standard_normal((B, T, F), dtype=np.float32)) * frame_levels(rng, B, T, rng.random() < 0.7)
+        if n > 1 and rng.random() < 0.3:
+            H[rng.integers(0, B), rng.integers(0, T)] = 0.0           # a silent frame: exact zeros
+        kw = {}
+        if rng.random() < 0.5:
+            kw["uniform"] = rng.random((B, T, hop), dtype=np.float32)
+        else:
+            kw["seed"], kw["offset"] = int(rng.integers(1 << 62)), int(rng.integers(1 << 62))
+            if rng.random() < 0.3:
+                kw["counter"] = int(rng.integers(1 << 40))
+        r = noise_forward_case(H, hop, mode=mode, against_d=False, **kw)
+        okay = noise_forward_ok(r)
+        bad += not okay
+        for fam, (rs, rf, _) in r["parts"].items():
+            worst[fam] = max(worst.get(fam, 0.0), rs if r["direct"] else rf)
+        if verbose or not okay:
+            print(f"{'ok ' if okay else 'BAD'} noise forward B{B} T{T} F{F} hop{hop} mode {mode} form {r['form']} "
+                  f"{'injected' if 'uniform' in kw else 'philox'}: {r['ratio_sample']:.1e} of Y[n], {r['ratio_frame']:.1e} of Yframe, "
+                  f"{r['frame_rel']:.1e} of the peak{'' if r['nonfinite_ok'] else ' NON-FINITE'}"
+                  f"{'' if r['zero_exact'] else ' ZERO FRAME NONZERO'}{'' if r['repeat_same'] else ' REPEAT DIFFERS'}", flush=True)
+    return bad, worst
+
+
 # ---- the GRU recurrence (csrc/ddsp_gru.hip) step by step against the fp64 reference of tests/gru_reference.py -------------------
 def gru_case(B, T, Hd, lowp, seed, h0=True, bias=True, dhT=True, io16=None, spread=False, keep=False):
     """One forward (saving and not saving) and one backward of the raw launchers on the inputs of gru_reference.make_inputs, against
@@ -786,6 +1014,11 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] == "noise_backward":
         bad, worst = sweep_noise_backward(cases, seed, verbose=False)
         print(f"noise backward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per form: "
+              + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
+        sys.exit(1 if bad else 0)
+    if len(sys.argv) > 3 and sys.argv[3] == "noise_forward":
+        bad, worst = sweep_noise_forward(cases, seed, verbose=False)
+        print(f"noise forward: cases {cases}, seed {seed}, failed {bad}; worst error / yardstick per form: "
               + ", ".join(f"{k} {v:.1e}" for k, v in sorted(worst.items())))
         sys.exit(1 if bad else 0)
     if len(sys.argv) > 3 and sys.argv[3] == "gru":

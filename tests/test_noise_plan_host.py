@@ -3,7 +3,8 @@ ddsp_noise_backward_ws take for a shape, a mode of ddsp_noise_set_generic and wh
 
 The plan header is plain C++; the test compiles tests/noise_plan_dump.cpp against it and reads the plans as text.  The backward's
 plans are held against fuzz_parity.noise_bwd_form, the Python statement of the same dispatch that the form assertions of
-test_gpu_noise_backward.py rest on; the forward's against expectations written out here."""
+test_gpu_noise_backward.py rest on; the forward's against expectations written out here and against fuzz_parity.noise_fwd_form, on
+which the form assertions of test_gpu_noise_forward.py rest."""
 import os
 import shutil
 import subprocess
@@ -140,6 +141,44 @@ def test_forward_plans(dump):
         assert (lds > 0) == direct, (c[:7], lds)
         if p["status"] == 0:
             assert lds <= 160 * 1024 or (c[4] >> 8), (c[:7], lds)
+
+
+def fwd_name(p):
+    if p["form"] == "Fft":
+        return "FFT+IR" if p["ir"] else "FFT"
+    assert p["ir"] == 0
+    direct = {"Batched": f"C{p['lpf']}", "Frame": "D"}
+    if p["form"] == "Wave":
+        assert p["wave"] > 0 and p["wave"] % 16 == 0
+        return "WAVE" if p["rest"] == "None" else "WAVE+" + direct[p["rest"]]
+    assert p["wave"] == 0 and p["rest"] == "None"
+    return direct[p["form"]]
+
+
+def mirror(B, T, F, hop, mode, facts, ws):
+    return fz.noise_fwd_form(B, T, F, hop, mode=mode, y_aligned=facts[0] == "1", hm_aligned=facts[1] == "1", u_given=facts[2] == "1",
+                             u_aligned=facts[3] == "1", workspace=ws == "0" and facts[4] == "1")
+
+
+FWD_MODES = (0, 1, 2, 4, 8, 16) + tuple((l + 1) << 8 for l in range(4))
+FWD_FACTS = (ALIGNED, Y_MISALIGNED, "10001", U_ALIGNED, U_MISALIGNED, "11000")
+
+
+def test_forward_plan_is_what_the_python_mirror_says(dump):
+    """The backward's grid (shapes x frame counts x modes x pointer facts; the frame counts straddle the group of 16 and the
+    product's 4 096), with and without a workspace, and every written-out case above."""
+    cases = [(1, T, F, hop, mode, facts, ws) for F, hop in BWD_SHAPES for T in (15, 16, 511, 4095, 4096, 4100) for mode in FWD_MODES
+             for facts in FWD_FACTS for ws in ("0", "none")]
+    cases += [c[:7] for c in FWD_CASES]
+    seen = set()
+    for c, p in zip(cases, dump([("f",) + c for c in cases])):
+        got = fwd_name(p)
+        assert got == mirror(*c), (c, p)
+        if p["form"] == "Batched" or p["rest"] == "Batched":
+            assert p["lpf"] == fz.noise_fwd_lpf_log(c[2], c[3], c[4]), (c, p)
+        assert p["status"] == 0 or got == "D"
+        seen.add(got)
+    assert seen == {"FFT", "FFT+IR", "WAVE", "D"} | {f"C{l}" for l in range(4)} | {f"WAVE+C{l}" for l in range(4)}, seen
 
 
 # ---- workspace size -----------------------------------------------------------------------------------------------------
