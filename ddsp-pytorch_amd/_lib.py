@@ -141,6 +141,8 @@ SIGNATURES = {
     "ddsp_wfft_probe_sizes": (_i32, [_i32, _long, ctypes.POINTER(_long), ctypes.POINTER(_long)]),
     "ddsp_wfft_probe": (_i32, [_i32, _vp, _vp, _long, _vp]),
     "ddsp_griffinlim_stage": (_i32, [_i32] + [_vp] * 8 + [_long, _long, _i32, _i32, _long, _f32, _vp]),
+    "ddsp_notes_extract": (_i32, [_vp] * 12 + [_long, _long, _long, _long, _i32, _i32, _long, _long, _i32, _f32, _f32, _vp]),
+    "ddsp_notes_render": (_i32, [_vp] * 14 + [_long, _long, _long, _long, _i32] + [_long] * 6 + [_f64, _f64, _f32, _f32, _vp]),
     "ddsp_gather_batch": (_i32, [_vp, _vp, ctypes.POINTER(_long), _i32, _vp, _vp, _long, _long, _i32, _i32, _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)

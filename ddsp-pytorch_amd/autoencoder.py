@@ -18,6 +18,10 @@
                              forward with conditioning.fit_conditioning between encoder and decoder: the clip's register moved by
                              whole octaves towards, and its loudness quantile-mapped onto, `target` (the ConditioningStatistics of
                              the decoder's training set)
+  transcribe(x, **extract_options)
+                             the encoder followed by notes.extract_notes: the clip's note events (notes.Notes)
+  play(notes, frames=None, target=None, **render_options)
+                             notes.render_notes, fit_conditioning where a target is given, the decoder: a score -> audio
   forward_live(x, hidden, delayed=False, conditioning=None)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -38,6 +42,7 @@ import torch.nn.functional as F
 
 from .conditioning import fit_conditioning
 from .tuning import tune_pitch
+from .notes import extract_notes, render_notes
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
@@ -73,6 +78,29 @@ class AutoEncoder(nn.Module):
         z = fit_conditioning(self.encoder(x), target, **fit_options)
         if tune:
             z = tune_pitch(z, **(tune if isinstance(tune, dict) else {}))
+        return self.decoder(z)
+
+    def transcribe(self, x: torch.Tensor, **extract_options):
+        """audio [B, L] -> notes.Notes: the encoder (on the clip padded as forward() pads it) followed by notes.extract_notes
+        and its options (tuning, scale, root, hysteresis, min_note_frames, max_notes)."""
+        with torch.no_grad():
+            z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
+        return extract_notes(z, **extract_options)
+
+    def play(self, notes, frames=None, target=None, **render_options) -> torch.Tensor:
+        """notes.Notes -> audio [B, frames hop]: notes.render_notes (and its options) at the decoder's sample rate and hop, then
+        `fit_conditioning(z, target)` where a ConditioningStatistics `target` is given (the decoder's training set: the score's
+        register and levels brought into its range), then the decoder's ordinary forward.  frames=None takes the end of the last
+        note (that reads the notes back from the device)."""
+        if render_options.get('return_info'):
+            raise ValueError("play returns audio; ask render_notes itself for the info")
+        if frames is None:
+            used = notes._used()
+            ends = torch.where(used, notes.onset.to(torch.int64) + notes.frames, torch.zeros_like(notes.onset, dtype=torch.int64))
+            frames = max(int(ends.max()) if ends.numel() else 0, 1)
+        z = render_notes(notes, frames, self.decoder.harmonics.sample_rate, self.hop_length, **render_options)
+        if target is not None:
+            z = fit_conditioning(z, target)
         return self.decoder(z)
 
     def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,

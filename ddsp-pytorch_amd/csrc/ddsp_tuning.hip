@@ -10,7 +10,8 @@
 //   tuning_apply_kernel     one wavefront per row, four sweeps over tiles of 64 frames, the row's intermediates (32 bytes per
 //                           frame) in LDS, or in the caller's workspace for rows beyond kLdsFrames:
 //                             1  position, nearest allowed note, the note recurrence (a ballot finds the first lane that leaves
-//                                the running note: one iteration per note change, not per frame), an int64 prefix sum of the
+//                                the running note: one iteration per note change, not per frame; these three live in
+//                                ddsp_tuning_common.h, which the note kernels of ddsp_notes.hip share), an int64 prefix sum of the
 //                                positions, max-scans for the frame a note and a run of on frames began at
 //                             2  a note's last frame forms its length, its sum and its correction, and leaves it at the note's
 //                                first frame; a run's last frame leaves its index at the run's first frame
@@ -25,8 +26,11 @@
 
 #include "ddsp_hip.h"
 #include "ddsp_internal.h"
+#include "ddsp_tuning_common.h"
 
 namespace {
+
+using namespace ddsp_tuning;
 
 constexpr int kThreads = 256;
 constexpr int kCells = DDSP_TUNING_CELLS;
@@ -36,41 +40,6 @@ constexpr int kMaxBlocks = 2048;                // rows in flight (statistics pe
 constexpr int kPooledBlocks = 512;              // workgroups that merge into one pooled histogram
 constexpr long kChunk = 1024;                   // frames of one pooled unit
 constexpr long kMaxGroupFrames = 1l << 24;      // frames of one statistic
-constexpr long kMaxRowFrames = 1l << 24;        // apply: T below it keeps 2 |note S L| and every prefix sum far below 2^63
-constexpr long long kSemitone = 100ll * 65536;
-constexpr int kOctave = 12 * 100 * 65536;
-constexpr long long kMaxHysteresis = 1200ll * 65536;
-constexpr double kOrigin = 2346.0614660728625;  // 1997.3794084376191 - 1200 log2(44) + 6900
-constexpr int kOff = INT_MIN;
-
-__device__ __forceinline__ bool frame_on(float n, const float *harm, const float *loud, const uint8_t *voiced, long i, float silence,
-                                         float confidence)
-{
-    bool on = fabsf(n) <= 4.0f;                 // (a NaN fails every comparison)
-    if (harm) on = on && harm[i] >= confidence;
-    if (loud) on = on && loud[i] > silence;
-    if (voiced) on = on && voiced[i] != 0;
-    return on;
-}
-
-// |n| <= 4: |7180 n + K| < 31067 cents, the position's magnitude below 2^31.  The product is exact, the sum rounds once.
-__device__ __forceinline__ int position(float n) { return (int)llrint((7180.0 * (double)n + kOrigin) * 65536.0); }
-
-__device__ __forceinline__ int floor_mod(int a, int b)
-{
-    const int m = a % b;
-    return m < 0 ? m + b : m;
-}
-
-__device__ __forceinline__ long long floor_div(long long a, long long b)     // b > 0
-{
-    const long long q = a / b;
-    return (a % b) < 0 ? q - 1 : q;
-}
-
-__device__ __forceinline__ long long rdiv(long long a, long long b) { return floor_div(2 * a + b, 2 * b); }
-
-__device__ __forceinline__ long long magnitude(long long a) { return a < 0 ? -a : a; }
 
 __global__ void __launch_bounds__(kThreads) tuning_stats_kernel(const float *__restrict__ cents, const float *__restrict__ harm,
                                                                 const float *__restrict__ loud, const uint8_t *__restrict__ voiced,
@@ -183,27 +152,6 @@ __global__ void __launch_bounds__(64) tuning_estimate_kernel(const uint32_t *__r
     }
 }
 
-template <typename V>
-__device__ __forceinline__ V scan_sum(V v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const V up = __shfl_up(v, o);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int scan_max(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(v, o);
-        if (lane >= o && up > v) v = up;
-    }
-    return v;
-}
-
 template <bool kLds>
 __global__ void __launch_bounds__(64)
 tuning_apply_kernel(const float *__restrict__ f0, const float *__restrict__ cents, const float *__restrict__ harm,
@@ -227,19 +175,11 @@ tuning_apply_kernel(const float *__restrict__ f0, const float *__restrict__ cent
     int *run_last = note_corr + T;              // at a run's first frame: its last frame
 
     const long g = per_row ? row : 0;
-    int o = offset[g];
-    o = o < -50 ? -50 : (o > 50 ? 50 : o);      // (an estimate lies in -50 .. 49; a hand-made one is kept inside the arithmetic's range)
+    const int o = clamp_offset(offset[g]);
     const int rt = forced_root >= 0 ? forced_root : floor_mod(root[g], 12);
     const long long shift = 65536ll * o, conc = flags & DDSP_TUNING_CONCERT ? shift : 0;
     const bool vibrato = flags & DDSP_TUNING_VIBRATO;
-    if (lane < 12) {
-        int k = 0;
-        while (k < 11 && !((mask >> floor_mod(lane - k, 12)) & 1)) ++k;       // (mask != 0: one of twelve is allowed)
-        step_down[lane] = k;
-        k = 0;
-        while (k < 11 && !((mask >> floor_mod(lane + 1 + k, 12)) & 1)) ++k;
-        step_up[lane] = k;
-    }
+    fill_steps(step_down, step_up, mask, lane);
     __syncthreads();
     const long base = row * (long)T;
     const float *nrow = cents + base;
@@ -254,32 +194,12 @@ tuning_apply_kernel(const float *__restrict__ f0, const float *__restrict__ cent
         const bool on = in && frame_on(n, harm, loud, voiced, base + t, silence, confidence);
         const int u = on ? position(n) : kOff;
         const long long v = on ? (long long)u - shift : 0;
-        int q = 0;
-        if (on) {
-            const int c = (int)floor_div(v, kSemitone), rel = floor_mod(c - rt, 12);
-            const int lo = c - step_down[rel], hi = c + 1 + step_up[rel];
-            q = v - lo * kSemitone <= hi * kSemitone - v ? lo : hi;            // ties to the lower note
-        }
+        const int q = on ? nearest_allowed(v, rt, step_down, step_up) : 0;
         int before_on = __shfl_up((int)on, 1);
         if (lane == 0) before_on = prev_on;
         const bool fresh = on && !before_on;                                    // a run of on frames begins
-        const long long reach = on ? magnitude(v - q * kSemitone) + hysteresis : 0;
         const int before_note = prev_on ? cur : kOff;                           // the note of frame t0 - 1
-        int note = kOff, from = 0;
-        for (;;) {                                                              // one turn per note change inside the tile
-            const bool leaves = on && lane >= from && (fresh || magnitude(v - cur * kSemitone) > reach);
-            const unsigned long long m = __ballot(leaves);
-            if (!m) {
-                if (on && lane >= from) note = cur;
-                break;
-            }
-            const int first = __ffsll((long long)m) - 1;
-            if (on && lane >= from && lane < first) note = cur;
-            cur = __shfl(q, first);
-            if (lane == first) note = cur;
-            from = first + 1;
-            if (from >= 64) break;
-        }
+        const int note = tile_notes(on, fresh, v, q, hysteresis, cur, lane);
         int pn = __shfl_up(note, 1);
         if (lane == 0) pn = before_note;
         int nf = scan_max(on && pn != note ? t : -1, lane);

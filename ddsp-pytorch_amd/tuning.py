@@ -190,6 +190,37 @@ def _estimate_host(H, mask, forced_root):
     return offset.astype(np.int32), root.astype(np.int32), profile.astype(np.int64), H.sum(axis=1).astype(np.int64)
 
 
+def _row_notes_host(n, on, o, root, mask, h):
+    """One row with an on frame -> (v, notes, starts, ends): the positions relative to the row's own grid (0 where off), note_t
+    (OFF where off), and the first and last frame of every note (notes.py reads the same four)"""
+    T = n.shape[0]
+    notes = np.full(T, OFF, dtype=np.int64)
+    v = np.where(on, _positions_host(n, on) - 65536 * o, 0)
+    c = v // SEMITONE
+    rel = (c - root) % 12
+    down = np.array([next(k for k in range(12) if (mask >> ((r - k) % 12)) & 1) for r in range(12)], dtype=np.int64)
+    up = np.array([next(k for k in range(12) if (mask >> ((r + 1 + k) % 12)) & 1) for r in range(12)], dtype=np.int64)
+    lo, hi = c - down[rel], c + 1 + up[rel]
+    q = np.where(v - lo * SEMITONE <= hi * SEMITONE - v, lo, hi)
+    before = np.concatenate([[False], on[:-1]])
+    fresh = on & ~before
+    reach = np.abs(v - q * SEMITONE) + h
+    at, cur = 0, 0
+    while at < T:                                                       # one turn per note change, as the kernel's ballot
+        leaves = on[at:] & (fresh[at:] | (np.abs(v[at:] - cur * SEMITONE) > reach[at:]))
+        if not leaves.any():
+            notes[at:][on[at:]] = cur
+            break
+        first = at + int(np.argmax(leaves))
+        notes[at:first][on[at:first]] = cur
+        cur = int(q[first])
+        notes[first] = cur
+        at = first + 1
+    starts = np.flatnonzero(on & (np.concatenate([[OFF], notes[:-1]]) != notes))
+    ends = np.flatnonzero(on & (np.concatenate([notes[1:], [OFF]]) != notes))
+    return v, notes, starts, ends
+
+
 def _snap_row_host(n, f0, on, o, root, mask, h, min_note, glide, vibrato, concert, amount):
     T = n.shape[0]
     o = int(min(max(o, -50), 50))
@@ -199,30 +230,10 @@ def _snap_row_host(n, f0, on, o, root, mask, h, min_note, glide, vibrato, concer
     notes, d = np.full(T, OFF, dtype=np.int64), np.zeros(T, dtype=np.int64)
     out_n, out_f = n.copy(), f0.copy()
     if on.any():
-        v = np.where(on, _positions_host(n, on) - shift, 0)
-        c = v // SEMITONE
-        rel = (c - root) % 12
-        down = np.array([next(k for k in range(12) if (mask >> ((r - k) % 12)) & 1) for r in range(12)], dtype=np.int64)
-        up = np.array([next(k for k in range(12) if (mask >> ((r + 1 + k) % 12)) & 1) for r in range(12)], dtype=np.int64)
-        lo, hi = c - down[rel], c + 1 + up[rel]
-        q = np.where(v - lo * SEMITONE <= hi * SEMITONE - v, lo, hi)
+        v, notes, starts, ends = _row_notes_host(n, on, o, root, mask, h)
         before = np.concatenate([[False], on[:-1]])
         after = np.concatenate([on[1:], [False]])
         fresh = on & ~before
-        reach = np.abs(v - q * SEMITONE) + h
-        at, cur = 0, 0
-        while at < T:                                                       # one turn per note change, as the kernel's ballot
-            leaves = on[at:] & (fresh[at:] | (np.abs(v[at:] - cur * SEMITONE) > reach[at:]))
-            if not leaves.any():
-                notes[at:][on[at:]] = cur
-                break
-            first = at + int(np.argmax(leaves))
-            notes[at:first][on[at:first]] = cur
-            cur = int(q[first])
-            notes[first] = cur
-            at = first + 1
-        starts = np.flatnonzero(on & (np.concatenate([[OFF], notes[:-1]]) != notes))
-        ends = np.flatnonzero(on & (np.concatenate([notes[1:], [OFF]]) != notes))
         L = ends - starts + 1
         prefix = np.cumsum(v)
         total = prefix[ends] - prefix[starts] + v[starts]

@@ -954,6 +954,67 @@ int ddsp_griffinlim_stage(int stage, const float *S, const float *ang0, const fl
                           void *stream);
 
 /*
+ * Notes: the note events of a pitch track, and note events rendered back to frame-rate controls, in the
+ * integer conventions of the auto-tune above: a position is an int64 count of 2^-16 cent on the MIDI scale, S = 100 * 65536, K the
+ * literal of step 1 there, rdiv(a, b) = floor((2 a + b) / (2 b)).
+ *
+ * ddsp_notes_extract, per row (inputs as ddsp_tuning_apply's; `loudness` gates a frame only with gate_loudness = 1):
+ *   1. u_t, "on", v_t = u_t - 65536 o and note_t are steps 1, 2 and 5 of the auto-tune.
+ *   2. A note is a maximal run of on frames with one note_t; its first frame is `onset`, its length L.
+ *   3. Notes with L < min_note_frames are dropped: not reported, their frames belong to no note.
+ *   4. A kept note's record: onset, frames = L, pitch = note_t, detune = -rdiv(pitch S L - sum v, L) (units above the pitch on the
+ *      performance's own grid: exactly minus the correction the auto-tune gives the note with DDSP_TUNING_VIBRATO alone, amount 1,
+ *      glide 0 -- the mean of v - pitch S rounded to the nearest unit, a tie going down, where rdiv(sum v - pitch S L, L) would
+ *      send it up and differ from that correction by one unit), all int32; level fp32 = the largest loudness over the note's frames that is not a NaN (+0 above -0), the canonical NaN
+ *      (0x7FC00000) where there is none or loudness is NULL.  A maximum: the same bits in any order.
+ *   5. Records are written in order of onset into [B, N] arrays.  count[b] = the kept notes of the row, those beyond N included:
+ *      overflow shows as count > N, and nothing is written past N.
+ *   6. Slots from min(count, N) on are filled: onset -1, frames 0, pitch INT32_MIN, detune 0, level NaN.
+ *   One wavefront per row, no per-frame storage, no atomics; one launch, no allocation, no host synchronisation.
+ *
+ * ddsp_notes_render: the five record arrays [B, N], count [B], offset [groups] -> f0, cents (normalized_cents), loudness,
+ * harmonicity fp32 [B, T], voiced bytes [B, T], and where not NULL position int64 [B, T] and owner int32 [B, T].
+ *   1. n = min(count, N) (a negative count is 0).  Onsets are expected non-decreasing over i < n; anything else gives
+ *      unspecified values, never an access out of bounds.
+ *   2. Note i is valid iff frames_i >= 1 and 0 <= pitch_i <= 127 and |detune_i| <= 2^30.
+ *   3. i*(t) = the largest i < n with onset_i <= t: a later note cuts an earlier one off (monophonic).
+ *   4. Frame t is on, and owner = i*, iff i* exists, is valid and t < onset_i* + frames_i*; otherwise owner = -1.
+ *   5. b_i = pitch_i S + (DDSP_NOTES_KEEP_DETUNE ? detune_i : 0) + (DDSP_NOTES_CONCERT ? 0 : 65536 o) + transpose (units;
+ *      o clamped to +-50 as in the auto-tune).
+ *   6. L'_i = min(frames_i, onset_{i+1} - onset_i); for the last note L'_i = frames_i.
+ *   7. On frames, k = t - onset_i: p = b_i + glide_term + vib_term.
+ *      glide_term = rdiv((b_{i-1} - b_i) (G - k), G + 1) when G = glide > 0, k < G, note i - 1 exists and is valid and
+ *      onset_i <= onset_{i-1} + frames_{i-1} (legato); else 0.
+ *      vib_term = llrint(vibrato_depth min(1, (k - delay + 1) / ramp) sin(vibrato_omega (k - delay))) in fp64 (depth in units,
+ *      omega in radians per frame), when vibrato_depth > 0 and k >= delay; else 0.
+ *   8. Off frames hold a pitch: p = b_i* where i* exists and is valid, b_0 before the first onset where note 0 is valid, else
+ *      6900 * 65536.
+ *   9. cents = fl32((p / 65536 - K) / 7180), f0 = fl32(440 exp2((p / 65536 - 6900) / 1200)), both formed in fp64.
+ *  10. On frames loudness = fl32(floor + (lv - floor) ga gr) in fp64: lv = level_i, or default_level where that is a NaN;
+ *      ga = min(1, (k + 1) / attack) where attack > 0, else 1; gr = min(1, (L'_i - k) / release) where release > 0, else 1.
+ *      Off frames: loudness = floor.  harmonicity is 1 on and 0 off, voiced the on flag.
+ *   One thread per output frame, no atomics; one launch, no allocation, no host synchronisation.
+ *
+ * Both: DDSP_EINVAL: a missing pointer (the record arrays may be NULL only with N = 0), T <= 0, N < 0, group counts other than 1
+ * or B; extract: a mask outside 1 .. 0xFFF, a forced root outside -1 .. 11, hysteresis outside 0 .. 1200 * 65536, a negative
+ * min_note_frames, a NaN silence or confidence, gate_loudness outside 0 .. 1 or set without loudness; render: unknown flags,
+ * |transpose| > 128 S, glide, attack, release, delay or ramp outside 0 .. 2^24 - 1, ramp < 1, a depth outside 0 .. 128 S, a NaN
+ * or |omega| > 10^6, a floor or default level that is not finite.  DDSP_ERANGE: T >= 2^24, B T >= 2^31 or B N >= 2^31.
+ * Nothing is launched before these checks; B = 0 returns 0 without a launch.  No output may alias an input.
+ */
+#define DDSP_NOTES_KEEP_DETUNE 1
+#define DDSP_NOTES_CONCERT 2
+int ddsp_notes_extract(const float *cents, const float *harmonicity, const float *loudness, const uint8_t *voiced, const int *offset,
+                       const int *root, int *onset, int *frames, int *pitch, int *detune, float *level, int *count, long B, long T,
+                       long N, long groups, int mask, int forced_root, long hysteresis, long min_note_frames, int gate_loudness,
+                       float silence, float confidence, void *stream);
+int ddsp_notes_render(const int *onset, const int *frames, const int *pitch, const int *detune, const float *level, const int *count,
+                      const int *offset, float *f0, float *cents, float *loudness, float *harmonicity, uint8_t *voiced,
+                      long *position, int *owner, long B, long T, long N, long groups, int flags, long transpose, long glide,
+                      long attack, long release, long vibrato_delay, long vibrato_ramp, double vibrato_depth, double vibrato_omega,
+                      float floor_level, float default_level, void *stream);
+
+/*
  * The trainer's batch fetch from a device-resident training set (train/train.py:48: DataLoader(shuffle=True), collate, copy).
  *
  * ddsp_gather_batch  for each of n_arrays (<= DDSP_GATHER_MAX_ARRAYS) fp32 arrays: dst[a] [rows, row_floats[a]] row r <-
