@@ -22,7 +22,7 @@ from .conditioning import ConditioningStatistics, conditioning_statistics, fit_c
 from . import tuning  # noqa: F401
 from .tuning import TuningStatistics, tuning_statistics, tune_pitch  # noqa: F401
 from . import notes  # noqa: F401
-from .notes import Notes, extract_notes, render_notes  # noqa: F401
+from .notes import Expression, Notes, extract_notes, note_expression, render_notes  # noqa: F401
 from . import analysis  # noqa: F401
 from .analysis import HarmonicAnalyzer, harmonic_analysis, harmonic_resynthesis, harmonic_residual, refine_f0  # noqa: F401
 from .analysis import NoiseAnalyzer, noise_analysis  # noqa: F401
@@ -39,7 +39,7 @@ from . import trainer  # noqa: F401
 from .trainer import DeviceBatches, PlateauRate, Trainer, gather_batch, load_checkpoint, latest_checkpoint  # noqa: F401
 from .training import MSSLoss, train_step, allreduce_gradients, OverlappedGradientReducer  # noqa: F401
 
-__all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "Crepe", "F0Encoder", "LoudnessEncoder", "Encoder", "pitch_voicing", "pitch_salience_yin", "conditioning", "ConditioningStatistics", "conditioning_statistics", "fit_conditioning", "tuning", "TuningStatistics", "tuning_statistics", "tune_pitch", "notes", "Notes", "extract_notes", "render_notes", "AutoEncoder", "AudioData", "PLHDataset", "load_audio", "example_geometry", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency", "griffinlim",
+__all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "GraphedSynth", "GraphedLiveDecoder", "GraphedTrainStep", "Controller", "Decoder", "Crepe", "F0Encoder", "LoudnessEncoder", "Encoder", "pitch_voicing", "pitch_salience_yin", "conditioning", "ConditioningStatistics", "conditioning_statistics", "fit_conditioning", "tuning", "TuningStatistics", "tuning_statistics", "tune_pitch", "notes", "Notes", "extract_notes", "render_notes", "Expression", "note_expression", "AutoEncoder", "AudioData", "PLHDataset", "load_audio", "example_geometry", "GRU", "MSSLoss", "train_step", "allreduce_gradients", "OverlappedGradientReducer", "osc_forward", "osc_backward", "noise_forward", "noise_backward", "calibrate_noise_residency", "griffinlim",
            "normalize_audio", "prepare_spectra", "gram_matrix", "FeatureExtractor", "ContentLoss", "StyleLoss", "style_transfer",
            "analysis", "HarmonicAnalyzer", "harmonic_analysis", "harmonic_resynthesis", "harmonic_residual", "refine_f0", "NoiseAnalyzer", "noise_analysis",
            "ControlTransform", "transform_controls", "ControlMorph", "morph_controls", "ControlAlign", "align_controls", "control_features", "dtw_align",

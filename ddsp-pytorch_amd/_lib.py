@@ -140,6 +140,9 @@ SIGNATURES = {
     "ddsp_griffinlim": (_i32, [_vp] * 6 + [_size, _long, _long, _i32, _i32, _long, _i32, _f32, _vp]),
     "ddsp_wfft_probe_sizes": (_i32, [_i32, _long, ctypes.POINTER(_long), ctypes.POINTER(_long)]),
     "ddsp_wfft_probe": (_i32, [_i32, _vp, _vp, _long, _vp]),
+    "ddsp_notes_expression": (_i32, [_vp] * 9 + [_long, _long, _long, _long, _vp]),
+    "ddsp_notes_render_expr": (_i32, [_vp] * 14 + [_long, _long, _long, _long, _i32] + [_long] * 6 + [_f64, _f64, _f32, _f32] + [_vp] * 7 +
+                               [_long, _long, _f64, _f64, _long, _long, _vp]),
     "ddsp_griffinlim_stage": (_i32, [_i32] + [_vp] * 8 + [_long, _long, _i32, _i32, _long, _f32, _vp]),
     "ddsp_notes_extract": (_i32, [_vp] * 12 + [_long, _long, _long, _long, _i32, _i32, _long, _long, _i32, _f32, _f32, _vp]),
     "ddsp_notes_render": (_i32, [_vp] * 14 + [_long, _long, _long, _long, _i32] + [_long] * 6 + [_f64, _f64, _f32, _f32, _vp]),

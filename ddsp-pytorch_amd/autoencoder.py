@@ -42,7 +42,7 @@ import torch.nn.functional as F
 
 from .conditioning import fit_conditioning
 from .tuning import tune_pitch
-from .notes import extract_notes, render_notes
+from .notes import extract_notes, note_expression, render_notes
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
@@ -80,15 +80,18 @@ class AutoEncoder(nn.Module):
             z = tune_pitch(z, **(tune if isinstance(tune, dict) else {}))
         return self.decoder(z)
 
-    def transcribe(self, x: torch.Tensor, **extract_options):
+    def transcribe(self, x: torch.Tensor, expression: bool = False, **extract_options):
         """audio [B, L] -> notes.Notes: the encoder (on the clip padded as forward() pads it) followed by notes.extract_notes
-        and its options (tuning, scale, root, hysteresis, min_note_frames, max_notes)."""
+        and its options (tuning, scale, root, hysteresis, min_note_frames, max_notes).  expression=True -> (notes, expression):
+        notes.note_expression of the same controls, the pitch and loudness curve of every note, for play(notes, expression=...)."""
         with torch.no_grad():
             z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
-        return extract_notes(z, **extract_options)
+        found = extract_notes(z, **extract_options)
+        return (found, note_expression(z, found)) if expression else found
 
     def play(self, notes, frames=None, target=None, **render_options) -> torch.Tensor:
-        """notes.Notes -> audio [B, frames hop]: notes.render_notes (and its options) at the decoder's sample rate and hop, then
+        """notes.Notes -> audio [B, frames hop]: notes.render_notes (and its options, `expression`, `source`, `bend_amount`,
+        `dynamics_amount`, `keep_attack` and `keep_release` among them) at the decoder's sample rate and hop, then
         `fit_conditioning(z, target)` where a ConditioningStatistics `target` is given (the decoder's training set: the score's
         register and levels brought into its range), then the decoder's ordinary forward.  frames=None takes the end of the last
         note (that reads the notes back from the device)."""

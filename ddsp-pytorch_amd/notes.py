@@ -11,11 +11,15 @@ per-frame array; this module turns the runs into a list of events and goes the o
   extract_notes         a control dict -> Notes (the notes `tune_pitch` would move, as records)
   render_notes          Notes -> a control dict with f0, normalized_cents, loudness, harmonicity and voiced: what the Controller and
                         the oscillator bank read, so a trained decoder can be played from a score
+  Expression            what a record does not hold (section 10g): bend [B, T] int32 (each frame's distance from its note's centre),
+                        loudness [B, T] fp32 or None, and the source notes' onset, frames, level and count
+  note_expression       a control dict and the Notes found on it -> Expression; render_notes(..., expression=e) gives the curves
+                        back to the notes after an edit, stretched to each note's new length
 
-Everything is integer arithmetic on positions of 2^-16 cent (include/ddsp_hip.h has the text): CUDA tensors run the two kernels
+Everything is integer arithmetic on positions of 2^-16 cent (include/ddsp_hip.h has the text): CUDA tensors run the kernels
 of csrc/ddsp_notes.hip, CPU tensors the same definition as numpy operations, to the same bits in every integer output and in
-normalized_cents (tests/notes_reference.py has it as plain loops).  Neither call synchronises with the host or allocates after
-its outputs, so both can be captured in a graph."""
+normalized_cents (tests/notes_reference.py and tests/notes_expression_reference.py have it as plain loops).  No call synchronises
+with the host or allocates after its outputs, so all can be captured in a graph."""
 from __future__ import annotations
 
 import math
@@ -27,14 +31,15 @@ import torch
 
 from . import _lib
 from .encoder import _refuse_grad
-from .tuning import (MAX_HYSTERESIS, ORIGIN, SCALES, SEMITONE, TuningStatistics, _gates, _inputs, _on_host, _root, _row_notes_host,
-                     scale_mask, tuning_statistics)
+from .tuning import (LIMIT, MAX_HYSTERESIS, ORIGIN, SCALES, SEMITONE, TuningStatistics, _gates, _inputs, _on_host, _positions_host, _root,
+                     _row_notes_host, scale_mask, tuning_statistics)
 
 NO_PITCH = -(1 << 31)                                           # the pitch of an unused slot
 HOLD = 6900 * 65536                                             # the position held where no note gives one (A4)
 MAX_DETUNE = 1 << 30
 MAX_STEPS = 1 << 24                                             # glide, attack, release, delay and ramp stay below it
 MAX_TRANSPOSE = 128.0                                           # semitones
+MAX_AMOUNT = 16.0                                               # |bend_amount| and |dynamics_amount| up to it
 _KEEP_DETUNE, _CONCERT = 1, 2                                   # DDSP_NOTES_*
 _NAN = np.float32(np.nan)
 TICKS_PER_QUARTER, TEMPO = 480, 500000                          # write_midi: 120 quarter notes a minute, 960 ticks a second
@@ -185,11 +190,14 @@ class Notes:
         snapped = torch.div(2 * o + (int(g) - 1), 2 * int(g), rounding_mode="floor") * int(g)
         return self._with(onset=torch.where(self._used(), snapped.to(torch.int32), self.onset))
 
-    def sorted(self) -> "Notes":
-        """The used slots in order of onset (a stable sort), the unused ones behind them."""
+    def sorted(self, return_order: bool = False):
+        """The used slots in order of onset (a stable sort), the unused ones behind them.  return_order=True -> (notes, order):
+        `order` int32 [B, N], the slot each note came from -- what `render_notes(..., source=order)` needs to find the notes'
+        curves in an Expression taken before the sort."""
         key = torch.where(self._used(), self.onset.to(torch.int64), torch.full_like(self.onset, 1 << 31, dtype=torch.int64))
         order = torch.sort(key, dim=1, stable=True).indices
-        return self._with(**{k: torch.gather(getattr(self, k), 1, order) for k in ("onset", "frames", "pitch", "detune", "level")})
+        notes = self._with(**{k: torch.gather(getattr(self, k), 1, order) for k in ("onset", "frames", "pitch", "detune", "level")})
+        return (notes, order.to(torch.int32)) if return_order else notes
 
     def validate(self) -> "Notes":
         """Raises a ValueError on count > N or onsets that are not in order.  Opt-in: it synchronises with the device."""
@@ -262,6 +270,68 @@ class Notes:
                 sounding = None
         return cls(onset=[x[0] for x in notes], frames=[x[1] for x in notes], pitch=[x[2] for x in notes],
                    level=[lo + x[3] * (hi - lo) / 127.0 for x in notes], scale="chromatic")
+
+
+class Expression:
+    """What a performer gave the notes of a performance beyond the five numbers of a record: `bend`
+    int32 [B, T], each frame's distance from its note's centre in units of 2^-16 cent (0 on a frame of no note); `loudness`
+    fp32 [B, T], a copy of the performance's loudness track, or None; and the records that say where each note's curve lies:
+    the source notes' `onset`, `frames` [B, N] int32, `level` [B, N] fp32 and `count` [B] int32.  `owner` int32 [B, T] (the note
+    of each frame, -1 for none) is there when note_expression was asked for it.  `render_notes(notes, ..., expression=e)` reads
+    it; the notes may have been edited in between."""
+
+    def __init__(self, bend, loudness, onset, frames, level, count, owner=None):
+        self.bend = torch.as_tensor(bend, dtype=torch.int32).contiguous()
+        dev = self.bend.device
+        if self.bend.dim() != 2 or self.bend.shape[0] < 1 or self.bend.shape[1] < 1:
+            raise ValueError(f"Expression: bend must be [B, T] with B, T >= 1, got {tuple(self.bend.shape)}")
+        B = self.bend.shape[0]
+        self.loudness = None if loudness is None else torch.as_tensor(loudness, dtype=torch.float32, device=dev).contiguous()
+        self.owner = None if owner is None else torch.as_tensor(owner, dtype=torch.int32, device=dev).contiguous()
+        for name in ("loudness", "owner"):
+            x = getattr(self, name)
+            if x is not None and x.shape != self.bend.shape:
+                raise ValueError(f"Expression: {name} is {tuple(x.shape)}, bend {tuple(self.bend.shape)}")
+        self.onset = torch.as_tensor(onset, dtype=torch.int32, device=dev).contiguous()
+        self.frames = torch.as_tensor(frames, dtype=torch.int32, device=dev).contiguous()
+        self.level = torch.as_tensor(level, dtype=torch.float32, device=dev).contiguous()
+        if self.onset.dim() != 2 or self.onset.shape[0] != B or self.frames.shape != self.onset.shape or self.level.shape != self.onset.shape:
+            raise ValueError(f"Expression: onset, frames and level must be [{B}, N], got {tuple(self.onset.shape)}, "
+                             f"{tuple(self.frames.shape)} and {tuple(self.level.shape)}")
+        self.count = torch.as_tensor(count, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+        if self.count.shape[0] != B:
+            raise ValueError(f"Expression: count must hold one value per row ({B}), got {self.count.shape[0]}")
+
+    @property
+    def rows(self) -> int:
+        return self.bend.shape[0]
+
+    @property
+    def source_frames(self) -> int:
+        return self.bend.shape[1]
+
+    @property
+    def max_notes(self) -> int:
+        return self.onset.shape[1]
+
+    @property
+    def device(self):
+        return self.bend.device
+
+    def _tensors(self) -> dict:
+        return dict(bend=self.bend, loudness=self.loudness, onset=self.onset, frames=self.frames, level=self.level, count=self.count,
+                    owner=self.owner)
+
+    def to(self, device) -> "Expression":
+        return Expression(**{k: None if v is None else v.to(device) for k, v in self._tensors().items()})
+
+    def to_dict(self) -> dict:
+        """Plain tensors (on the CPU); None where there is no loudness or owner."""
+        return {k: None if v is None else v.cpu() for k, v in self._tensors().items()}
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "Expression":
+        return cls(d["bend"], d["loudness"], d["onset"], d["frames"], d["level"], d["count"], d.get("owner"))
 
 
 def _vlq(value: int) -> bytes:
@@ -407,6 +477,70 @@ def _render_row_host(onset, frames, pitch, detune, level, n, o, T, keep, concert
     return pos, owner, loud
 
 
+def _expression_row_host(cents, onset, frames, pitch, detune, n, o):
+    """-> bend int32 [T], owner int32 [T] of one row"""
+    T = cents.shape[0]
+    if n == 0:
+        return np.zeros(T, dtype=np.int32), np.full(T, -1, dtype=np.int32)
+    onset, frames, pitch, detune = (x[:n].astype(np.int64) for x in (onset, frames, pitch, detune))
+    valid = (frames >= 1) & (pitch >= 0) & (pitch <= 127) & (np.abs(detune) <= MAX_DETUNE)
+    t = np.arange(T, dtype=np.int64)
+    star = np.searchsorted(onset, t, side="right") - 1
+    i = np.maximum(star, 0)
+    with np.errstate(all="ignore"):
+        own = (star >= 0) & valid[i] & (t - onset[i] < frames[i]) & (np.abs(cents) <= LIMIT)
+    bend = _positions_host(cents, own) - 65536 * int(min(max(o, -50), 50)) - pitch[i] * SEMITONE - detune[i]
+    bend = np.clip(bend, -(1 << 31), (1 << 31) - 1)                        # (records that do not match the track)
+    return np.where(own, bend, 0).astype(np.int32), np.where(own, star, -1).astype(np.int32)
+
+
+def _time_map_host(k, length, Ls, keep_attack, keep_release):
+    """Destination frame k of a note that sounds `length` frames -> (q, f), the position in its source note of Ls frames, f in
+    2^-16 frame; int64 arrays with 0 <= k < length and Ls >= 1."""
+    a = np.minimum(np.minimum(keep_attack, Ls), length)
+    r = np.minimum(np.minimum(keep_release, Ls - a), length - a)
+    middle = (k >= a) & (k < length - r)
+    D = np.where(middle, length - a - r + 1, 1)
+    x = np.where(middle, (k - a + 1) * (Ls - a - r + 1), 0)
+    q = np.where(k < a, k, np.where(middle, a - 1 + x // D, Ls - (length - k)))
+    f = ((x % D) << 16) // D
+    ends = (q < 0) | (q >= Ls - 1)
+    return np.clip(q, 0, Ls - 1), np.where(ends, 0, f)
+
+
+def _express_row_host(pos, owner, loud, onset, frames, n, source, src_onset, src_frames, src_level, n_src, bend, src_loud, bend_amount,
+                      dyn_amount, keep_attack, keep_release):
+    """One row of the plain render (position int64, owner, loudness fp64 [T]) -> position and loudness with the source's curves"""
+    on = owner >= 0
+    if n == 0 or n_src == 0 or not on.any():
+        return pos, loud
+    Tsrc = bend.shape[0]
+    onset, frames = onset[:n].astype(np.int64), frames[:n].astype(np.int64)
+    i = np.maximum(owner, 0).astype(np.int64)
+    k = np.arange(pos.shape[0], dtype=np.int64) - onset[i]
+    nxt = np.minimum(i + 1, n - 1)
+    length = np.where(i + 1 < n, np.minimum(frames[i], onset[nxt] - onset[i]), frames[i])       # L'
+    j = i if source is None else source[i].astype(np.int64)
+    ok = on & (k < length) & (j >= 0) & (j < n_src)
+    j = np.where(ok, j, 0)
+    Ls, so = src_frames[j].astype(np.int64), src_onset[j].astype(np.int64)
+    ok &= (Ls >= 1) & (so >= 0) & (so + Ls <= Tsrc)
+    Ls, so = np.where(ok, Ls, 1), np.where(ok, so, 0)
+    q, f = _time_map_host(np.where(ok, k, 0), np.where(ok, length, 1), Ls, keep_attack, keep_release)
+    at = so + q
+    nxt = np.minimum(at + 1, Tsrc - 1)                                      # (read only where f > 0: inside the source note)
+    b = bend[at].astype(np.int64)
+    b = b + np.where(f > 0, ((bend[nxt].astype(np.int64) - b) * f + 32768) >> 16, 0)
+    pos = pos + np.where(ok, np.rint(bend_amount * b.astype(np.float64)).astype(np.int64), 0)
+    if src_loud is not None and dyn_amount != 0.0:
+        with np.errstate(all="ignore"):
+            sl = src_level[j].astype(np.float64)
+            l = src_loud[at].astype(np.float64)
+            l = np.where(f > 0, l + (src_loud[nxt].astype(np.float64) - l) * (f.astype(np.float64) / 65536.0), l)
+            loud = np.where(ok & ~np.isnan(sl), loud + dyn_amount * (l - sl), loud)
+    return pos, loud
+
+
 # ------------------------------------------------------------------------------------------------------------------ the calls
 def _count(x, name, what, least=0, most=None):
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least or (most is not None and x >= most):
@@ -491,10 +625,57 @@ def extract_notes(z: dict, tuning=None, scale=None, root=None, hysteresis: float
     return Notes(*(torch.from_numpy(rec[i]) for i in range(4)), torch.from_numpy(level), torch.from_numpy(count), **opts)
 
 
+def note_expression(z: dict, notes: Notes, return_owner: bool = False) -> Expression:
+    """The expression of the performance `z` (the controls `extract_notes` reads) under the notes found on it: -> Expression.
+    A frame belongs to the note that owns it in `render_notes`' sense (the last note that began at or before it, valid, not yet
+    over) where its normalized_cents lies within +-4; its `bend` is its position minus the note's centre on the performance's own
+    grid, pitch S + detune + 65536 offset, so that rendering the unedited notes with the expression returns every position to
+    the bit.  The loudness track, where z has one, is copied.  Records that do not match z give defined values.  One launch."""
+    what = "note_expression"
+    if not isinstance(notes, Notes):
+        raise ValueError(f"{what}: notes must be a Notes, got {type(notes).__name__}")
+    n, _, _, _, _ = _inputs(z, what, None, None, False)
+    B, T = n.shape[:2]
+    N = notes.max_notes
+    if notes.rows != B:
+        raise ValueError(f"{what}: the notes have {notes.rows} rows, the controls {B}")
+    if notes.device != n.device:
+        raise ValueError(f"{what}: the notes are on {notes.device}, the controls on {n.device}: move them once with .to()")
+    loud = z.get("loudness")
+    if loud is not None:
+        if loud.shape != n.shape or loud.device != n.device:
+            raise ValueError(f"{what}: loudness is {tuple(loud.shape)} on {loud.device}, the pitch {tuple(n.shape)} on {n.device}")
+        _refuse_grad(loud, what)
+        loud = loud.detach().float().reshape(B, T).clone()
+    if T >= 1 << 24 or B * T >= 1 << 31 or B * N >= 1 << 31:
+        raise ValueError(f"{what}: {B} x {T} frames, {N} slots: a row takes fewer than 2^24 frames, a call fewer than 2^31 frames and slots")
+    if n.is_cuda:
+        dev = n.device
+        L = _lib.lib()
+        nc = n.detach().float().contiguous()
+        bend = torch.empty((B, T), device=dev, dtype=torch.int32)
+        owner = torch.empty((B, T), device=dev, dtype=torch.int32) if return_owner else None
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = L.ddsp_notes_expression(nc.data_ptr(), ptr(notes.onset), ptr(notes.frames), ptr(notes.pitch), ptr(notes.detune),
+                                         notes.count.data_ptr(), notes.offset.data_ptr(), bend.data_ptr(), ptr(owner), B, T, N, notes.groups,
+                                         torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_notes_expression")
+        return Expression(bend, loud, notes.onset.clone(), notes.frames.clone(), notes.level.clone(), notes.count.clone(), owner)
+    rec = [getattr(notes, k).numpy() for k in ("onset", "frames", "pitch", "detune")]
+    counts, offs = notes.count.numpy(), notes.offset.numpy()
+    cents = n.detach().float().numpy().reshape(B, T)
+    rows = [_expression_row_host(cents[b], *(x[b] for x in rec), min(max(int(counts[b]), 0), N), offs[b if notes.groups > 1 else 0])
+            for b in range(B)]
+    return Expression(torch.from_numpy(np.stack([r[0] for r in rows])), loud, notes.onset.clone(), notes.frames.clone(), notes.level.clone(),
+                      notes.count.clone(), torch.from_numpy(np.stack([r[1] for r in rows])) if return_owner else None)
+
+
 def render_notes(notes: Notes, frames: int, sample_rate: int, hop_length: int, detune: bool = True, concert: bool = False,
                  transpose: float = 0.0, glide: int = 0, attack: int = 0, release: int = 0, floor: float = 0.0, default_level: float = 1.0,
                  vibrato_cents: float = 0.0, vibrato_hz: float = 5.5, vibrato_delay: int = 0, vibrato_ramp: int = 1,
-                 return_info: bool = False) -> dict:
+                 return_info: bool = False, expression=None, source=None, bend_amount: float = 1.0, dynamics_amount: float = 1.0,
+                 keep_attack: int = 0, keep_release: int = 0) -> dict:
     """Note events -> `frames` frames of controls: a dict with f0, normalized_cents, loudness, harmonicity (fp32 [B, T, 1]) and
     voiced (bool [B, T, 1]); return_info=True adds position (int64 [B, T], units of 2^-16 cent on the MIDI scale) and owner
     (int32 [B, T]: the note a frame belongs to, -1 for none).
@@ -506,7 +687,15 @@ def render_notes(notes: Notes, frames: int, sample_rate: int, hop_length: int, d
     portamento lead from the previous note where the two touch; vibrato of `vibrato_cents` at `vibrato_hz` starts
     `vibrato_delay` frames into a note and swells over `vibrato_ramp` frames.  Off frames hold the pitch of the note before
     them.  Loudness is the note's level (`default_level` where that is NaN) over `floor`, with `attack` and `release` frames of
-    linear ramp at the note's ends; off frames are at `floor`.  harmonicity is 1 on and 0 off.  One launch."""
+    linear ramp at the note's ends; off frames are at `floor`.  harmonicity is 1 on and 0 off.  One launch.
+
+    `expression` (an Expression from `note_expression`, on the notes' device and with as many rows) gives the notes their
+    performer's curves back: note i reads the curve of the expression's note `source[i]` (`source` int32
+    [B, N]; None: note i itself -- right after any edit that keeps the slots, such as transpose, quantize or moved onsets; after
+    `sorted(return_order=True)` pass the order), stretched linearly to the note's sounding length with the first `keep_attack`
+    and the last `keep_release` frames kept one to one.  The pitch gains `bend_amount` times the curve's bend, the loudness
+    `dynamics_amount` times the curve's loudness above the source note's level, on top of everything above.  A note without a
+    valid source is rendered as without an expression; expression=None is the call as it always was."""
     what = "render_notes"
     if not isinstance(notes, Notes):
         raise ValueError(f"{what}: notes must be a Notes, got {type(notes).__name__}")
@@ -529,6 +718,29 @@ def render_notes(notes: Notes, frames: int, sample_rate: int, hop_length: int, d
     depth = float(vibrato_cents) * 65536.0
     omega = 2.0 * math.pi * (float(vibrato_hz) * hop_length / sample_rate)
     flags = (_KEEP_DETUNE if detune else 0) | (_CONCERT if concert else 0)
+    e = expression
+    if e is None:
+        if source is not None:
+            raise ValueError(f"{what}: source names the notes of an expression; none is given")
+    else:
+        if not isinstance(e, Expression):
+            raise ValueError(f"{what}: expression must be an Expression or None, got {type(e).__name__}")
+        if e.rows != B:
+            raise ValueError(f"{what}: the expression has {e.rows} rows, the notes {B}")
+        if e.device != notes.device:
+            raise ValueError(f"{what}: the expression is on {e.device}, the notes on {notes.device}: move it once with .to()")
+        if source is not None:
+            source = torch.as_tensor(source, dtype=torch.int32, device=notes.device).contiguous()
+            if source.shape != (B, N):
+                raise ValueError(f"{what}: source must be [{B}, {N}] (one source note per note), got {tuple(source.shape)}")
+        keep_attack, keep_release = (_count(x, k, what, 0, MAX_STEPS) for k, x in (("keep_attack", keep_attack), ("keep_release", keep_release)))
+        bend_amount, dynamics_amount = float(bend_amount), float(dynamics_amount)
+        if not (abs(bend_amount) <= MAX_AMOUNT and abs(dynamics_amount) <= MAX_AMOUNT):
+            raise ValueError(f"{what}: bend_amount and dynamics_amount must be finite and within +-{MAX_AMOUNT:g}")
+        Ts, Ns = e.source_frames, e.max_notes
+        if Ts >= 1 << 24 or B * Ts >= 1 << 31 or B * Ns >= 1 << 31:
+            raise ValueError(f"{what}: an expression of {B} x {Ts} frames, {Ns} slots: a row takes fewer than 2^24 frames, a call fewer "
+                             "than 2^31 frames and slots")
     if notes.onset.is_cuda:
         dev = notes.device
         L = _lib.lib()
@@ -537,19 +749,33 @@ def render_notes(notes: Notes, frames: int, sample_rate: int, hop_length: int, d
         position = torch.empty((B, T), device=dev, dtype=torch.int64) if return_info else None
         owner = torch.empty((B, T), device=dev, dtype=torch.int32) if return_info else None
         ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        args = (ptr(notes.onset), ptr(notes.frames), ptr(notes.pitch), ptr(notes.detune), ptr(notes.level), notes.count.data_ptr(),
+                notes.offset.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), voiced.data_ptr(),
+                ptr(position), ptr(owner), B, T, N, notes.groups, flags, units, glide, attack, release, delay, ramp, depth, omega, floor,
+                default_level)
         with torch.cuda.device(dev):
-            rc = L.ddsp_notes_render(ptr(notes.onset), ptr(notes.frames), ptr(notes.pitch), ptr(notes.detune), ptr(notes.level),
-                                     notes.count.data_ptr(), notes.offset.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
-                                     out[2].data_ptr(), out[3].data_ptr(), voiced.data_ptr(), ptr(position), ptr(owner), B, T, N,
-                                     notes.groups, flags, units, glide, attack, release, delay, ramp, depth, omega, floor, default_level,
-                                     torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "ddsp_notes_render")
+            if e is None:
+                rc = L.ddsp_notes_render(*args, torch.cuda.current_stream().cuda_stream)
+            else:
+                rc = L.ddsp_notes_render_expr(*args, ptr(source), ptr(e.onset), ptr(e.frames), ptr(e.level), e.count.data_ptr(),
+                                              e.bend.data_ptr(), ptr(e.loudness), Ts, Ns, bend_amount, dynamics_amount, keep_attack,
+                                              keep_release, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_notes_render" if e is None else "ddsp_notes_render_expr")
         z = dict(f0=out[0], normalized_cents=out[1], loudness=out[2], harmonicity=out[3], voiced=voiced)
         return dict(z, position=position, owner=owner) if return_info else z
     rec = [getattr(notes, k).numpy() for k in ("onset", "frames", "pitch", "detune", "level")]
     counts, offs = notes.count.numpy(), notes.offset.numpy()
     rows = [_render_row_host(*(x[b] for x in rec), min(max(int(counts[b]), 0), N), offs[b if notes.groups > 1 else 0], T, bool(detune),
                              bool(concert), units, glide, attack, release, floor, default_level, depth, omega, delay, ramp) for b in range(B)]
+    if e is not None:
+        src = None if source is None else source.numpy()
+        so, sf, sl, sc, bend = (x.numpy() for x in (e.onset, e.frames, e.level, e.count, e.bend))
+        sloud = None if e.loudness is None else e.loudness.numpy()
+        for b in range(B):
+            pos, loud = _express_row_host(rows[b][0], rows[b][1], rows[b][2], rec[0][b], rec[1][b], min(max(int(counts[b]), 0), N),
+                                          None if src is None else src[b], so[b], sf[b], sl[b], min(max(int(sc[b]), 0), Ns), bend[b],
+                                          None if sloud is None else sloud[b], bend_amount, dynamics_amount, keep_attack, keep_release)
+            rows[b] = (pos, rows[b][1], loud)
     position = np.stack([r[0] for r in rows])
     owner = np.stack([r[1] for r in rows])
     c = position.astype(np.float64) / 65536.0

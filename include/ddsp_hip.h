@@ -928,6 +928,64 @@ int ddsp_wfft_probe_sizes(int form, long units, long *in_floats, long *out_float
 int ddsp_wfft_probe(int form, const float *in, float *out, long units, void *stream);
 
 /*
+ * Notes with their expression: the pitch and loudness curve a performer gave each note, taken from the
+ * performance and carried through an edit of the notes.  Conventions, records and render as ddsp_notes_extract and
+ * ddsp_notes_render below (positions are int64 counts of 2^-16 cent, S = 100 * 65536, rdiv as there); declared here, ahead of
+ * ddsp_griffinlim_stage, because the header's last four declarations are pinned by tests.
+ *
+ * ddsp_notes_expression: cents (normalized_cents) [B, T], the record arrays onset, frames, pitch, detune [B, N], count [B],
+ * offset [groups] -> bend int32 [B, T] and, where not NULL, owner int32 [B, T].  For frame t of a row:
+ *   1. i* = the largest i < min(count, N) with onset_i <= t (ddsp_notes_render's step 3).
+ *   2. The frame belongs to note i* iff i* exists, is valid (the render's step 2), t < onset_i* + frames_i* and |n_t| <= 4.
+ *   3. Then bend_t = u_t - 65536 o - pitch_i* S - detune_i*, u_t the auto-tune's position of n_t (its step 1), o the clamped
+ *      offset; a value outside int32 (records that do not match the track) is saturated.  owner_t = i*.
+ *   4. Otherwise bend_t = 0 and owner_t = -1.
+ *   Nothing is assumed about where the records came from: onsets out of order give unspecified values, never an access out of
+ *   bounds.  One thread per frame; one launch, no allocation, no host synchronisation.
+ *   DDSP_EINVAL: B < 0, T <= 0, N < 0; then B = 0 returns 0; then a missing pointer (owner may be NULL, the record arrays only
+ *   with N = 0), group counts other than 1 or B.  DDSP_ERANGE: T >= 2^24, B T >= 2^31 or B N >= 2^31.
+ *
+ * ddsp_notes_render_expr: ddsp_notes_render -- every term of it, the glide, the synthetic vibrato and the ga and gr ramps
+ * included -- plus, on the on frames, the curves of a source performance: `source` [B, N] (the source note of each note; NULL:
+ * note i reads source note i), the source's records src_onset, src_frames, src_level [B, Nsrc] and src_count [B], its `bend`
+ * int32 [B, Tsrc] (ddsp_notes_expression's) and, where not NULL, its loudness track src_loudness fp32 [B, Tsrc].
+ *   1. For an on frame of note i (k = t - onset_i, L' its sounding length, the render's step 6), j = source[i], or i.  The
+ *      source is valid iff 0 <= j < min(src_count, Nsrc), src_frames_j >= 1, src_onset_j >= 0 and
+ *      src_onset_j + src_frames_j <= Tsrc.  A note without a valid source is rendered as by ddsp_notes_render; so is a frame
+ *      with k >= L' (there is none while the onsets are in order); so are the off frames.
+ *   2. Time map: with Ls = src_frames_j, a = min(keep_attack, Ls, L') and r = min(keep_release, Ls - a, L' - a), frame k reads
+ *      the source note at (q, f), f in 2^-16 frame:
+ *        k < a (head)          (k, 0)
+ *        k >= L' - r (tail)    (Ls - (L' - k), 0)
+ *        else (middle)         m = k - a + 1, Ns = Ls - a - r + 1, D = L' - a - r + 1:
+ *                              q = a - 1 + (m Ns) div D, f = (((m Ns) mod D) 65536) div D
+ *      then q < 0 gives (0, 0) and q >= Ls - 1 gives (Ls - 1, 0).  The middle interpolates between the anchors k = a - 1 <->
+ *      a - 1 and k = L' - r <-> Ls - r, and is the identity when L' = Ls.  All products stay below 2^48.
+ *   3. Pitch: with b_x = bend[src_onset_j + x], B = b_q + floor(((b_{q+1} - b_q) f + 32768) / 65536) in int64 (b_{q+1} is read
+ *      only where f > 0), and p += llrint(bend_amount (double)B): one fp64 product, exact at amount 1.
+ *   4. Loudness, where src_loudness is given, src_level_j is not a NaN and dyn_amount != 0: with l_x = src_loudness[src_onset_j
+ *      + x], l(q, f) = l_q + (l_{q+1} - l_q) (f / 65536) in fp64 (l_q alone where f = 0), and
+ *      loudness = fl32(base + dyn_amount (l(q, f) - (double)src_level_j)), base the render's floor + (lv - floor) ga gr.
+ *   A thread reads at most two neighbouring source frames, both inside the source note.  One launch, no allocation, no host
+ *   synchronisation.
+ *   DDSP_EINVAL: ddsp_notes_render's options, then Tsrc <= 0, Nsrc < 0, an amount that is not finite or beyond 16 in magnitude,
+ *   keep_attack or keep_release outside 0 .. 2^24 - 1; then B = 0 returns 0; then ddsp_notes_render's pointers, a NULL src_count
+ *   or bend, a NULL src_onset, src_frames or src_level with Nsrc > 0.  DDSP_ERANGE: ddsp_notes_render's sizes, Tsrc >= 2^24,
+ *   B Tsrc >= 2^31 or B Nsrc >= 2^31.
+ */
+int ddsp_notes_expression(const float *cents, const int *onset, const int *frames, const int *pitch, const int *detune,
+                          const int *count, const int *offset, int *bend, int *owner, long B, long T, long N, long groups,
+                          void *stream);
+int ddsp_notes_render_expr(const int *onset, const int *frames, const int *pitch, const int *detune, const float *level,
+                           const int *count, const int *offset, float *f0, float *cents, float *loudness, float *harmonicity,
+                           uint8_t *voiced, long *position, int *owner, long B, long T, long N, long groups, int flags,
+                           long transpose, long glide, long attack, long release, long vibrato_delay, long vibrato_ramp,
+                           double vibrato_depth, double vibrato_omega, float floor_level, float default_level, const int *source,
+                           const int *src_onset, const int *src_frames, const float *src_level, const int *src_count,
+                           const int *bend, const float *src_loudness, long Tsrc, long Nsrc, double bend_amount, double dyn_amount,
+                           long keep_attack, long keep_release, void *stream);
+
+/*
  * Test hook (DDSP_EPERM unless DDSP_TEST_HOOKS=1 was set when the library was loaded): ONE of the three launches of a Griffin-Lim
  * iteration (csrc/ddsp_griffinlim.hip) on the caller's buffers, for tests/test_gpu_griffinlim_stages.py.  It fills the kernels'
  * parameter block and calls the launcher ddsp_griffinlim calls; it does no arithmetic of its own.  Everything is device memory in
