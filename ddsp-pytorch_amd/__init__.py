@@ -16,6 +16,7 @@ from .graphed import GraphedSynth, GraphedLiveDecoder, GraphedTrainStep  # noqa:
 from .gru import GRU, gru_forward, gru_backward, gru_status  # noqa: F401
 from .decoder import Controller, Decoder  # noqa: F401
 from .encoder import Crepe, F0Encoder, LoudnessEncoder, Encoder  # noqa: F401
+from .encoder import mfcc, MFCC, ZEncoder  # noqa: F401
 from .encoder import pitch_argmax, pitch_centered, pitch_weighted, pitch_viterbi, pitch_voicing, pitch_salience_yin  # noqa: F401
 from . import conditioning  # noqa: F401
 from .conditioning import ConditioningStatistics, conditioning_statistics, fit_conditioning  # noqa: F401
@@ -44,4 +45,4 @@ __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "
            "analysis", "HarmonicAnalyzer", "harmonic_analysis", "harmonic_resynthesis", "harmonic_residual", "refine_f0", "NoiseAnalyzer", "noise_analysis",
            "ControlTransform", "transform_controls", "ControlMorph", "morph_controls", "ControlAlign", "align_controls", "control_features", "dtw_align",
            "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
-           "latest_checkpoint"]
+           "latest_checkpoint", "mfcc", "MFCC", "ZEncoder"]

@@ -133,6 +133,7 @@ SIGNATURES = {
     "ddsp_dtw_align": (_i32, [_vp] * 8 + [_size, _long, _long, _long, _i32, _long, _long, _f32, _f64, _vp]),
     "ddsp_loudness_supported": (_i32, [_i32]),
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
+    "ddsp_mfcc": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
     "ddsp_griffinlim_supported": (_i32, [_i32]),

@@ -28,6 +28,12 @@
                              encoder, then Decoder.forward_live -> (audio as numpy, hidden); conditioning=(target, source) maps
                              the block (one launch) between the two
 
+With a decoder that has a timbre latent (conf.z_dims > 0) `forward`, `transfer` and `play` take
+`timbre=`: another clip [B, L'] (its z averaged over time and held for every frame), a latent [B, z_dims] (held) or
+[B, T, z_dims] (per frame).  Without it forward and transfer take the timbre from x itself, frame by frame; play has no audio
+and requires it.  `encode_timbre(y)` is the time average on its own, and forward_live's `hidden` is the pair
+(decoder_hidden, z_hidden).
+
 State-dict keys are the reference's (`encoder.f0_encoder.model.*`, `encoder.loudness_encoder.a_weight`, `decoder.*`).  CREPE
 weights come from `weights` or `conf.crepe_weights` (see encoder.F0Encoder); `voicing` and `tracker` are handed to `Encoder`.
 With tracker 'yin' (the argument, else `conf.pitch_tracker`) no weights are needed and the state dict has no
@@ -57,28 +63,60 @@ class AutoEncoder(nn.Module):
         self.hop_length = conf.hop_length
         self.n_noise_filters = conf.n_noise_filters
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
-        return self.decoder(self.encoder(x))
+    def encode_timbre(self, y: torch.Tensor) -> torch.Tensor:
+        """clip [B, L'] -> [B, z_dims]: the decoder's z_encoder on the clip, averaged over its frames."""
+        self._need_latent("encode_timbre")
+        return self.decoder.z_encoder(y).mean(dim=1)
+
+    def _need_latent(self, what: str) -> None:
+        if self.decoder.z_dims <= 0:
+            raise ValueError(f"{what}: this decoder has no timbre latent (it was built without conf.z_dims)")
+
+    def _timbre(self, timbre, frames: int, what: str) -> torch.Tensor:
+        """`timbre` (a clip [B, L'], a latent [B, z_dims] or [B, T, z_dims]) -> z [B, frames, z_dims]"""
+        self._need_latent(f"{what}(timbre=...)")
+        d = self.decoder.z_dims
+        if timbre.dim() == 2 and timbre.shape[-1] != d:
+            timbre = self.encode_timbre(timbre)
+        if timbre.dim() == 2:
+            return timbre.unsqueeze(1).expand(-1, frames, -1).contiguous()
+        if timbre.dim() != 3 or timbre.shape[1] != frames or timbre.shape[2] != d:
+            raise ValueError(f"{what}: timbre must be a clip [B, L], a latent [B, {d}] or [B, {frames}, {d}], got {tuple(timbre.shape)}")
+        return timbre
+
+    def _with_timbre(self, z: dict, x, timbre, what: str) -> dict:
+        """The encoder's dict with what a decoder with a latent reads besides: `z` from `timbre`, else the clip itself as `audio`."""
+        if timbre is not None:
+            z['z'] = self._timbre(timbre, z['f0'].shape[1], what)
+        elif self.decoder.z_dims > 0:
+            if x is None:
+                raise ValueError(f"{what}: a decoder with a timbre latent needs timbre= here (there is no audio to take it from)")
+            z['audio'] = x
+        return z
+
+    def forward(self, x: torch.Tensor, timbre=None) -> torch.Tensor:
+        z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
+        return self.decoder(self._with_timbre(z, x, timbre, "forward"))
 
     def transfer(self, x: torch.Tensor, target, **fit_options) -> torch.Tensor:
         """audio [B, L] -> audio: `forward` with the encoder's controls brought into `target`'s range on the way
         (conditioning.fit_conditioning and its options: source, octaves, max_octaves, strength, min_frames).  Without a
         `source` every clip is measured by itself, over its whole length.  One more keyword is taken out of the options:
         tune=True, or a dict of tuning.tune_pitch's options, moves the fitted controls' notes onto a scale before the decoder
-        (the chain's last step: octave shift, loudness match, auto-tune); tune=None is the path without it."""
+        (the chain's last step: octave shift, loudness match, auto-tune); tune=None is the path without it.  `timbre=` (taken
+        out of the options as well) is forward's, for a decoder with a timbre latent."""
         tune = fit_options.pop('tune', None)
+        timbre = fit_options.pop('timbre', None)
         if fit_options.get('return_info'):
             raise ValueError("transfer returns audio; ask fit_conditioning itself for the info")
         if tune is not None and tune is not True and tune is not False and not isinstance(tune, dict):
             raise ValueError(f"transfer: tune must be None, a bool or a dict of tune_pitch options, got {type(tune).__name__}")
         if isinstance(tune, dict) and tune.get('return_info'):
             raise ValueError("transfer returns audio; ask tune_pitch itself for the info")
-        x = F.pad(x, (self.padding // 2, self.padding - self.padding // 2))
-        z = fit_conditioning(self.encoder(x), target, **fit_options)
+        z = fit_conditioning(self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2))), target, **fit_options)
         if tune:
             z = tune_pitch(z, **(tune if isinstance(tune, dict) else {}))
-        return self.decoder(z)
+        return self.decoder(self._with_timbre(dict(z), x, timbre, "transfer"))
 
     def transcribe(self, x: torch.Tensor, expression: bool = False, **extract_options):
         """audio [B, L] -> notes.Notes: the encoder (on the clip padded as forward() pads it) followed by notes.extract_notes
@@ -89,12 +127,13 @@ class AutoEncoder(nn.Module):
         found = extract_notes(z, **extract_options)
         return (found, note_expression(z, found)) if expression else found
 
-    def play(self, notes, frames=None, target=None, **render_options) -> torch.Tensor:
+    def play(self, notes, frames=None, target=None, timbre=None, **render_options) -> torch.Tensor:
         """notes.Notes -> audio [B, frames hop]: notes.render_notes (and its options, `expression`, `source`, `bend_amount`,
         `dynamics_amount`, `keep_attack` and `keep_release` among them) at the decoder's sample rate and hop, then
         `fit_conditioning(z, target)` where a ConditioningStatistics `target` is given (the decoder's training set: the score's
         register and levels brought into its range), then the decoder's ordinary forward.  frames=None takes the end of the last
-        note (that reads the notes back from the device)."""
+        note (that reads the notes back from the device).  `timbre` (a clip or a latent, see the module docstring) is required
+        when the decoder has a timbre latent: a score has no audio to take it from."""
         if render_options.get('return_info'):
             raise ValueError("play returns audio; ask render_notes itself for the info")
         if frames is None:
@@ -104,7 +143,7 @@ class AutoEncoder(nn.Module):
         z = render_notes(notes, frames, self.decoder.harmonics.sample_rate, self.hop_length, **render_options)
         if target is not None:
             z = fit_conditioning(z, target)
-        return self.decoder(z)
+        return self.decoder(self._with_timbre(dict(z), None, timbre, "play"))
 
     def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,
                 refine: int = 0) -> dict:
@@ -187,14 +226,19 @@ class AutoEncoder(nn.Module):
         audio_in = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).unsqueeze(0).to(device, non_blocking=False)
         return audio_in[:, self.hop_length // 2:-(self.hop_length - self.hop_length // 2)]
 
-    def forward_live(self, x: np.ndarray, hidden: torch.Tensor, delayed: bool = False, conditioning=None):
-        """`delayed`: Decoder.forward_live's (the overlap-add noise as a stream, the audio n_noise_filters - 2 samples late).
+    def forward_live(self, x: np.ndarray, hidden, delayed: bool = False, conditioning=None):
+        """On a decoder with a timbre latent `hidden` is the pair (decoder_hidden, z_hidden), taken and returned.
+        `delayed`: Decoder.forward_live's (the overlap-add noise as a stream, the audio n_noise_filters - 2 samples late).
         `conditioning`: None, or (target, source) ConditioningStatistics on the module's device -- the block's controls go
         through fit_conditioning(z, target, source=source), one launch, before the decoder (calibrate `source` once on a few
         seconds of the player; a source of None would measure each short block by itself)."""
         self.decoder.check_live(delayed, "forward_live")
-        z = self.encoder(self.live_window(x))
+        window = self.live_window(x)
+        z = self.encoder(window)
         if conditioning is not None:
             target, source = conditioning
             z = fit_conditioning(z, target, source=source)
+        if self.decoder.z_dims > 0:
+            z = dict(z)
+            z['audio'] = window           # the block's frames are the window's own: Decoder.forward_live encodes it with z_hidden
         return self.decoder.forward_live(z, hidden, delayed=delayed)

@@ -7,6 +7,11 @@ Sub-module and parameter names follow the reference so that its checkpoints load
 (`rt/utils.py:7-24` strips the `model.` prefix, `rt/synth.py:17` loads into `zak.decoder`):
   controller.mlp_f0 / mlp_loudness / gru / mlp_gru / dense_harmonic / dense_loudness / dense_filter,
   harmonics.{harmonics,last_phases}, reverb.{noise,decay,wet,t,buffer}.
+
+With `conf.z_dims > 0` (opt-in; absent or 0 nothing below exists and every key and output bit is as without it) the decoder is
+conditioned on a third input, the time-varying timbre latent z [B, T, z_dims] of the DDSP autoencoder:
+`controller.mlp_z` is a third stack beside mlp_f0 / mlp_loudness, and the decoder owns `z_encoder` (encoder.ZEncoder), which
+computes z from `batch['audio']` where the batch does not bring a `z` of its own.
 """
 from __future__ import annotations
 
@@ -16,6 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import dense
+from .encoder import ZEncoder
 from .filtered_noise import FilteredNoise
 from .gru import GRU
 from .harmonic_oscillator import OscillatorBank
@@ -316,8 +322,13 @@ class Controller(nn.Module):
         width, depth = conf.decoder_mlp_units, conf.decoder_mlp_layers
         self.mlp_f0 = _dense_stack(1, width, depth)
         self.mlp_loudness = _dense_stack(1, width, depth)
-        self.gru = GRU(2 * width, conf.decoder_gru_units, conf.decoder_gru_layers, batch_first=True)
-        self.mlp_gru = _dense_stack(conf.decoder_gru_units + 2 * width, width, depth)
+        self.z_dims = int(getattr(conf, 'z_dims', 0) or 0)
+        n_stacks = 2
+        if self.z_dims > 0:
+            self.mlp_z = _dense_stack(self.z_dims, width, depth)
+            n_stacks = 3
+        self.gru = GRU(n_stacks * width, conf.decoder_gru_units, conf.decoder_gru_layers, batch_first=True)
+        self.mlp_gru = _dense_stack(conf.decoder_gru_units + n_stacks * width, width, depth)
         self.dense_harmonic = nn.Linear(width, conf.n_harmonics)
         self.dense_loudness = nn.Linear(width, 1)
         self.dense_filter = nn.Linear(width, conf.n_noise_filters)
@@ -325,13 +336,22 @@ class Controller(nn.Module):
     def forward(self, batch, hidden=None):
         z_pitch = _run_stack(self.mlp_f0, batch['normalized_cents'])
         z_loud = _run_stack(self.mlp_loudness, batch['loudness'])
-        z = torch.cat((z_pitch, z_loud), dim=-1)
+        stacks = (z_pitch, z_loud)
+        if self.z_dims > 0:
+            if batch.get('z') is None:
+                raise ValueError("Controller: this decoder is conditioned on a timbre latent (z_dims > 0) and the batch has no 'z'")
+            latent = batch['z']
+            if latent.shape[:-1] != z_pitch.shape[:-1] or latent.shape[-1] != self.z_dims:
+                raise ValueError(f"Controller: 'z' must be {tuple(z_pitch.shape[:-1]) + (self.z_dims,)}, got {tuple(latent.shape)}")
+            z_timbre = _run_stack(self.mlp_z, latent)
+            stacks += (z_timbre if z_timbre.dtype == z_pitch.dtype else z_timbre.to(z_pitch.dtype),)
+        z = torch.cat(stacks, dim=-1)
         z, state = self.gru(z, hidden) if hidden is not None else self.gru(z)
         if z.dtype != z_pitch.dtype:
             # torch.autocast: the recurrence hands back fp32, the stacks 16-bit activations.  One narrow cast of z here instead of
             # cat widening both stacks to fp32 and the next Linear narrowing all three again (the Linear computes in 16 bit anyway)
             z = z.to(z_pitch.dtype)
-        z = _run_stack(self.mlp_gru, torch.cat((z, z_pitch, z_loud), dim=-1))
+        z = _run_stack(self.mlp_gru, torch.cat((z,) + stacks, dim=-1))
         if FUSED_HEADS and z.is_cuda and z.dtype in dense._IO:
             c, a, H = _Heads.apply(z, self.dense_harmonic.weight, self.dense_harmonic.bias, self.dense_loudness.weight,
                                    self.dense_loudness.bias, self.dense_filter.weight, self.dense_filter.bias)
@@ -354,6 +374,27 @@ class Decoder(nn.Module):
         self.harmonics = OscillatorBank(conf)
         self.noise = FilteredNoise(conf, rng=noise_rng, seed=seed, overlap_add=noise_overlap_add)
         self.reverb = Reverb(conf)
+        self.z_dims = self.controller.z_dims
+        if self.z_dims > 0:
+            self.z_encoder = ZEncoder(conf)
+
+    def with_latent(self, batch, z_hidden=None, live: bool = False):
+        """The batch the controller reads: `batch['z']` where given, else z_encoder's of `batch['audio']` (the clip [B, T hop] as
+        the dataset stores it; with `live` the block's window, whose frames are its own, and the GRU state `z_hidden`).
+        -> (batch, z_hidden after the block).  A decoder without a latent returns the batch as it is."""
+        if self.z_dims <= 0:
+            return batch, z_hidden
+        if batch.get('z') is not None:
+            return batch, z_hidden
+        if batch.get('audio') is None:
+            raise ValueError("Decoder: this decoder is conditioned on a timbre latent (z_dims > 0): the batch needs 'z' [B, T, z_dims] "
+                             "or the 'audio' [B, T hop] to compute it from")
+        batch = dict(batch)
+        if live:
+            batch['z'], z_hidden = self.z_encoder.live(batch['audio'], z_hidden)
+        else:
+            batch['z'] = self.z_encoder(batch['audio'])
+        return batch, z_hidden
 
     def check_live(self, delayed: bool, what: str) -> None:
         """The one rule of every real-time entry point: the overlap-add noise runs live only as a stream `noise.stream_delay` samples
@@ -380,11 +421,23 @@ class Decoder(nn.Module):
         return self.noise(ctrl, out=dry)
 
     def forward(self, z):
+        if self.z_dims > 0:
+            z, _ = self.with_latent(z)
         return self.reverb(self.synthesize(self.controller(z)))
 
     def forward_live(self, z, hidden, delayed: bool = False):
+        """With a timbre latent `hidden` is the pair (decoder_hidden, z_hidden), taken and returned (z_hidden None: a fresh state);
+        `z['audio']` is then the block's window as the encoder saw it, unless the block brings its own `z['z']`."""
         # (without the stream a callback's block would lose the M/2 samples its frames spread into the neighbouring blocks)
         self.check_live(delayed, "forward_live")
+        if self.z_dims > 0:
+            if not isinstance(hidden, (tuple, list)) or len(hidden) != 2:
+                raise ValueError("forward_live: a decoder with a timbre latent carries hidden = (decoder_hidden, z_hidden)")
+            hidden, z_hidden = hidden
+            z, z_hidden = self.with_latent(z, z_hidden, live=True)
+            ctrl, hidden = self.controller(z, hidden)
+            audio = self.reverb.live_forward(self.synthesize(ctrl, live=True, delayed=delayed))
+            return audio.cpu().squeeze(0).numpy(), (hidden, z_hidden)
         ctrl, hidden = self.controller(z, hidden)
         audio = self.reverb.live_forward(self.synthesize(ctrl, live=True, delayed=delayed))
         return audio.cpu().squeeze(0).numpy(), hidden   # one D2H per callback (rt/synth.py:50-52)

@@ -11,6 +11,9 @@
                    unvoiced gaps held or interpolated (one launch; `Encoder(voicing=...)` applies it, off by default)
   LoudnessEncoder  A-weighted loudness of the un-windowed STFT (encoder.py:131-156)
   Encoder          both, as the dict {f0, harmonicity, loudness, probabilities, normalized_cents} (encoder.py:159-177)
+  mfcc, MFCC       mel-frequency cepstral coefficients on LoudnessEncoder's frame grid (one launch, csrc/ddsp_mfcc.hip)
+  ZEncoder         the timbre latent z of the DDSP autoencoder: MFCC -> LayerNorm -> GRU -> Linear (the decoder owns one when
+                   conf.z_dims > 0)
 
 On CUDA tensors the work runs on hand-written HIP (csrc/ddsp_encoder.hip, csrc/ddsp_pitch.hip, csrc/ddsp_yin.hip, csrc/ddsp_loudness.hip;
 include/ddsp_hip.h) around the library work it keeps: CREPE's convolutions on MIOpen (F.conv1d on a [N, C, L] view of the
@@ -39,6 +42,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import dense
+from .gru import GRU
 
 PITCH_BINS = 360
 PITCH_DECODERS = ('argmax', 'weighted', 'viterbi')
@@ -849,3 +854,205 @@ class Encoder(nn.Module):
             out['f0'], out['voiced'], out['normalized_cents'], _ = pitch_voicing(f0, harmonicity, normalized_cents, loudness,
                                                                                  **self.voicing)
         return out
+
+
+# ------------------------------------------------------------------------------------------------- timbre latent (MFCC -> z)
+# DESIGN.md section 10h.  The definition is restated in fp64 as plain loops in tests/mfcc_reference.py.
+
+MFCC_MAX_MELS = 128                      # csrc/ddsp_mfcc.hip: kMaxMels, kMaxMfcc
+MFCC_MAX_COEFFS = 64
+MFCC_FLOOR = 1e-5                        # -100 dB relative to a full-scale sine
+
+
+def hann_window(n_fft: int) -> torch.Tensor:
+    """Periodic Hann, 0.5 - 0.5 cos(2 pi n / n_fft), in fp64 and rounded to fp32 (what the kernel computes for itself)."""
+    n = np.arange(int(n_fft), dtype=np.float64)
+    return torch.from_numpy((0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft)).astype(np.float32))
+
+
+def _hz_to_mel(f):
+    return 2595.0 * np.log10(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+
+def mel_filterbank(n_fft: int, sample_rate: float, n_mels: int = 128, fmin: float = 20.0, fmax: float = 8000.0):
+    """HTK-mel triangles with slopes in the mel domain, built in fp64 and rounded to fp32: n_mels + 2 edges equally spaced in
+    mel between fmin and min(fmax, sample_rate / 2); bin 0 has weight 0.  -> (dense [n_mels, n_fft / 2 + 1] fp32,
+    band_start [n_mels] int32, band_count [n_mels] int32, band_w fp32: every band's contiguous run of non-zero weights, packed
+    band after band).  A band that covers no bin has count 0."""
+    bins = int(n_fft) // 2 + 1
+    top = min(float(fmax), float(sample_rate) / 2.0)
+    if not (0.0 <= float(fmin) < top):
+        raise ValueError(f"mel_filterbank: need 0 <= fmin < min(fmax, sample_rate / 2), got fmin = {fmin}, fmax = {fmax}, rate {sample_rate}")
+    edges = np.linspace(_hz_to_mel(fmin), _hz_to_mel(top), int(n_mels) + 2, dtype=np.float64)
+    mel_k = _hz_to_mel(np.arange(bins, dtype=np.float64) * float(sample_rate) / float(n_fft))
+    lo, ce, hi = edges[:-2, None], edges[1:-1, None], edges[2:, None]
+    dense64 = np.maximum(0.0, np.minimum((mel_k[None] - lo) / (ce - lo), (hi - mel_k[None]) / (hi - ce)))
+    dense64[:, 0] = 0.0
+    dense = dense64.astype(np.float32)
+    start = np.zeros(n_mels, dtype=np.int32)
+    count = np.zeros(n_mels, dtype=np.int32)
+    packed = []
+    for m in range(n_mels):
+        nz = np.nonzero(dense[m])[0]
+        if nz.size:
+            start[m], count[m] = nz[0], nz[-1] - nz[0] + 1
+            packed.append(dense[m, nz[0]:nz[-1] + 1])
+    band_w = np.concatenate(packed) if packed else np.zeros(0, dtype=np.float32)
+    if band_w.size == 0:
+        band_w = np.zeros(1, dtype=np.float32)           # (never read: every count is 0; keeps the pointer valid)
+    return torch.from_numpy(dense), torch.from_numpy(start), torch.from_numpy(count), torch.from_numpy(band_w.astype(np.float32))
+
+
+def dct_table(n_mels: int, n_mfcc: int) -> torch.Tensor:
+    """D[j, m] = sqrt(2 / n_mels) cos(pi j (m + 1/2) / n_mels) (tf.signal.mfccs_from_log_mel_spectrograms), fp32 from fp64."""
+    j = np.arange(int(n_mfcc), dtype=np.float64)[:, None]
+    m = np.arange(int(n_mels), dtype=np.float64)[None]
+    return torch.from_numpy((np.sqrt(2.0 / n_mels) * np.cos(np.pi * j * (m + 0.5) / n_mels)).astype(np.float32))
+
+
+def _check_mfcc_sizes(n_fft: int, hop: int, n_mels: int, n_mfcc: int) -> None:
+    if n_fft < 64 or n_fft > 2048 or n_fft & (n_fft - 1):
+        raise ValueError(f"mfcc: n_fft must be a power of two in 64 .. 2048, got {n_fft}")
+    if hop < 1:
+        raise ValueError(f"mfcc: hop must be positive, got {hop}")
+    if not (1 <= n_mfcc <= n_mels <= MFCC_MAX_MELS) or n_mfcc > MFCC_MAX_COEFFS:
+        raise ValueError(f"mfcc: need 1 <= n_mfcc <= n_mels <= {MFCC_MAX_MELS} and n_mfcc <= {MFCC_MAX_COEFFS}, "
+                         f"got n_mels = {n_mels}, n_mfcc = {n_mfcc}")
+
+
+def mfcc_tables(n_fft: int, sample_rate: float, n_mels: int = 128, n_mfcc: int = 30, fmin: float = 20.0, fmax: float = 8000.0) -> dict:
+    """Every table of the MFCC definition, on the CPU: window, scale (fp32(2 / sum window)), fbank (dense), band_start,
+    band_count, band_w, dct."""
+    window = hann_window(n_fft)
+    dense, start, count, band_w = mel_filterbank(n_fft, sample_rate, n_mels, fmin, fmax)
+    scale = float(np.float32(2.0 / window.double().sum().item()))
+    return dict(window=window, scale=scale, fbank=dense, band_start=start, band_count=count, band_w=band_w, dct=dct_table(n_mels, n_mfcc))
+
+
+_MFCC_TABLES = {}
+
+
+def _mfcc_tables_on(device, *key) -> dict:
+    full = key + (str(device),)
+    if full not in _MFCC_TABLES:
+        t = mfcc_tables(*key)
+        _MFCC_TABLES[full] = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in t.items()}
+    return _MFCC_TABLES[full]
+
+
+def _mfcc_run(x: torch.Tensor, t: dict, n_fft: int, hop: int, floor: float, return_logmel: bool):
+    """x [B, L] (detached) -> mfcc [B, F, n_mfcc] (and logmel [B, F, n_mels]) with the tables `t` on x's device."""
+    if x.dim() != 2:
+        raise ValueError(f"mfcc: audio must be [B, L], got {tuple(x.shape)}")
+    B, L = x.shape
+    if L < n_fft:
+        raise ValueError(f"audio of {L} samples is too short for one frame of n_fft = {n_fft}")
+    n_mfcc, n_mels = t['dct'].shape
+    Fr = 1 + (L - n_fft) // hop
+    x = x.detach()
+    if x.is_cuda:
+        x = x.contiguous().float()
+        out = torch.empty((B, Fr, n_mfcc), device=x.device, dtype=torch.float32)
+        logmel = torch.empty((B, Fr, n_mels), device=x.device, dtype=torch.float32) if return_logmel else None
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().ddsp_mfcc(x.data_ptr(), t['band_start'].data_ptr(), t['band_count'].data_ptr(), t['band_w'].data_ptr(),
+                                      t['dct'].data_ptr(), out.data_ptr(), None if logmel is None else logmel.data_ptr(), B, L,
+                                      n_fft, hop, n_mels, n_mfcc, t['scale'], float(floor), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_mfcc")
+        return (out, logmel) if return_logmel else out
+    out, logmel = mfcc_torch(x.float(), t, n_fft, hop, floor)
+    return (out, logmel) if return_logmel else out
+
+
+def mfcc_torch(x: torch.Tensor, t: dict, n_fft: int, hop: int, floor: float = MFCC_FLOOR):
+    """The MFCC definition as fp32 torch operations on x's device (the CPU path; tools/bench_mfcc.py times it on the GPU):
+    framing, window, torch.fft.rfft, magnitude, the dense filterbank and the DCT as two matmuls.  -> (mfcc, logmel)."""
+    with torch.no_grad():
+        frames = x.unfold(-1, n_fft, hop) * t['window']
+        dead = ~torch.isfinite(frames).all(dim=-1, keepdim=True)
+        spec = torch.fft.rfft(torch.where(dead, torch.zeros((), dtype=frames.dtype, device=frames.device), frames))
+        mel = torch.matmul(spec.abs() * t['scale'], t['fbank'].t())
+        logmel = torch.log(mel + floor)
+        out = torch.matmul(logmel, t['dct'].t())
+        nan = torch.full((), float('nan'), dtype=out.dtype, device=out.device)
+        return torch.where(dead, nan, out), torch.where(dead, nan, logmel)
+
+
+def mfcc(x: torch.Tensor, n_fft: int, hop: int, sample_rate: float, n_mels: int = 128, n_mfcc: int = 30, fmin: float = 20.0,
+         fmax: float = 8000.0, floor: float = MFCC_FLOOR, return_logmel: bool = False):
+    """Mel-frequency cepstral coefficients of x [B, L] fp32 -> [B, F, n_mfcc] fp32, F = (L - n_fft) // hop + 1 (and, with
+    return_logmel, the log-mel spectrogram [B, F, n_mels] as well).  Frame f is x[f hop : f hop + n_fft) as in LoudnessEncoder,
+    under a periodic Hann window; magnitudes are scaled by 2 / sum(window), so that a full-scale sine reads 1 and `floor` is
+    a level relative to full scale; HTK-mel triangles between fmin and min(fmax, sample_rate / 2); natural log; the DCT-II of
+    tf.signal.mfccs_from_log_mel_spectrograms.  n_fft a power of two in 64 .. 2048, 1 <= n_mfcc <= n_mels <= 128, n_mfcc <= 64.
+    A frame holding a NaN or an infinite sample is NaN; no other frame is affected.
+
+    CUDA tensors run one HIP launch (ddsp_mfcc); CPU tensors the same definition as fp32 torch operations.  No gradient flows
+    to x: the input is detached."""
+    n_fft, hop, n_mels, n_mfcc = int(n_fft), int(hop), int(n_mels), int(n_mfcc)
+    _check_mfcc_sizes(n_fft, hop, n_mels, n_mfcc)
+    t = _mfcc_tables_on(x.device, n_fft, float(sample_rate), n_mels, n_mfcc, float(fmin), float(fmax))
+    return _mfcc_run(x, t, n_fft, hop, floor, return_logmel)
+
+
+class MFCC(nn.Module):
+    """`mfcc` with its tables held as buffers (non-persistent: state dicts do not grow).  Reads conf.n_fft, conf.hop_length,
+    conf.sample_rate and, where present, z_mels (128), z_mfcc (30), z_fmin (20.0), z_fmax (8000.0).  forward(audio [B, L]) ->
+    [B, F, n_mfcc] on LoudnessEncoder's frame grid; the audio is detached (no gradient flows to it)."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.n_fft, self.hop_length, self.sample_rate = int(conf.n_fft), int(conf.hop_length), conf.sample_rate
+        self.n_mels, self.n_mfcc = int(getattr(conf, 'z_mels', 128)), int(getattr(conf, 'z_mfcc', 30))
+        self.fmin, self.fmax = float(getattr(conf, 'z_fmin', 20.0)), float(getattr(conf, 'z_fmax', 8000.0))
+        self.floor = MFCC_FLOOR
+        _check_mfcc_sizes(self.n_fft, self.hop_length, self.n_mels, self.n_mfcc)
+        t = mfcc_tables(self.n_fft, float(self.sample_rate), self.n_mels, self.n_mfcc, self.fmin, self.fmax)
+        self.scale = t.pop('scale')
+        for name, value in t.items():
+            self.register_buffer(name, value, persistent=False)
+
+    def tables(self) -> dict:
+        return dict(window=self.window, scale=self.scale, fbank=self.fbank, band_start=self.band_start, band_count=self.band_count,
+                    band_w=self.band_w, dct=self.dct)
+
+    def forward(self, audio: torch.Tensor, return_logmel: bool = False):
+        return _mfcc_run(audio, self.tables(), self.n_fft, self.hop_length, self.floor, return_logmel)
+
+
+class ZEncoder(nn.Module):
+    """The timbre latent of the DDSP autoencoder: MFCC -> LayerNorm(n_mfcc) -> GRU(n_mfcc, z_gru_units) -> Linear(z_gru_units, z_dims).
+    The normalisation is per frame (the original's instance norm runs over time, which has no causal form; this one runs live
+    on a one-block window).  conf.z_dims > 0; conf.z_gru_units defaults to 512; the MFCC options are `MFCC`'s.
+
+      forward(audio [B, T hop])          the clip as the dataset stores it, padded (p // 2, p - p // 2) with p = n_fft - hop as
+                                         AutoEncoder.forward pads it -> z [B, T, z_dims]
+      forward(audio, padded=True)        the audio is padded already
+      live(window [B, L], state)         a block whose frames are the window's own (no padding) -> (z, new GRU state)
+
+    Gradients reach the module's parameters, not the audio."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.z_dims = int(getattr(conf, 'z_dims', 0) or 0)
+        if self.z_dims <= 0:
+            raise ValueError("ZEncoder needs conf.z_dims > 0")
+        units = int(getattr(conf, 'z_gru_units', 512))
+        self.padding = int(conf.n_fft) - int(conf.hop_length)
+        self.mfcc = MFCC(conf)
+        self.norm = nn.LayerNorm(self.mfcc.n_mfcc)
+        self.gru = GRU(self.mfcc.n_mfcc, units, batch_first=True)
+        self.out = nn.Linear(units, self.z_dims)
+
+    def _encode(self, audio: torch.Tensor, state):
+        h = self.norm(self.mfcc(audio))
+        h, state = self.gru(h) if state is None else self.gru(h, state)
+        return dense.linear(h, self.out.weight, self.out.bias), state
+
+    def forward(self, audio: torch.Tensor, padded: bool = False) -> torch.Tensor:
+        if not padded:
+            audio = F.pad(audio, (self.padding // 2, self.padding - self.padding // 2))
+        return self._encode(audio, None)[0]
+
+    def live(self, window: torch.Tensor, state=None):
+        return self._encode(window, state)

@@ -20,9 +20,16 @@ from .filtered_noise import FilteredNoise, noise_forward, noise_ola_stream, ola_
 from .harmonic_oscillator import osc_forward
 
 
+_NO_LATENT = ("{what}: the timbre latent (conf.z_dims > 0) is not wired into the graphed live objects -- the z-encoder's GRU state "
+              "would have to be carried by the graph; run AutoEncoder.forward_live / Decoder.forward_live, which carry "
+              "(decoder_hidden, z_hidden), or build the decoder without z_dims")
+
+
 class GraphedSynth:
     def __init__(self, conf, batch: int, frames: int, n_noise_filters: int, device="cuda", live: bool = False,
                  noise_seed: int = 0, delayed: bool = False):
+        if live and int(getattr(conf, 'z_dims', 0) or 0) > 0:
+            raise ValueError(_NO_LATENT.format(what="GraphedSynth(live=True)"))
         self.hop, self.sample_rate, self.live = conf.hop_length, conf.sample_rate, live
         dev = torch.device(device)
         H = conf.n_harmonics
@@ -111,6 +118,8 @@ class GraphedLiveDecoder:
     """
 
     def __init__(self, decoder, frames: int, noise_seed: int = 0, carry_hidden: bool = False, delayed: bool = False):
+        if getattr(decoder, 'z_dims', 0) > 0:
+            raise ValueError(_NO_LATENT.format(what="GraphedLiveDecoder"))
         decoder.check_live(delayed, "GraphedLiveDecoder")
         self.dec = decoder.eval()
         dev = next(decoder.parameters()).device

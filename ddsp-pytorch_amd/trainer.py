@@ -411,7 +411,8 @@ class Trainer:
         the trainer's autocast.  Draws noise from the model's current offset like any eager forward."""
         b = self.batches
         idx = b.permutation(self.epoch)[i_batch * b.batch_size:(i_batch + 1) * b.batch_size].to(self.device)
-        z = {k: b.data[k].index_select(0, idx) for k in KEYS[:3]}
+        keys = KEYS if getattr(self.model, 'z_dims', 0) > 0 else KEYS[:3]      # a timbre latent is computed from the audio
+        z = {k: b.data[k].index_select(0, idx) for k in keys}
         with torch.no_grad(), torch.autocast('cuda', dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None):
             return self.model(z).float()
 

@@ -840,6 +840,25 @@ int ddsp_loudness_supported(int n_fft);
 int ddsp_loudness(const float *x, const double *a_weight, float *out, long B, long L, int n_fft, int hop, void *stream);
 
 /*
+ * MFCC front end of the timbre encoder: x [B, L] fp32 -> mfcc [B, F, n_mfcc] and, where `logmel` is not
+ * NULL, logmel [B, F, n_mels], F = 1 + (L - n_fft) / hop, in ONE launch.
+ *   frame f   = x[f hop .. f hop + n_fft), times the periodic Hann window 0.5 - 0.5 cos(2 pi n / n_fft) (fp64, rounded to fp32)
+ *   A[k]      = |FFT(frame)[k]| * scale, k = 0 .. n_fft / 2     (the caller passes scale = 2 / sum of the window)
+ *   mel[m]    = sum_i band_w[o_m + i] * A[band_start[m] + i], i = 0 .. band_count[m] - 1 ascending; o_m = the sum of the counts
+ *               of the bands before m (the weights are packed band after band); an empty band is legal
+ *   logmel[m] = log(mel[m] + floor), the natural logarithm in fp32; a band whose sum is exactly 0 reads fl32(log(floor))
+ *   mfcc[j]   = sum_m dct[j n_mels + m] * logmel[m], m ascending
+ * A frame with a NaN or an infinite sample is NaN in both outputs and touches no other frame; an all-zero frame has
+ * logmel = log(floor) in every band.  A frame's values do not depend on the rest of the batch or on the grid.  band_start and
+ * band_count are clamped to the frame's bins when read; band_w must hold the sum of the counts.
+ * DDSP_EINVAL: a null pointer (logmel excepted), n_fft not a power of two in 64 .. 2048, hop < 1, L < n_fft with B > 0,
+ * n_mels outside 1 .. 128, n_mfcc outside 1 .. min(n_mels, 64), B < 0.  B = 0 with valid sizes returns 0 without a launch.
+ * Nothing is launched before these checks.  No allocation and no host synchronisation: the call can be captured in a graph.
+ */
+int ddsp_mfcc(const float *x, const int *band_start, const int *band_count, const float *band_w, const float *dct, float *mfcc,
+              float *logmel, long B, long L, int n_fft, int hop, int n_mels, int n_mfcc, float scale, float floor, void *stream);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
