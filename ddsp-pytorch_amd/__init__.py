@@ -24,6 +24,8 @@ from . import tuning  # noqa: F401
 from .tuning import TuningStatistics, tuning_statistics, tune_pitch  # noqa: F401
 from . import notes  # noqa: F401
 from .notes import Expression, Notes, extract_notes, note_expression, render_notes  # noqa: F401
+from . import voices  # noqa: F401
+from .voices import allocate_voices, mix_voices  # noqa: F401
 from . import analysis  # noqa: F401
 from .analysis import HarmonicAnalyzer, harmonic_analysis, harmonic_resynthesis, harmonic_residual, refine_f0  # noqa: F401
 from .analysis import NoiseAnalyzer, noise_analysis  # noqa: F401
@@ -45,4 +47,4 @@ __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "
            "analysis", "HarmonicAnalyzer", "harmonic_analysis", "harmonic_resynthesis", "harmonic_residual", "refine_f0", "NoiseAnalyzer", "noise_analysis",
            "ControlTransform", "transform_controls", "ControlMorph", "morph_controls", "ControlAlign", "align_controls", "control_features", "dtw_align",
            "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
-           "latest_checkpoint", "mfcc", "MFCC", "ZEncoder"]
+           "latest_checkpoint", "mfcc", "MFCC", "ZEncoder", "voices", "allocate_voices", "mix_voices"]

@@ -134,6 +134,8 @@ SIGNATURES = {
     "ddsp_loudness_supported": (_i32, [_i32]),
     "ddsp_loudness": (_i32, [_vp] * 3 + [_long, _long, _i32, _i32, _vp]),
     "ddsp_mfcc": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
+    "ddsp_voices_allocate": (_i32, [_vp] * 16 + [_long, _long, _i32, _long, _i32, _i32, _long, _vp]),
+    "ddsp_voices_mix": (_i32, [_vp] * 4 + [_long, _i32, _i32, _long, _long, _long, _long, _long, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
     "ddsp_griffinlim_supported": (_i32, [_i32]),

@@ -20,8 +20,10 @@
                              the decoder's training set)
   transcribe(x, **extract_options)
                              the encoder followed by notes.extract_notes: the clip's note events (notes.Notes)
-  play(notes, frames=None, target=None, **render_options)
-                             notes.render_notes, fit_conditioning where a target is given, the decoder: a score -> audio
+  play(notes, frames=None, target=None, voices=None, **render_options)
+                             notes.render_notes, fit_conditioning where a target is given, the decoder: a score -> audio;
+                             voices=V plays chords: voices.allocate_voices in front, the B V rows as one batch, voices.mix_voices
+                             behind
   forward_live(x, hidden, delayed=False, conditioning=None)
                              the real-time callback of rt/synth.py:40-55: a numpy window (4096 samples by default) -> one H2D
                              copy, hop // 2 samples dropped at the front and hop - hop // 2 at the back (autoencoder.py:26-32),
@@ -48,7 +50,8 @@ import torch.nn.functional as F
 
 from .conditioning import fit_conditioning
 from .tuning import tune_pitch
-from .notes import extract_notes, note_expression, render_notes
+from .notes import Expression, extract_notes, note_expression, render_notes
+from .voices import allocate_voices, mix_voices
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
@@ -127,23 +130,63 @@ class AutoEncoder(nn.Module):
         found = extract_notes(z, **extract_options)
         return (found, note_expression(z, found)) if expression else found
 
-    def play(self, notes, frames=None, target=None, timbre=None, **render_options) -> torch.Tensor:
+    def play(self, notes, frames=None, target=None, timbre=None, voices=None, voice_options=None, mix_options=None,
+             **render_options) -> torch.Tensor:
         """notes.Notes -> audio [B, frames hop]: notes.render_notes (and its options, `expression`, `source`, `bend_amount`,
         `dynamics_amount`, `keep_attack` and `keep_release` among them) at the decoder's sample rate and hop, then
         `fit_conditioning(z, target)` where a ConditioningStatistics `target` is given (the decoder's training set: the score's
         register and levels brought into its range), then the decoder's ordinary forward.  frames=None takes the end of the last
         note (that reads the notes back from the device).  `timbre` (a clip or a latent, see the module docstring) is required
-        when the decoder has a timbre latent: a score has no audio to take it from."""
+        when the decoder has a timbre latent: a score has no audio to take it from.
+
+        voices=V plays a score whose notes overlap: voices.allocate_voices (with `voice_options`) gives
+        each of V monophonic voices its notes, the B V rows go through the steps above as one batch -- `expression` and `timbre`
+        repeated per voice, every voice note finding its curve through the allocation's `index` -- and voices.mix_voices (with
+        `mix_options`: gain, pan, hold, fade; gate=True passes the render's `voiced` as the gate) sums them: [B, frames hop], or
+        [B, 2, frames hop] with a pan.  voices=None is the monophonic call as it always was."""
         if render_options.get('return_info'):
             raise ValueError("play returns audio; ask render_notes itself for the info")
+        if voices is None and (voice_options is not None or mix_options is not None):
+            raise ValueError("play: voice_options and mix_options belong to voices=V")
         if frames is None:
             used = notes._used()
             ends = torch.where(used, notes.onset.to(torch.int64) + notes.frames, torch.zeros_like(notes.onset, dtype=torch.int64))
             frames = max(int(ends.max()) if ends.numel() else 0, 1)
+        if voices is not None:
+            return self._play_voices(notes, frames, target, timbre, voices, dict(voice_options or {}), dict(mix_options or {}),
+                                     render_options)
         z = render_notes(notes, frames, self.decoder.harmonics.sample_rate, self.hop_length, **render_options)
         if target is not None:
             z = fit_conditioning(z, target)
         return self.decoder(self._with_timbre(dict(z), None, timbre, "play"))
+
+    def _play_voices(self, notes, frames, target, timbre, voices, voice_options, mix_options, render_options):
+        """play(voices=V): allocate, render and decode the B V voice rows as one batch, mix"""
+        if voice_options.pop('return_info', False) or 'out' in mix_options:
+            raise ValueError("play returns audio; ask allocate_voices and mix_voices themselves for their info and `out`")
+        rows, info = allocate_voices(notes, voices, return_info=True, **voice_options)
+        V = rows.rows // notes.rows
+        render_options = dict(render_options)
+        e = render_options.get('expression')
+        if isinstance(e, Expression):
+            if e.rows != notes.rows:
+                raise ValueError(f"play: the expression has {e.rows} rows, the notes {notes.rows}")
+            per_voice = lambda x: None if x is None else x.repeat_interleave(V, dim=0)     # noqa: E731
+            render_options['expression'] = Expression(**{k: per_voice(x) for k, x in e._tensors().items()})
+            index, given = info['index'], render_options.get('source')
+            if given is not None:                                               # the caller's map first: voice note -> note -> curve
+                given = per_voice(torch.as_tensor(given, dtype=torch.int32, device=notes.device).reshape(notes.rows, notes.max_notes))
+                index = torch.where(index >= 0, torch.gather(given, 1, index.clamp(min=0).long()), index)
+            render_options['source'] = index
+        z = render_notes(rows, frames, self.decoder.harmonics.sample_rate, self.hop_length, **render_options)
+        active = z['voiced'] if mix_options.pop('gate', False) else None
+        if target is not None:
+            z = fit_conditioning(z, target)
+        if timbre is not None:
+            timbre = self._timbre(timbre, frames, "play").repeat_interleave(V, dim=0)
+        audio = self.decoder(self._with_timbre(dict(z), None, timbre, "play"))
+        return mix_voices(audio.detach(), V, active=active, hop_length=self.hop_length if active is not None else None,     # (no backward)
+                          **mix_options)
 
     def analyse(self, x: torch.Tensor, return_complex: bool = False, noise=False, average: int = 1, iterations=None,
                 refine: int = 0) -> dict:

@@ -210,10 +210,11 @@ class Notes:
         return self
 
     # ------------------------------------------------------------------------------------------------- standard MIDI files
-    def write_midi(self, path, hop_length: int, sample_rate: int, level_range=(0.0, 1.0), row: int = 0) -> None:
+    def write_midi(self, path, hop_length: int, sample_rate: int, level_range=(0.0, 1.0), row: int = 0, polyphonic: bool = False) -> None:
         """Row `row` as a standard MIDI file, format 0: one track, 480 ticks per quarter at 120 quarters a minute, velocity
         clamp(round(127 (level - lo) / (hi - lo)), 1, 127) (64 for a NaN level).  A later note cuts an earlier one off, as in
-        render_notes; detune is not written.  Host only."""
+        render_notes; polyphonic=True writes every note at its full length instead (a chord stays a chord; DESIGN.md section
+        10i).  detune is not written.  Host only."""
         lo, hi = float(level_range[0]), float(level_range[1])
         if not hi > lo:
             raise ValueError(f"write_midi: level_range must be (lo, hi) with hi > lo, got {level_range!r}")
@@ -223,7 +224,7 @@ class Notes:
         tick = lambda f: int(round(Fraction(f * int(hop_length) * 2 * TICKS_PER_QUARTER, int(sample_rate))))       # noqa: E731
         events = []                                                             # (tick, 0: off / 1: on, note, velocity)
         for i in range(n):
-            length = frames[i] if i + 1 >= n else min(frames[i], onset[i + 1] - onset[i])
+            length = frames[i] if polyphonic or i + 1 >= n else min(frames[i], onset[i + 1] - onset[i])
             if length < 1 or not 0 <= pitch[i] <= 127 or onset[i] < 0:
                 continue
             velocity = 64 if level[i] != level[i] else min(max(int(round(127.0 * (level[i] - lo) / (hi - lo))), 1), 127)
@@ -239,10 +240,12 @@ class Notes:
             f.write(b"MThd" + struct.pack(">IHHH", 6, 0, 1, TICKS_PER_QUARTER) + b"MTrk" + struct.pack(">I", len(track)) + bytes(track))
 
     @classmethod
-    def read_midi(cls, path, hop_length: int, sample_rate: int, level_range=(0.0, 1.0)) -> "Notes":
+    def read_midi(cls, path, hop_length: int, sample_rate: int, level_range=(0.0, 1.0), polyphonic: bool = False) -> "Notes":
         """A standard MIDI file (format 0, or 1 with its tracks merged) -> one row of Notes on the chromatic scale.  Running
         status and every set-tempo event are honoured, a note-on with velocity 0 is a note-off, a new note-on cuts the sounding
-        note (the instrument is monophonic), everything else is ignored.  Files with SMPTE time division are refused."""
+        note (the instrument is monophonic), everything else is ignored.  Files with SMPTE time division are refused.
+        polyphonic=True keeps chords: a note-on cuts nothing and a note-off closes the oldest open note of
+        its own pitch; the notes come out in order of onset, and of pitch within one onset -- what voices.allocate_voices takes."""
         lo, hi = float(level_range[0]), float(level_range[1])
         with open(path, "rb") as f:
             data = f.read()
@@ -250,6 +253,7 @@ class Notes:
         events.sort(key=lambda e: (e[0], e[1]))                                 # by tick; tempo, then note-offs, then note-ons
         tempo, at_tick, at_us = TEMPO, 0, Fraction(0)
         notes, sounding = [], None                                              # sounding: (onset frame, note, velocity)
+        held = {}                                                               # polyphonic: note -> [(onset frame, velocity)], oldest first
 
         def close(frame):
             if sounding is not None and frame > sounding[0]:
@@ -262,12 +266,22 @@ class Notes:
                 tempo = a
                 continue
             frame = int(round(at_us * int(sample_rate) / (1000000 * int(hop_length))))
+            if polyphonic:
+                if kind == 2:
+                    held.setdefault(a, []).append((frame, b))
+                elif held.get(a):
+                    began, velocity = held[a].pop(0)
+                    if frame > began:
+                        notes.append((began, frame - began, a, velocity))
+                continue
             if kind == 2:
                 close(frame)
                 sounding = (frame, a, b)
             elif sounding is not None and sounding[1] == a:
                 close(frame)
                 sounding = None
+        if polyphonic:
+            notes.sort(key=lambda x: (x[0], x[2]))
         return cls(onset=[x[0] for x in notes], frames=[x[1] for x in notes], pitch=[x[2] for x in notes],
                    level=[lo + x[3] * (hi - lo) / 127.0 for x in notes], scale="chromatic")
 

@@ -859,6 +859,70 @@ int ddsp_mfcc(const float *x, const int *band_start, const int *band_count, cons
               float *logmel, long B, long L, int n_fft, int hop, int n_mels, int n_mfcc, float scale, float floor, void *stream);
 
 /*
+ * Polyphony: a score whose notes overlap is played by V monophonic voices, each a row of the batch that
+ * ddsp_notes_render and the decoder already handle, and the B V rows of audio are summed back to B.  Declared here, ahead of the
+ * notes they work on (below), whose record conventions they share.
+ *
+ * ddsp_voices_allocate: the five record arrays [B, N] and count [B] of ddsp_notes_extract -> the same five arrays as [B V, Nv]
+ * (row b V + v is voice v of score b), v_count [B V], index [B V, Nv] (the source slot of each voice note), voice and slot [B, N]
+ * (where each source note went) and stats [B, 2] (notes stolen, notes dropped), all int32 but the levels.  Per row, all in integer
+ * arithmetic, for the notes i = 0 .. min(count, N) - 1 (a negative count is 0) in slot order; onsets are expected non-decreasing:
+ *   1. A note with frames_i < 1, onset_i < 0, a pitch outside 0 .. 127 or |detune_i| > 2^30 sounds nowhere in ddsp_notes_render:
+ *      voice_i = slot_i = -1 and nothing else changes.
+ *   2. Voice v carries until_v (int64: onset + frames of its last note; -2^31 before its first), last_onset_v, last_pitch_v and
+ *      last_level_v (of that note), and count_v.
+ *   3. Voice v is free for note i iff until_v + gap <= onset_i.  Among the free voices the smallest key wins; a key is an int64
+ *      k 64 + v, so that a tie goes to the lowest voice:  assign = DDSP_VOICES_LOWEST: k = 0;  DDSP_VOICES_OLDEST (round robin):
+ *      k = until_v + 2^31;  DDSP_VOICES_NEAREST (a line stays in its voice, a re-struck pitch returns to it):
+ *      k = |pitch_i - last_pitch_v|, 128 for a voice without a note yet.
+ *   4. With no voice free (every voice then has a note):  steal = DDSP_VOICES_STEAL_OLDEST: the smallest key
+ *      last_onset_v 64 + v;  DDSP_VOICES_STEAL_QUIETEST: the smallest key u(last_level_v) 64 + v, u the uint32 that orders fp32
+ *      values (bits with the sign bit set where the sign is clear, all bits inverted where it is set), 0xFFFFFFFF for a NaN -- a
+ *      note without a level is never the quietest;  DDSP_VOICES_DROP: voice_i = slot_i = -1, stats[b][1] grows, nothing else
+ *      changes.  A steal shortens the stolen note in its voice row (where that note was written) to
+ *      max(0, min(its frames, onset_i - last_onset_v)) frames, which may be 0, and stats[b][0] grows.
+ *   5. The note goes to its voice's row at slot_i = count_v, every field copied, index = i; count_v grows by one, and the
+ *      voice's until, last_onset, last_pitch and last_level become the note's.  Past Nv count_v still counts and nothing is
+ *      written (ddsp_notes_extract's overflow rule); voice_i is the voice and slot_i = -1.
+ *   6. Voice slots from min(count_v, Nv) on are filled: onset -1, frames 0, pitch INT32_MIN, detune 0, level NaN, index -1;
+ *      voice and slot from min(count, N) on are -1.
+ *   One wavefront per row (the lanes are the voices), a wave-wide minimum per note; a capped grid strides over the rows.
+ *   DDSP_EINVAL: B, N or Nv < 0, V outside 1 .. 64, assign or steal outside 0 .. 2, gap outside 0 .. 2^24 - 1; then B = 0 returns
+ *   0; then a missing count, v_count or stats, a missing source array, voice or slot with N > 0, a missing voice array or index
+ *   with Nv > 0.  DDSP_ERANGE: B N >= 2^31 or B V Nv >= 2^31.
+ *
+ * ddsp_voices_mix: audio fp32 [B V, L], gains fp32 [B, V, C] (C = 1 or 2) and, where not NULL, active bytes [B V, T] (a frame is
+ * active where its byte is not 0: ddsp_notes_render's `voiced`) -> out fp32 [B, C, L]:
+ *      out[b, c, n] = sum over v ascending of (gains[b, v, c] g_v(n)) audio[b V + v, n], products and sums rounded to fp32, no
+ *      fused multiply-add; the sum starts from voice 0's term (V = 1 with a gain of 1 and no gate copies the bits).
+ *   Without `active` g = 1 and is not multiplied in.  With it, d_v(t) = the frames since row b V + v's last active frame at or
+ *   before t, e(t) = 1 where d <= hold, max(0, (fade - (d - hold)) / fade) beyond (0 where there is no such frame; fade = 0: a
+ *   hard gate), and g(n) = e(t) + (e(min(t + 1, T - 1)) - e(t)) (n mod hop) / hop with t = min(n / hop, T - 1).  The kernel forms
+ *   it without cancellation: with F = max(fade, 1) and the integers a = F e(t), a' = F e(min(t + 1, T - 1)), r = n mod hop,
+ *   g =fl32(a (hop - r) + a' r) * fl32(1 / fl32(F hop)), and exactly 1 where the numerator equals F hop: at most
+ *   four roundings, six with the two products, V - 1 more in the sum.
+ *   A workgroup per tile of up to 1024 samples of one score, 16-byte loads and stores where L is a multiple of 4 and audio and out
+ *   are 16-byte aligned (4-byte ones otherwise, and in a tile's last partial group); the look-back for d is hold + fade frames at
+ *   most.  One launch, no workspace.
+ *   DDSP_EINVAL: B < 0, V outside 1 .. 64, C other than 1 or 2, L < 1, hold or fade negative or hold + fade >= 2^16, with `active`
+ *   T < 1 or hop < 1; then B = 0 returns 0; then a missing audio, gains or out.  DDSP_ERANGE: L >= 2^31, with `active` hop > 2^15
+ *   or T >= 2^31, B times a row's tiles (of 1024 samples; of 32 hop with `active` and hop < 32) >= 2^31, B V L or B V T >= 2^47.
+ * Both: nothing is launched before these checks; no allocation, no host synchronisation; no output may alias an input.
+ */
+#define DDSP_VOICES_LOWEST 0
+#define DDSP_VOICES_OLDEST 1
+#define DDSP_VOICES_NEAREST 2
+#define DDSP_VOICES_STEAL_OLDEST 0
+#define DDSP_VOICES_STEAL_QUIETEST 1
+#define DDSP_VOICES_DROP 2
+int ddsp_voices_allocate(const int *onset, const int *frames, const int *pitch, const int *detune, const float *level,
+                         const int *count, int *v_onset, int *v_frames, int *v_pitch, int *v_detune, float *v_level, int *v_count,
+                         int *index, int *voice, int *slot, int *stats, long B, long N, int V, long Nv, int assign, int steal,
+                         long gap, void *stream);
+int ddsp_voices_mix(const float *audio, const float *gains, const uint8_t *active, float *out, long B, int V, int C, long L, long T,
+                    long hop, long hold, long fade, void *stream);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
