@@ -136,6 +136,14 @@ SIGNATURES = {
     "ddsp_mfcc": (_i32, [_vp] * 7 + [_long, _long, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
     "ddsp_voices_allocate": (_i32, [_vp] * 16 + [_long, _long, _i32, _long, _i32, _i32, _long, _vp]),
     "ddsp_voices_mix": (_i32, [_vp] * 4 + [_long, _i32, _i32, _long, _long, _long, _long, _long, _vp]),
+    "ddsp_wavetable_supported": (_i32, [_i32, _i32]),
+    "ddsp_wavetable_form": (_i32, [_i32] * 5),
+    "ddsp_wavetable_scratch_bytes": (_size, [_i32] * 5),
+    "ddsp_wavetable_forward": (_i32, [_vp] * 7 + [_i32] * 6 + [_vp]),
+    "ddsp_wavetable_backward_scratch_bytes": (_size, [_i32] * 5),
+    "ddsp_wavetable_backward": (_i32, [_vp] * 10 + [_i32] * 6 + [_vp]),
+    "ddsp_wavetable_set_form": (_i32, [_i32]),
+    "ddsp_wavetable_set_grid": (_i32, [_i32]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
     "ddsp_griffinlim_supported": (_i32, [_i32]),

@@ -55,13 +55,15 @@ from .voices import allocate_voices, mix_voices
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
+from .wavetable import refuse_wavetable
 
 
 class AutoEncoder(nn.Module):
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None, noise_overlap_add=None):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None, noise_overlap_add=None,
+                 synth=None):
         super().__init__()
         self.encoder = Encoder(conf, weights, voicing=voicing, tracker=tracker)
-        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed, noise_overlap_add=noise_overlap_add)
+        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed, noise_overlap_add=noise_overlap_add, synth=synth)
         self.padding = conf.n_fft - conf.hop_length
         self.hop_length = conf.hop_length
         self.n_noise_filters = conf.n_noise_filters
@@ -202,6 +204,7 @@ class AutoEncoder(nn.Module):
 
         refine=N runs N steps of analysis.refine_f0 on the encoder's track before the analysis (a decoded track is a bin centre,
         up to 10 cents off); the dict's f0 is then the refined track.  refine=0 is the analysis along the encoder's own track."""
+        refuse_wavetable(self.decoder, "analyse")
         if noise not in (False, True, 'truncated', 'overlap_add'):
             raise ValueError(f"analyse: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
         overlap_add = noise == 'overlap_add'
@@ -234,6 +237,7 @@ class AutoEncoder(nn.Module):
         `formant` -- 0 keeps the formants in place, None lets them follow the pitch -- and `positions`), then
         `decoder.synthesize`, and `decoder.reverb` only when asked.  noise follows analyse's rules (True / 'truncated' /
         'overlap_add' must be the decoder's noise form); noise=False plays the harmonics alone (`decoder.harmonics`)."""
+        refuse_wavetable(self.decoder, "transform")
         ctrl = transform_controls(self.analyse(x, noise=noise, refine=refine), self.decoder.harmonics.sample_rate, stretch=stretch,
                                   transpose=transpose, formant=formant, positions=positions)
         with torch.no_grad():
@@ -250,6 +254,7 @@ class AutoEncoder(nn.Module):
         harmonics alone (`decoder.harmonics`).  align=True finds the two positions by analysis.align_controls (dynamic time warping
         of the two analysed dicts; `timing`, 0 is x's clock and 1 is y's, `radius`, `penalty`; `frames` is then the timeline's T')
         instead of stretching both clips linearly; positions_a / positions_b must then be left out."""
+        refuse_wavetable(self.decoder, "morph")
         if align and (positions_a is not None or positions_b is not None):
             raise ValueError("morph: align=True finds positions_a and positions_b; give one or the other")
         ctrl_x, ctrl_y = self.analyse(x, noise=noise, refine=refine), self.analyse(y, noise=noise, refine=refine)

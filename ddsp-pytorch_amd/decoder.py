@@ -26,6 +26,7 @@ from .filtered_noise import FilteredNoise
 from .gru import GRU
 from .harmonic_oscillator import OscillatorBank
 from .reverb import Reverb
+from .wavetable import WavetableBank
 
 
 def _dense_stack(n_in: int, width: int, depth: int) -> nn.Module:
@@ -317,7 +318,7 @@ class _Heads(torch.autograd.Function):
 class Controller(nn.Module):
     """f0 / loudness features -> control dict {f0, c, a, H, hidden} (decoder.py:41-108)."""
 
-    def __init__(self, conf):
+    def __init__(self, conf, n_controls=None):
         super().__init__()
         width, depth = conf.decoder_mlp_units, conf.decoder_mlp_layers
         self.mlp_f0 = _dense_stack(1, width, depth)
@@ -329,7 +330,7 @@ class Controller(nn.Module):
             n_stacks = 3
         self.gru = GRU(n_stacks * width, conf.decoder_gru_units, conf.decoder_gru_layers, batch_first=True)
         self.mlp_gru = _dense_stack(conf.decoder_gru_units + n_stacks * width, width, depth)
-        self.dense_harmonic = nn.Linear(width, conf.n_harmonics)
+        self.dense_harmonic = nn.Linear(width, conf.n_harmonics if n_controls is None else n_controls)
         self.dense_loudness = nn.Linear(width, 1)
         self.dense_filter = nn.Linear(width, conf.n_noise_filters)
 
@@ -368,10 +369,19 @@ class Controller(nn.Module):
 class Decoder(nn.Module):
     """controller -> harmonics + noise -> reverb (decoder.py:119-147), all on the device."""
 
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None, synth=None):
         super().__init__()
-        self.controller = Controller(conf)
-        self.harmonics = OscillatorBank(conf)
+        synth = synth if synth is not None else (getattr(conf, 'synth', None) or 'harmonic')
+        if synth not in ('harmonic', 'wavetable'):
+            raise ValueError(f"Decoder: synth must be 'harmonic' or 'wavetable', got {synth!r}")
+        self.synth = synth
+        if synth == 'wavetable':
+            # the second tonal synthesiser (wavetable.py): `c` mixes its N learnable tables instead of weighting harmonics
+            self.harmonics = WavetableBank(conf)
+            self.controller = Controller(conf, n_controls=self.harmonics.n_wavetables)
+        else:
+            self.controller = Controller(conf)
+            self.harmonics = OscillatorBank(conf)
         self.noise = FilteredNoise(conf, rng=noise_rng, seed=seed, overlap_add=noise_overlap_add)
         self.reverb = Reverb(conf)
         self.z_dims = self.controller.z_dims

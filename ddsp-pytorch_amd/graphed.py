@@ -18,6 +18,7 @@ from . import _lib
 from . import dense
 from .filtered_noise import FilteredNoise, noise_forward, noise_ola_stream, ola_stream_state
 from .harmonic_oscillator import osc_forward
+from .wavetable import refuse_wavetable
 
 
 _NO_LATENT = ("{what}: the timbre latent (conf.z_dims > 0) is not wired into the graphed live objects -- the z-encoder's GRU state "
@@ -30,6 +31,8 @@ class GraphedSynth:
                  noise_seed: int = 0, delayed: bool = False):
         if live and int(getattr(conf, 'z_dims', 0) or 0) > 0:
             raise ValueError(_NO_LATENT.format(what="GraphedSynth(live=True)"))
+        if live:
+            refuse_wavetable((getattr(conf, 'synth', None) or 'harmonic') == 'wavetable', "GraphedSynth(live=True)")
         self.hop, self.sample_rate, self.live = conf.hop_length, conf.sample_rate, live
         dev = torch.device(device)
         H = conf.n_harmonics
@@ -120,6 +123,7 @@ class GraphedLiveDecoder:
     def __init__(self, decoder, frames: int, noise_seed: int = 0, carry_hidden: bool = False, delayed: bool = False):
         if getattr(decoder, 'z_dims', 0) > 0:
             raise ValueError(_NO_LATENT.format(what="GraphedLiveDecoder"))
+        refuse_wavetable(decoder, "GraphedLiveDecoder")
         decoder.check_live(delayed, "GraphedLiveDecoder")
         self.dec = decoder.eval()
         dev = next(decoder.parameters()).device

@@ -923,6 +923,48 @@ int ddsp_voices_mix(const float *audio, const float *gains, const uint8_t *activ
                     long hop, long hold, long fade, void *stream);
 
 /*
+ * Wavetable synthesis (csrc/ddsp_wavetable.hip): N single-cycle tables of L points, one fp64 phase
+ * accumulator per batch row reading them at f0 with linear interpolation, mixed by per-frame weights.
+ *   f0 [B,T,1] Hz, c [B,T,N] mix weights (normalised by their sum per frame inside), a [B,T,1] loudness, tables [N,L]
+ *   -> y [B, T*hop].  up() is the oscillator bank's upsampling; the phase P[b,n] = P0[b] + sum_{m<=n} up(fl32(f0/sample_rate))[b,m]
+ *   in cycles; y = up(a) * sum_k up(c_k / sum c) * (W[k,j] + fr * (W[k,j+1] - W[k,j])) at j = floor(frac(P) L), j + 1 wrapping.
+ *
+ * ddsp_wavetable_supported  1 when the kernels take N tables of L points (1 <= N <= 1024, 2 <= L <= 65536, N L <= 2^18).
+ * ddsp_wavetable_form       what the planner (csrc/ddsp_wavetable_plan.h) picks for the shape under the current hooks: the
+ *                           forward's form in bits 0-1 and the backward's in bits 2-3, 1 = the tables staged in LDS, 2 = read
+ *                           from memory; a negative DDSP_E* code for a shape the entry points would refuse.
+ * ddsp_wavetable_scratch_bytes  bytes of `scratch` the forward wants: 0 today (neither form keeps anything, the backward
+ *                           rebuilds the phases from f0); `scratch` may then be NULL.
+ * ddsp_wavetable_forward    one launch.  phase_io [B] fp64, nullable: the start phases P0 (cycles), replaced in place by
+ *                           frac(P[b, T*hop-1]) -- the state of a live stream, with no host round trip, so the call can be
+ *                           captured in a graph.  NULL: P0 = 0 and nothing is carried.
+ * ddsp_wavetable_backward   two launches.  grad_y [B, T*hop] -> grad_c [B,T,N] (with respect to the raw c: the normalisation's
+ *                           backward is inside), grad_a [B,T,1], grad_tables [N,L]; f0 gets no gradient.  phase_in [B]: the P0 the
+ *                           forward started from (nullable, read only).  scratch: >= ddsp_wavetable_backward_scratch_bytes bytes,
+ *                           256-byte aligned: three partials per frame and table (3x grad_c) and one private [N,L] table per
+ *                           workgroup of the plan (at most 256), sized under the test hooks in force when it is asked.  grad_c and grad_a are sums in a fixed order (the same bits every run); grad_tables
+ *                           is accumulated with atomics inside a workgroup, then over the workgroups in a fixed order.
+ * Both need hop <= 1024, T*hop <= 2^24 and return DDSP_ERANGE otherwise; with B == 0 they return 0 and write nothing.
+ *
+ * ddsp_wavetable_set_form   test hook: bits 0-1 force a form (0: the planner's, 1: LDS -- DDSP_ERANGE from the launch where it
+ *                           does not fit --, 2: memory); bits 8-15 the frames of a chunk and bits 16-23 the frames of an iteration
+ *                           (0: the planner's), so that the chunk prefix and the carried scan run at small shapes.
+ * ddsp_wavetable_set_grid   test hook: at most this many workgroups (1..256; 0: the default), so that the stride over the units
+ *                           runs at small shapes.
+ */
+int ddsp_wavetable_supported(int N, int L);
+int ddsp_wavetable_form(int B, int T, int N, int L, int hop);
+size_t ddsp_wavetable_scratch_bytes(int B, int T, int N, int L, int hop);
+int ddsp_wavetable_forward(const float *f0, const float *c, const float *a, const float *tables, float *y, void *scratch,
+                           double *phase_io, int B, int T, int N, int L, int hop, int sample_rate, void *stream);
+size_t ddsp_wavetable_backward_scratch_bytes(int B, int T, int N, int L, int hop);
+int ddsp_wavetable_backward(const float *grad_y, const float *f0, const float *c, const float *a, const float *tables,
+                            const double *phase_in, void *scratch, float *grad_c, float *grad_a, float *grad_tables, int B, int T,
+                            int N, int L, int hop, int sample_rate, void *stream);
+int ddsp_wavetable_set_form(int mode);
+int ddsp_wavetable_set_grid(int workgroups);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
