@@ -12,6 +12,8 @@ from . import training  # noqa: F401
 from .harmonic_oscillator import OscillatorBank, osc_forward, osc_backward  # noqa: F401
 from . import wavetable  # noqa: F401
 from .wavetable import WavetableBank, wavetable_forward, wavetable_backward, wavetable_form  # noqa: F401
+from .wavetable import (dirichlet_kernels, wavetable_mipmaps, wavetable_forward_bl, wavetable_backward_bl,  # noqa: F401
+                        wavetable_form_bl)
 from .filtered_noise import FilteredNoise, noise_forward, noise_backward, noise_ola_stream, ola_stream_state, calibrate_noise_residency  # noqa: F401
 from .reverb import Reverb, causal_fft_convolve  # noqa: F401
 from .graphed import GraphedSynth, GraphedLiveDecoder, GraphedTrainStep  # noqa: F401
@@ -50,4 +52,5 @@ __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "
            "ControlTransform", "transform_controls", "ControlMorph", "morph_controls", "ControlAlign", "align_controls", "control_features", "dtw_align",
            "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
            "latest_checkpoint", "mfcc", "MFCC", "ZEncoder", "voices", "allocate_voices", "mix_voices",
-           "wavetable", "WavetableBank", "wavetable_forward", "wavetable_backward", "wavetable_form"]
+           "wavetable", "WavetableBank", "wavetable_forward", "wavetable_backward", "wavetable_form",
+           "dirichlet_kernels", "wavetable_mipmaps", "wavetable_forward_bl", "wavetable_backward_bl", "wavetable_form_bl"]

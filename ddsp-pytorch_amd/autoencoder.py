@@ -60,10 +60,11 @@ from .wavetable import refuse_wavetable
 
 class AutoEncoder(nn.Module):
     def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, weights=None, voicing=None, tracker=None, noise_overlap_add=None,
-                 synth=None):
+                 synth=None, band_limited=None):
         super().__init__()
         self.encoder = Encoder(conf, weights, voicing=voicing, tracker=tracker)
-        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed, noise_overlap_add=noise_overlap_add, synth=synth)
+        self.decoder = Decoder(conf, noise_rng=noise_rng, seed=seed, noise_overlap_add=noise_overlap_add, synth=synth,
+                               band_limited=band_limited)
         self.padding = conf.n_fft - conf.hop_length
         self.hop_length = conf.hop_length
         self.n_noise_filters = conf.n_noise_filters

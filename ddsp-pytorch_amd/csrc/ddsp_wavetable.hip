@@ -11,7 +11,11 @@
 //                       order into the partial gradients of the frame and its two neighbours.
 //   wt_finish_kernel    the second launch: per frame the three partials, the normalisation's backward and grad_a; per table entry
 //                       the workgroups' private tables in workgroup order.
-// Every frame index is clamped into [0, T), every entry into [0, L), every sample index is below T hop.
+// Band-limited tables are the same three kernels with kBl set: W is then the mip levels M [Q + 1, N, L]
+// (ddsp_wavetable_mip.hip builds them) and a sample reads two of them.  A unit keeps in LDS the levels its frames can reach when
+// they fit: the forward their images to read, the backward their private gradient copies to scatter into (it reads the levels from
+// memory); the backward's private table is [Q + 1, N, L] in scratch, to which what LDS collected is added.
+// Every frame index is clamped into [0, T), every entry into [0, L), every level into [0, Q], every sample index is below T hop.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,6 +35,7 @@ static_assert(kHeadBytes >= sizeof(double) * (kThreads / 64) && kHeadBytes % 16 
 
 std::atomic<int> g_mode{0};     // ddsp_wavetable_set_form
 std::atomic<int> g_grid{0};     // ddsp_wavetable_set_grid
+std::atomic<long> g_mip_lds{0}; // ddsp_wavetable_set_mip_lds
 
 struct WtParams {
     const float *f0, *c, *a, *W;
@@ -42,6 +47,8 @@ struct WtParams {
     int B, T, N, L, hop;
     int P4, Q;                  // image pitch in 16-byte units; units that hold tables = ceil(N / 4)
     int iter_frames, chunk_frames, chunks, parts;
+    int nlev, fit;              // band-limited: W is M [nlev, N, L] and a unit stages up to `fit` levels; otherwise 1 and 0
+    unsigned *masks;            // band-limited backward: the levels each workgroup's private table holds anything in
     long units;
     int vec;                    // c rows can be read as float4
     float scale, sr;
@@ -128,7 +135,7 @@ __device__ __forceinline__ void table_position(double P, int L, int &j, float &f
 
 // tables 4 q .. 4 q + 3 at entries j and j + 1 (wrapped); tables past N read as 0
 template <bool kLds>
-__device__ __forceinline__ void fetch4(const WtParams &p, const float4 *img, int q, int j, float4 &lo, float4 &hi)
+__device__ __forceinline__ void fetch4(const WtParams &p, const float *W, const float4 *img, int q, int j, float4 &lo, float4 &hi)
 {
     if constexpr (kLds) {
         lo = img[image_unit(j, p.P4) + q];
@@ -140,7 +147,7 @@ __device__ __forceinline__ void fetch4(const WtParams &p, const float4 *img, int
         for (int x = 0; x < 4; ++x) {
             const int k = 4 * q + x;
             const bool ok = k < p.N;
-            const float *row = p.W + (long)(ok ? k : 0) * p.L;
+            const float *row = W + (long)(ok ? k : 0) * p.L;
             l[x] = ok ? row[j] : 0.0f;
             h[x] = ok ? row[j1] : 0.0f;
         }
@@ -163,23 +170,168 @@ __device__ __forceinline__ float4 lerp4(float fr, const float4 &lo, const float4
 }
 
 // the [L + 1][N] image: coalesced reads of W, row L repeats row 0, the pad tables are 0
-__device__ __forceinline__ void stage_image(const WtParams &p, float *img)
+__device__ __forceinline__ void stage_image(const WtParams &p, const float *W, float *img)
 {
     const int rows = p.L + 1, NP = 4 * p.P4;
     for (long i = threadIdx.x; i < (long)NP * rows; i += kThreads) {
         const int k = (int)(i / rows), row = (int)(i % rows);
-        img[4 * image_unit(row, p.P4) + k] = k < p.N ? p.W[(long)k * p.L + (row == p.L ? 0 : row)] : 0.0f;
+        img[4 * image_unit(row, p.P4) + k] = k < p.N ? W[(long)k * p.L + (row == p.L ? 0 : row)] : 0.0f;
     }
 }
 
-template <bool kLds>
+// ---- band-limited tables -------------------------------------------------------------------------------
+// The two levels a sample hears and the weight of the upper one, from its increment u: r = L u = m 2^e with m in [0.5, 1) gives
+// level e and t = 2 m - 1, all exact in fp32.  not (r > 0.5) -- u <= 0 and NaN too -- is level 0 alone; r >= L / 2 is the top alone.
+struct Level {
+    int q, q1;
+    float t;
+};
+
+__device__ __forceinline__ Level mip_level(float u, int L, int top)
+{
+    Level lv = {0, 1, 0.0f};
+    const float r = (float)L * u;
+    if (!(r > 0.5f)) return lv;
+    if (!(r < 0.5f * (float)L)) {
+        lv.q = lv.q1 = top;
+        return lv;
+    }
+    const int bits = __float_as_int(r);                                         // (0.5 < r < L / 2: a normal number)
+    lv.q = ((bits >> 23) & 0xff) - 126;
+    lv.q1 = lv.q + 1;
+    lv.t = __fmaf_rn(2.0f, __int_as_float((bits & 0x007fffff) | 0x3f000000), -1.0f);
+    return lv;
+}
+
+// What a unit stages, the same in every thread: the images of the levels [lo, hi] sit in LDS, level lo first.
+struct Staged {
+    int lo, hi;         // lo > hi: nothing staged
+    bool use;           // this unit reads them (its own levels fit); otherwise it reads M from memory
+};
+
+// The levels the frames [t_begin - 1, t_end] can make a sample of the chunk hear: every increment is an interpolation of two of
+// their g = f0 / sample_rate, so it lies between the smallest and the largest g, widened by 2^-20 for the interpolation's roundings.
+// (A lane whose level falls outside what is staged reads memory: the range decides speed, never what is read.)
+__device__ __forceinline__ void unit_levels(const WtParams &p, const float *f0row, int t_begin, int t_end, int *slots, int &lo, int &hi)
+{
+    const int fa = t_begin > 0 ? t_begin - 1 : 0, fb = t_end < p.T - 1 ? t_end : p.T - 1;
+    const int top = p.nlev - 1;
+    int l = top, h = 0;
+    for (int f = fa + (int)threadIdx.x; f <= fb; f += kThreads) {
+        const float g = f0row[f] / p.sr;
+        const Level a = mip_level(g * (1.0f - 0x1p-20f), p.L, top), b = mip_level(g * (1.0f + 0x1p-20f), p.L, top);
+        const int x = a.q < b.q ? a.q : b.q, y = a.q1 > b.q1 ? a.q1 : b.q1;
+        l = x < l ? x : l;
+        h = y > h ? y : h;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int l2 = __shfl_xor(l, o), h2 = __shfl_xor(h, o);
+        l = l2 < l ? l2 : l;
+        h = h2 > h ? h2 : h;
+    }
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = l | (h << 8);
+    __syncthreads();
+    l = top;
+    h = 0;
+    for (int w = 0; w < kThreads / 64; ++w) {
+        const int v = slots[w], x = v & 0xff, y = v >> 8;
+        l = x < l ? x : l;
+        h = y > h ? y : h;
+    }
+    __syncthreads();
+    lo = l < h ? l : h;
+    hi = h < top ? h : top;
+}
+
+// decide the unit's path and stage what it needs; every thread calls it with the same arguments (barriers inside)
+__device__ __forceinline__ void stage_levels(const WtParams &p, float4 *img, long img_units, int lo, int hi, Staged &st)
+{
+    st.use = hi - lo + 1 <= p.fit;
+    if (!st.use || (lo >= st.lo && hi <= st.hi)) return;
+    st.lo = lo;
+    st.hi = hi;
+    for (int q = lo; q <= hi; ++q)
+        stage_image(p, p.W + (long)q * p.N * p.L, reinterpret_cast<float *>(img + (long)(q - lo) * img_units));
+    __syncthreads();
+}
+
+// The backward keeps in LDS not the levels it reads (those come from memory) but the private grad_M of the levels it scatters to:
+// the same window [lo, hi], the same image layout.  What a window holds goes to the workgroup's slice in memory when the window
+// moves and at the end -- with atomics, like every other addition to the slice, so that all of them meet in L2.
+__device__ __forceinline__ void flush_private(const WtParams &p, const float *win, long img_units, const Staged &st, float *slice)
+{
+    const long NL = (long)p.N * p.L;
+    for (int q = st.lo; q <= st.hi; ++q) {
+        const float *im = win + 4 * (long)(q - st.lo) * img_units;
+        for (long i = threadIdx.x; i < NL; i += kThreads) {
+            const int k = (int)(i / p.L), row = (int)(i % p.L);
+            float v = im[4 * image_unit(row, p.P4) + k];
+            if (row == 0) v += im[4 * image_unit(p.L, p.P4) + k];               // row L belongs to entry 0
+            if (v != 0.0f) unsafeAtomicAdd(slice + q * NL + i, v);
+        }
+    }
+}
+
+// the backward's stage_levels: every thread calls it with the same arguments, after a barrier behind the last scatter
+__device__ __forceinline__ void open_private(const WtParams &p, float *win, long img_units, int lo, int hi, Staged &st, float *slice)
+{
+    st.use = hi - lo + 1 <= p.fit;
+    if (!st.use || (lo >= st.lo && hi <= st.hi)) return;
+    flush_private(p, win, img_units, st, slice);
+    __syncthreads();
+    st.lo = lo;
+    st.hi = hi;
+    for (long i = threadIdx.x; i < 4 * img_units * (hi - lo + 1); i += kThreads) win[i] = 0.0f;
+    __syncthreads();
+}
+
+// tables 4 g .. 4 g + 3 read at (j, fr): the unlimited table, or the blend of the sample's two levels
+template <bool kLds, bool kBl>
+__device__ __forceinline__ float4 entry4(const WtParams &p, const float4 *img, long img_units, const Staged &st, bool staged, int g,
+                                         int j, float fr, const Level &lv)
+{
+    float4 lo, hi;
+    if constexpr (!kBl) {
+        fetch4<kLds>(p, p.W, img, g, j, lo, hi);
+        return lerp4(fr, lo, hi);
+    } else {
+        // t == 0 -- level 0 alone, the top level alone, an exact octave -- reads one level and returns it as it is: the unlimited
+        // kernel's bits where that level is the table, whatever level q + 1 holds
+        const long NL = (long)p.N * p.L;
+        float4 v0, v1;
+        if (kLds && staged) {
+            fetch4<true>(p, p.W, img + (long)(lv.q - st.lo) * img_units, g, j, lo, hi);
+            v0 = lerp4(fr, lo, hi);
+            if (lv.t == 0.0f) return v0;
+            fetch4<true>(p, p.W, img + (long)(lv.q1 - st.lo) * img_units, g, j, lo, hi);
+            v1 = lerp4(fr, lo, hi);
+        } else {
+            fetch4<false>(p, p.W + lv.q * NL, img, g, j, lo, hi);
+            v0 = lerp4(fr, lo, hi);
+            if (lv.t == 0.0f) return v0;
+            fetch4<false>(p, p.W + lv.q1 * NL, img, g, j, lo, hi);
+            v1 = lerp4(fr, lo, hi);
+        }
+        const float t = lv.t, omt = 1.0f - lv.t;                                // (exact)
+        return make_float4(__fmaf_rn(t, v1.x, omt * v0.x), __fmaf_rn(t, v1.y, omt * v0.y), __fmaf_rn(t, v1.z, omt * v0.z),
+                           __fmaf_rn(t, v1.w, omt * v0.w));
+    }
+}
+
+__device__ __forceinline__ bool is_staged(const Staged &st, const Level &lv) { return st.use && lv.q >= st.lo && lv.q1 <= st.hi; }
+
+template <bool kLds, bool kBl>
 __global__ void __launch_bounds__(kThreads) wt_forward_kernel(const WtParams p)
 {
     extern __shared__ float4 smem[];
     double *head = reinterpret_cast<double *>(smem);
+    int *slots = reinterpret_cast<int *>(smem) + 32;                            // (behind the wavefronts' totals)
     const float4 *img = smem + kHeadBytes / 16;
-    if constexpr (kLds) {
-        stage_image(p, reinterpret_cast<float *>(smem + kHeadBytes / 16));
+    const long img_units = image_unit(p.L, p.P4) + p.P4;
+    Staged st = {1, 0, false};
+    if constexpr (kLds && !kBl) {
+        stage_image(p, p.W, reinterpret_cast<float *>(smem + kHeadBytes / 16));
         __syncthreads();
     }
     const int tid = threadIdx.x;
@@ -191,6 +343,11 @@ __global__ void __launch_bounds__(kThreads) wt_forward_kernel(const WtParams p)
         const float *f0row = p.f0 + (long)b * p.T;
         const float *arow = p.a + (long)b * p.T;
         const float *crow = p.c + (long)b * p.T * p.N;
+        if constexpr (kLds && kBl) {
+            int lo, hi;
+            unit_levels(p, f0row, t_begin, t_end, slots, lo, hi);
+            stage_levels(p, smem + kHeadBytes / 16, img_units, lo, hi, st);
+        }
         double carry = p.phase_io ? p.phase_io[b] : 0.0;
         if (t_begin > 0) carry += row_prefix(p, f0row, t_begin * p.hop, head);
         for (int t0 = t_begin; t0 < t_end; t0 += p.iter_frames) {
@@ -209,13 +366,17 @@ __global__ void __launch_bounds__(kThreads) wt_forward_kernel(const WtParams p)
             int j;
             float fr;
             table_position(P, p.L, j, fr);
+            Level lv = {0, 0, 0.0f};
+            bool staged = false;
+            if constexpr (kBl) {
+                lv = mip_level(u, p.L, p.nlev - 1);
+                staged = is_staged(st, lv);
+            }
             const float *c0 = crow + (long)s.i0 * p.N, *c1 = crow + (long)s.i1 * p.N;
             float A0 = 0.0f, A1 = 0.0f;
             double S0 = 0.0, S1 = 0.0;
             for (int q = 0; q < p.Q; ++q) {
-                float4 lo, hi;
-                fetch4<kLds>(p, img, q, j, lo, hi);
-                const float4 v = lerp4(fr, lo, hi);
+                const float4 v = entry4<kLds, kBl>(p, img, img_units, st, staged, q, j, fr, lv);
                 const float4 x0 = load4(c0, q, p.N, p.vec), x1 = load4(c1, q, p.N, p.vec);
                 A0 = __fmaf_rn(x0.x, v.x, A0); A0 = __fmaf_rn(x0.y, v.y, A0); A0 = __fmaf_rn(x0.z, v.z, A0); A0 = __fmaf_rn(x0.w, v.w, A0);
                 A1 = __fmaf_rn(x1.x, v.x, A1); A1 = __fmaf_rn(x1.y, v.y, A1); A1 = __fmaf_rn(x1.z, v.z, A1); A1 = __fmaf_rn(x1.w, v.w, A1);
@@ -231,22 +392,29 @@ __global__ void __launch_bounds__(kThreads) wt_forward_kernel(const WtParams p)
     }
 }
 
-template <bool kLds>
+// Band-limited (kBl): the levels are read from memory, the private table is [nlev, N, L] in scratch, and kLds says that a unit keeps
+// the private copies of the levels it scatters to in LDS when they fit (open_private).  A level of the slice is zeroed when the
+// workgroup first adds to it, and a word per workgroup tells the finish which levels those are: the rest is never written or read.
+template <bool kLds, bool kBl>
 __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
 {
     extern __shared__ float4 smem[];
     double *head = reinterpret_cast<double *>(smem);
+    int *slots = reinterpret_cast<int *>(smem) + 32;
     const long img_units = image_unit(p.L, p.P4) + p.P4;
     const float4 *img = smem + kHeadBytes / 16;
     float *priv_lds = reinterpret_cast<float *>(smem + kHeadBytes / 16 + img_units);
-    float4 *rec = smem + kHeadBytes / 16 + (kLds ? 2 * img_units : 0);
+    float *win = reinterpret_cast<float *>(smem + kHeadBytes / 16);            // band-limited: the private window, p.fit images
+    float4 *rec = smem + kHeadBytes / 16 + (kBl ? p.fit * img_units : (kLds ? 2 * img_units : 0));
     const int tid = threadIdx.x;
     const long NL = (long)p.N * p.L;
-    float *slice = p.priv + (long)blockIdx.x * NL;
-    if constexpr (kLds) {
-        stage_image(p, reinterpret_cast<float *>(smem + kHeadBytes / 16));
+    float *slice = p.priv + (long)blockIdx.x * NL * p.nlev;
+    Staged st = {1, 0, false};
+    unsigned zeroed = 0;        // band-limited: the levels of the slice this workgroup has zeroed, which are those it adds to
+    if constexpr (kLds && !kBl) {
+        stage_image(p, p.W, reinterpret_cast<float *>(smem + kHeadBytes / 16));
         for (long i = tid; i < 4 * img_units; i += kThreads) priv_lds[i] = 0.0f;
-    } else {
+    } else if constexpr (!kBl) {
         for (long i = tid; i < NL; i += kThreads) slice[i] = 0.0f;
         __threadfence_block();
     }
@@ -260,6 +428,11 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
         const float *f0row = p.f0 + (long)b * p.T;
         const float *arow = p.a + (long)b * p.T;
         const float *crow = p.c + (long)b * p.T * p.N;
+        if constexpr (kLds && kBl) {
+            int lo, hi;
+            unit_levels(p, f0row, t_begin, t_end, slots, lo, hi);
+            open_private(p, win, img_units, lo, hi, st, slice);
+        }
         double carry = p.phase_io ? p.phase_io[b] : 0.0;
         if (t_begin > 0) carry += row_prefix(p, f0row, t_begin * p.hop, head);
         for (int t0 = t_begin; t0 < t_end; t0 += p.iter_frames) {
@@ -274,7 +447,32 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
                 s = locate(p, n);
                 u = increment(p, f0row, s);
             }
+            Level lv = {0, 0, 0.0f};
+            if constexpr (kBl) {    // the levels this iteration adds to, over the workgroup (read behind the scan's barriers)
+                unsigned bits = 0;
+                if (active) {
+                    lv = mip_level(u, p.L, p.nlev - 1);
+                    bits = 1u << lv.q;
+                    if (lv.t != 0.0f) bits |= 1u << lv.q1;
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) bits |= __shfl_xor(bits, o);
+                if ((tid & 63) == 0) slots[tid >> 6] = (int)bits;
+            }
             const double P = block_scan((double)u, head, carry);
+            if constexpr (kBl) {    // a level is zeroed when the workgroup first adds to it: most levels never are
+                unsigned need = 0;
+                for (int w = 0; w < kThreads / 64; ++w) need |= (unsigned)slots[w];
+                const unsigned fresh = need & ~zeroed;                          // (the same in every thread)
+                if (fresh) {
+                    for (int q = 0; q < p.nlev; ++q)
+                        if (fresh >> q & 1)
+                            for (long i = tid; i < NL; i += kThreads) slice[q * NL + i] = 0.0f;
+                    __threadfence_block();
+                    __syncthreads();
+                    zeroed |= fresh;
+                }
+            }
             // ---- A: a thread per sample ----
             if (active) {
                 int j;
@@ -294,11 +492,17 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
                 const float qv = gy * au;
                 const float glo = qv * (1.0f - fr), ghi = qv * fr;
                 const int j1 = j + 1 == p.L ? 0 : j + 1;
+                bool staged = false;
+                float w[4] = {glo, ghi, 0.0f, 0.0f};                            // level q at j and j + 1, level q + 1 at j and j + 1
+                if constexpr (kBl) {
+                    staged = is_staged(st, lv);
+                    const float omt = 1.0f - lv.t;
+                    w[0] = glo * omt; w[1] = ghi * omt; w[2] = glo * lv.t; w[3] = ghi * lv.t;
+                }
+                float *const s0p = slice + lv.q * NL, *const s1p = slice + lv.q1 * NL;
                 float A0 = 0.0f, A1 = 0.0f;
                 for (int q = 0; q < p.Q; ++q) {
-                    float4 lo, hi;
-                    fetch4<kLds>(p, img, q, j, lo, hi);
-                    const float4 v = lerp4(fr, lo, hi);
+                    const float4 v = entry4<kLds && !kBl, kBl>(p, img, img_units, st, false, q, j, fr, lv);
                     const float4 x0 = load4(c0, q, p.N, p.vec), x1 = load4(c1, q, p.N, p.vec);
                     A0 = __fmaf_rn(x0.x, v.x, A0); A0 = __fmaf_rn(x0.y, v.y, A0); A0 = __fmaf_rn(x0.z, v.z, A0); A0 = __fmaf_rn(x0.w, v.w, A0);
                     A1 = __fmaf_rn(x1.x, v.x, A1); A1 = __fmaf_rn(x1.y, v.y, A1); A1 = __fmaf_rn(x1.z, v.z, A1); A1 = __fmaf_rn(x1.w, v.w, A1);
@@ -308,7 +512,22 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
                     for (int x = 0; x < 4; ++x) {
                         const int k = 4 * q + x;
                         if (k >= p.N) break;
-                        if constexpr (kLds) {
+                        if (kBl && kLds && staged) {
+                            float *const w0p = win + 4 * (long)(lv.q - st.lo) * img_units, *const w1p = win + 4 * (long)(lv.q1 - st.lo) * img_units;
+                            atomicAdd(w0p + 4 * image_unit(j, p.P4) + k, w[0] * m[x]);
+                            atomicAdd(w0p + 4 * image_unit(j + 1, p.P4) + k, w[1] * m[x]);
+                            if (lv.t != 0.0f) {
+                                atomicAdd(w1p + 4 * image_unit(j, p.P4) + k, w[2] * m[x]);
+                                atomicAdd(w1p + 4 * image_unit(j + 1, p.P4) + k, w[3] * m[x]);
+                            }
+                        } else if constexpr (kBl) {
+                            unsafeAtomicAdd(s0p + (long)k * p.L + j, w[0] * m[x]);
+                            unsafeAtomicAdd(s0p + (long)k * p.L + j1, w[1] * m[x]);
+                            if (lv.t != 0.0f) {
+                                unsafeAtomicAdd(s1p + (long)k * p.L + j, w[2] * m[x]);
+                                unsafeAtomicAdd(s1p + (long)k * p.L + j1, w[3] * m[x]);
+                            }
+                        } else if constexpr (kLds) {
                             atomicAdd(priv_lds + 4 * image_unit(j, p.P4) + k, glo * m[x]);
                             atomicAdd(priv_lds + 4 * image_unit(j + 1, p.P4) + k, ghi * m[x]);
                         } else {
@@ -346,9 +565,10 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
                     for (int r = part; r < p.hop; r += p.parts) {
                         const float4 ra = rec[2 * (f * p.hop + r)], rb = rec[2 * (f * p.hop + r) + 1];
                         if (kind < p.Q) {
-                            float4 lo, hi;
-                            fetch4<kLds>(p, img, kind, __float_as_int(ra.x), lo, hi);
-                            const float4 v = lerp4(ra.y, lo, hi);
+                            Level lv = {0, 0, 0.0f};
+                            if constexpr (kBl)                                  // (the record has no room: the sample's increment again)
+                                lv = mip_level(increment(p, f0row, locate(p, (t0 + f) * p.hop + r)), p.L, p.nlev - 1);
+                            const float4 v = entry4<kLds && !kBl, kBl>(p, img, img_units, st, false, kind, __float_as_int(ra.x), ra.y, lv);
                             const float e[3] = {ra.z, ra.w, rb.x};
 #pragma unroll
                             for (int x = 0; x < 3; ++x) {
@@ -387,7 +607,13 @@ __global__ void __launch_bounds__(kThreads) wt_backward_kernel(const WtParams p)
             __syncthreads();
         }
     }
-    if constexpr (kLds) {   // the private image -> this workgroup's [N, L] slice; row L belongs to entry 0
+    if constexpr (kBl) {
+        if constexpr (kLds) {
+            __syncthreads();
+            flush_private(p, win, img_units, st, slice);
+        }
+        if (tid == 0) p.masks[blockIdx.x] = zeroed;                             // the finish reads no other level of this slice
+    } else if constexpr (kLds) {   // the private image -> this workgroup's [N, L] slice; row L belongs to entry 0
         __syncthreads();
         for (long i = tid; i < NL; i += kThreads) {
             const int k = (int)(i / p.L), row = (int)(i % p.L);
@@ -433,11 +659,17 @@ __global__ void __launch_bounds__(kFinishThreads) wt_finish_kernel(const WtParam
         }
         return;
     }
-    const long NL = (long)p.N * p.L;
+    const long NL = (long)p.N * p.L * p.nlev;                                   // (band-limited: grad_W is grad_M [nlev, N, L])
     const long i = ((long)blockIdx.x - frame_blocks) * kFinishThreads + threadIdx.x;
     if (i >= NL) return;
     float v = 0.0f;
-    for (int w = 0; w < nwg; ++w) v += p.priv[(long)w * NL + i];
+    if (p.masks) {      // a workgroup that added nothing to the level holds zeros there: skipped, the order of the rest kept
+        const unsigned bit = 1u << (int)(i / ((long)p.N * p.L));
+        for (int w = 0; w < nwg; ++w)
+            if (p.masks[w] & bit) v += p.priv[(long)w * NL + i];
+    } else {
+        for (int w = 0; w < nwg; ++w) v += p.priv[(long)w * NL + i];
+    }
     p.grad_W[i] = v;
 }
 
@@ -458,6 +690,8 @@ void fill_params(WtParams &p, const Plan &pl, int B, int T, int N, int L, int ho
     p.B = B; p.T = T; p.N = N; p.L = L; p.hop = hop;
     p.P4 = pitch4(N);
     p.Q = (N + 3) / 4;
+    p.nlev = 1;
+    p.fit = 0;
     p.iter_frames = pl.iter_frames;
     p.chunk_frames = pl.chunk_frames;
     p.chunks = pl.chunks;
@@ -514,8 +748,8 @@ extern "C" int ddsp_wavetable_forward(const float *f0, const float *c, const flo
     p.f0 = f0; p.c = c; p.a = a; p.W = tables; p.y = y; p.phase_io = phase_io;
     fill_params(p, pl, B, T, N, L, hop, sample_rate);
     static bool done_lds[64], done_glb[64];
-    return (int)(pl.form == kFormLds ? launch(wt_forward_kernel<true>, done_lds, pl, p, (hipStream_t)stream)
-                                     : launch(wt_forward_kernel<false>, done_glb, pl, p, (hipStream_t)stream));
+    return (int)(pl.form == kFormLds ? launch(wt_forward_kernel<true, false>, done_lds, pl, p, (hipStream_t)stream)
+                                     : launch(wt_forward_kernel<false, false>, done_glb, pl, p, (hipStream_t)stream));
 }
 
 extern "C" size_t ddsp_wavetable_backward_scratch_bytes(int B, int T, int N, int L, int hop)
@@ -546,8 +780,8 @@ extern "C" int ddsp_wavetable_backward(const float *grad_y, const float *f0, con
     p.grad_c = grad_c; p.grad_a = grad_a; p.grad_W = grad_tables;
     fill_params(p, pl, B, T, N, L, hop, sample_rate);
     static bool done_lds[64], done_glb[64];
-    const hipError_t e = pl.form == kFormLds ? launch(wt_backward_kernel<true>, done_lds, pl, p, (hipStream_t)stream)
-                                             : launch(wt_backward_kernel<false>, done_glb, pl, p, (hipStream_t)stream);
+    const hipError_t e = pl.form == kFormLds ? launch(wt_backward_kernel<true, false>, done_lds, pl, p, (hipStream_t)stream)
+                                             : launch(wt_backward_kernel<false, false>, done_glb, pl, p, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
     const long frame_blocks = ((long)B * T + kFinishThreads / 64 - 1) / (kFinishThreads / 64);
     const long entry_blocks = ((long)N * L + kFinishThreads - 1) / kFinishThreads;
@@ -569,5 +803,98 @@ extern "C" int ddsp_wavetable_set_grid(int workgroups)
     if (workgroups != 0 && !ddsp_hooks_on()) return DDSP_EPERM;
     if (workgroups < 0 || workgroups > kMaxGrid) return DDSP_ERANGE;
     g_grid.store(workgroups);
+    return 0;
+}
+
+// ---- band-limited entry points: the same walk over the mip levels M [Q + 1, N, L] ---------------------------
+namespace {
+
+int out_of_range_bl(long B, long T, long N, long L, long hop)
+{
+    const int rc = out_of_range(B, T, N, L, hop);
+    return rc ? rc : (mip_supported(N, L) ? 0 : DDSP_ERANGE);
+}
+
+}  // namespace
+
+extern "C" int ddsp_wavetable_form_bl(int B, int T, int N, int L, int hop)
+{
+    if (bad_shape(B, T, N, L, hop, 1) || B == 0) return DDSP_EINVAL;
+    if (out_of_range_bl(B, T, N, L, hop)) return DDSP_ERANGE;
+    const int mode = g_mode.load(), cap = g_grid.load();
+    const size_t budget = (size_t)g_mip_lds.load();
+    const MipPlan f = plan_mip(B, T, N, L, hop, false, false, mode, cap, budget), b = plan_mip(B, T, N, L, hop, true, false, mode, cap, budget);
+    if (f.walk.status) return f.walk.status;
+    if (b.walk.status) return b.walk.status;
+    return f.walk.form | (b.walk.form << 2) | (f.fit << 8) | (b.fit << 16);
+}
+
+extern "C" int ddsp_wavetable_forward_bl(const float *f0, const float *c, const float *a, const float *levels, float *y,
+                                         double *phase_io, int B, int T, int N, int L, int hop, int sample_rate, void *stream)
+{
+    if (bad_shape(B, T, N, L, hop, sample_rate)) return DDSP_EINVAL;
+    if (B == 0) return 0;
+    if (!f0 || !c || !a || !levels || !y) return DDSP_EINVAL;
+    if (out_of_range_bl(B, T, N, L, hop)) return DDSP_ERANGE;
+    const MipPlan mp = plan_mip(B, T, N, L, hop, false, phase_io != nullptr, g_mode.load(), g_grid.load(), (size_t)g_mip_lds.load());
+    if (mp.walk.status) return mp.walk.status;
+    WtParams p = {};
+    p.f0 = f0; p.c = c; p.a = a; p.W = levels; p.y = y; p.phase_io = phase_io;
+    fill_params(p, mp.walk, B, T, N, L, hop, sample_rate);
+    p.nlev = mp.levels;
+    p.fit = mp.fit;
+    static bool done_lds[64], done_glb[64];
+    return (int)(mp.fit ? launch(wt_forward_kernel<true, true>, done_lds, mp.walk, p, (hipStream_t)stream)
+                        : launch(wt_forward_kernel<false, true>, done_glb, mp.walk, p, (hipStream_t)stream));
+}
+
+extern "C" size_t ddsp_wavetable_backward_bl_scratch_bytes(int B, int T, int N, int L, int hop)
+{
+    if (bad_shape(B, T, N, L, hop, 1) || B == 0 || out_of_range_bl(B, T, N, L, hop)) return 0;
+    const MipPlan mp = plan_mip(B, T, N, L, hop, true, false, g_mode.load(), g_grid.load(), (size_t)g_mip_lds.load());
+    return mip_backward_scratch_bytes(B, T, N, L, mp.levels, mp.walk.grid);
+}
+
+extern "C" int ddsp_wavetable_backward_bl(const float *grad_y, const float *f0, const float *c, const float *a, const float *levels,
+                                          const double *phase_in, void *scratch, float *grad_c, float *grad_a, float *grad_levels,
+                                          int B, int T, int N, int L, int hop, int sample_rate, void *stream)
+{
+    if (bad_shape(B, T, N, L, hop, sample_rate)) return DDSP_EINVAL;
+    if (B == 0) return 0;                                                       // (nothing is written: the caller zeroes grad_levels)
+    if (!grad_y || !f0 || !c || !a || !levels || !scratch || !grad_c || !grad_a || !grad_levels) return DDSP_EINVAL;
+    if (out_of_range_bl(B, T, N, L, hop)) return DDSP_ERANGE;
+    const MipPlan mp = plan_mip(B, T, N, L, hop, true, phase_in != nullptr, g_mode.load(), g_grid.load(), (size_t)g_mip_lds.load());
+    if (mp.walk.status) return mp.walk.status;
+    // (the scratch was sized for the plan without a start phase, whose grid is no smaller)
+    const int grid_sized = plan_mip(B, T, N, L, hop, true, false, g_mode.load(), g_grid.load(), (size_t)g_mip_lds.load()).walk.grid;
+    WtParams p = {};
+    p.f0 = f0; p.c = c; p.a = a; p.W = levels; p.grad_y = grad_y;
+    p.phase_io = const_cast<double *>(phase_in);                                // (read only)
+    char *ws = static_cast<char *>(scratch);
+    p.part_c = reinterpret_cast<float *>(ws);
+    p.part_a = reinterpret_cast<float *>(ws + part_c_bytes(B, T, N));
+    p.priv = reinterpret_cast<float *>(ws + part_c_bytes(B, T, N) + part_a_bytes(B, T));
+    if (mp.walk.grid > grid_sized) return DDSP_EINVAL;                          // (never: a start phase makes a row one unit, so no more units)
+    p.masks = reinterpret_cast<unsigned *>(ws + part_c_bytes(B, T, N) + part_a_bytes(B, T) + mip_private_bytes(N, L, mp.levels, grid_sized));
+    p.grad_c = grad_c; p.grad_a = grad_a; p.grad_W = grad_levels;
+    fill_params(p, mp.walk, B, T, N, L, hop, sample_rate);
+    p.nlev = mp.levels;
+    p.fit = mp.fit;
+    static bool done_lds[64], done_glb[64];
+    const hipError_t e = mp.fit ? launch(wt_backward_kernel<true, true>, done_lds, mp.walk, p, (hipStream_t)stream)
+                                : launch(wt_backward_kernel<false, true>, done_glb, mp.walk, p, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    const long frame_blocks = ((long)B * T + kFinishThreads / 64 - 1) / (kFinishThreads / 64);
+    const long entry_blocks = ((long)mp.levels * N * L + kFinishThreads - 1) / kFinishThreads;
+    hipLaunchKernelGGL(wt_finish_kernel, dim3((unsigned)(frame_blocks + entry_blocks)), dim3(kFinishThreads), 0, (hipStream_t)stream, p,
+                       frame_blocks, mp.walk.grid);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ddsp_wavetable_set_mip_lds(long bytes)
+{
+    if (bytes != 0 && !ddsp_hooks_on()) return DDSP_EPERM;
+    if (bytes < 0 || bytes > (long)kMaxLdsBytes) return DDSP_ERANGE;
+    g_mip_lds.store(bytes);
     return 0;
 }

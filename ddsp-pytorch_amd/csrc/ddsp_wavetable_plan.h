@@ -111,4 +111,73 @@ inline size_t backward_scratch_bytes(long B, long T, int N, int L, int grid)
     return part_c_bytes(B, T, N) + part_a_bytes(B, T) + round256(sizeof(float) * (size_t)grid * N * L);
 }
 
+// ---- band-limited tables: Q + 1 = log2 L + 1 mip levels M [Q + 1, N, L], two of them read per sample ------
+constexpr int kMipMinSize = 16, kMipMaxSize = 4096;                  // L: a power of two in this range
+constexpr size_t kMipMaxPrivateBytes = (size_t)512 << 20;           // backward: the private grad_M tables of all workgroups together
+
+inline bool mip_supported(long N, long L)
+{
+    return supported(N, L) && L >= kMipMinSize && L <= kMipMaxSize && (L & (L - 1)) == 0;
+}
+// Q + 1, or 0 for a table size that cannot be band-limited
+inline int mip_levels(long L)
+{
+    if (L < kMipMinSize || L > kMipMaxSize || (L & (L - 1)) != 0) return 0;
+    int Q = 0;
+    while ((1l << Q) < L) ++Q;
+    return Q + 1;
+}
+
+// The fit rule.  A unit (row, chunk) that hears the levels q_lo .. q_hi + 1 keeps one [L + 1][N] image (the layout above) of each
+// behind the scan totals: in the forward the level itself, to read; in the backward the workgroup's private gradient of the level,
+// to scatter into, with the iteration's records behind (it reads the levels from memory: images AND private copies of two levels
+// are 166 KB at 16 tables of 512 points and fit nowhere).  `budget`: 0 = a CU's LDS.
+inline size_t mip_lds_bytes(int N, int L, int levels, bool backward, int iter_samples)
+{
+    return kHeadBytes + (size_t)levels * image_bytes(N, L) + (backward ? kRecordBytes * (size_t)iter_samples : 0);
+}
+// the most levels a unit may stage: 0 .. Q + 1; below 2 no unit can take the LDS path (a sample reads two levels)
+inline int mip_fit_levels(int N, int L, bool backward, int iter_samples, size_t budget)
+{
+    const size_t cap = budget > 0 && budget < kMaxLdsBytes ? budget : kMaxLdsBytes;
+    const int all = mip_levels(L);
+    int n = 0;
+    while (n < all && mip_lds_bytes(N, L, n + 1, backward, iter_samples) <= cap) ++n;
+    return n;
+}
+
+struct MipPlan {
+    Plan walk;           // iterations, chunks, grid, parts as in the unlimited plan (its form and lds_bytes are replaced below)
+    int levels;          // Q + 1
+    int fit;             // levels a unit may stage (0: the memory path for every unit)
+};
+
+// mode: ddsp_wavetable_set_form's word.  Form 1 (LDS) wants EVERY level to fit, so that every unit takes the LDS path; form 2 none.
+inline MipPlan plan_mip(long B, long T, int N, int L, int hop, bool backward, bool live, int mode, int grid_cap, size_t budget)
+{
+    MipPlan mp;
+    mp.walk = plan(B, T, N, L, hop, backward, live, (mode & ~3) | kFormGlobal, grid_cap);     // (no shortened iterations)
+    mp.levels = mip_levels(L);
+    const int iter_samples = mp.walk.iter_frames * hop;
+    const int want = mode & 3;
+    mp.fit = want == kFormGlobal ? 0 : mip_fit_levels(N, L, backward, iter_samples, budget);
+    if (mp.fit < 2) mp.fit = 0;
+    if (mp.levels == 0 || (want == kFormLds && mp.fit < mp.levels)) mp.walk.status = kPlanERange;
+    mp.walk.form = mp.fit ? kFormLds : kFormGlobal;
+    mp.walk.lds_bytes = mip_lds_bytes(N, L, mp.fit, backward, iter_samples);
+    if (backward) {     // one private [Q + 1, N, L] table per workgroup: fewer workgroups where those would pass kMipMaxPrivateBytes
+        const size_t slice = sizeof(float) * (size_t)(mp.levels > 0 ? mp.levels : 1) * N * L;
+        const long most = (long)(kMipMaxPrivateBytes / slice);
+        if (mp.walk.grid > most) mp.walk.grid = most > 1 ? (int)most : 1;
+    }
+    return mp;
+}
+
+// band-limited backward scratch: | part_c | part_a | private grad_M tables [grid][Q + 1, N, L] | touched-level masks [grid] |
+inline size_t mip_private_bytes(int N, int L, int levels, int grid) { return round256(sizeof(float) * (size_t)grid * levels * N * L); }
+inline size_t mip_backward_scratch_bytes(long B, long T, int N, int L, int levels, int grid)
+{
+    return part_c_bytes(B, T, N) + part_a_bytes(B, T) + mip_private_bytes(N, L, levels, grid) + round256(sizeof(uint32_t) * (size_t)grid);
+}
+
 }  // namespace ddsp_wavetable

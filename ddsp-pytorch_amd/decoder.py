@@ -369,7 +369,7 @@ class Controller(nn.Module):
 class Decoder(nn.Module):
     """controller -> harmonics + noise -> reverb (decoder.py:119-147), all on the device."""
 
-    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None, synth=None):
+    def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None, synth=None, band_limited=None):
         super().__init__()
         synth = synth if synth is not None else (getattr(conf, 'synth', None) or 'harmonic')
         if synth not in ('harmonic', 'wavetable'):
@@ -377,7 +377,8 @@ class Decoder(nn.Module):
         self.synth = synth
         if synth == 'wavetable':
             # the second tonal synthesiser (wavetable.py): `c` mixes its N learnable tables instead of weighting harmonics
-            self.harmonics = WavetableBank(conf)
+            # (band_limited: None reads conf.wavetable_band_limited; it means nothing to the oscillator bank, which masks its harmonics)
+            self.harmonics = WavetableBank(conf, band_limited=band_limited)
             self.controller = Controller(conf, n_controls=self.harmonics.n_wavetables)
         else:
             self.controller = Controller(conf)

@@ -251,6 +251,9 @@ class GraphedTrainStep:
         if next((v.shape[0] for v in self.batch.values() if torch.is_tensor(v)), 0) == 0:
             raise ValueError("GraphedTrainStep cannot capture an empty shard")
         self.noises = [m for m in model.modules() if isinstance(m, FilteredNoise) and m.rng == "device"]
+        # band-limited wavetable banks keep the mip levels of their tables for live(): a replayed update rewrites the tables
+        # without touching the parameter's version, so every step tells them
+        self.level_caches = [m for m in model.modules() if hasattr(m, 'invalidate_levels')]
         # (the modules see their counter only inside this object's steps; eager calls keep the host-side offset)
         self.counters = [torch.tensor([m._offset], dtype=torch.int64, device=dev) for m in self.noises]
         self._mirror = [int(m._offset) for m in self.noises]    # what each device counter holds (host-side knowledge)
@@ -378,6 +381,8 @@ class GraphedTrainStep:
         for i, (m, d) in enumerate(zip(self.noises, self._draws)):
             self._mirror[i] += d
             m._offset = self._mirror[i]
+        for m in self.level_caches:
+            m.invalidate_levels()
         return self.loss, self.nbytes
 
     __call__ = step

@@ -9,8 +9,17 @@ with the same controller, noise, reverb, loss and trainer.
   wavetable_backward(grad_y, f0, c, a, tables, hop, sample_rate, phase=None) -> (grad_c, grad_a, grad_tables)
   wavetable_form(B, T, N, L, hop) -> dict(forward='lds' | 'global', backward=...)      the planner's answer
 
-Known limit: the tables are not band-limited (no mip-maps).  A table with content above sample_rate / (2 f0) aliases, as in the
-published method.
+Band-limited tables, opt-in with `WavetableBank(conf, band_limited=True)` or `conf.wavetable_band_limited`:
+every sample reads two mip levels of the tables, chosen from its increment, so that no harmonic above sample_rate / 2 is played.
+
+  dirichlet_kernels(L, device) -> D [Q+1, L]            the levels' kernels, fp64 on the host, cached per (L, device)
+  wavetable_mipmaps(tables) -> M [Q+1, N, L]            differentiable: the backward is the adjoint launch
+  wavetable_forward_bl(f0, c, a, levels, hop, sample_rate, phase=None) -> y
+  wavetable_backward_bl(grad_y, f0, c, a, levels, hop, sample_rate, phase=None) -> (grad_c, grad_a, grad_levels)
+
+Without the switch the tables are played as given: a table with content above sample_rate / (2 f0) aliases, as in the published
+method.  With it, inside an octave the top band fades out linearly (up to one octave of brightness is given away), and the images
+that linear interpolation itself creates are not addressed.
 """
 from __future__ import annotations
 
@@ -30,6 +39,14 @@ def wavetable_form(B: int, T: int, N: int, L: int, hop: int) -> dict:
     rc = _lib.lib().ddsp_wavetable_form(B, T, N, L, hop)
     _lib.check(rc if rc < 0 else 0, "ddsp_wavetable_form")
     return dict(forward=FORMS[rc & 3], backward=FORMS[(rc >> 2) & 3])
+
+
+def wavetable_form_bl(B: int, T: int, N: int, L: int, hop: int) -> dict:
+    """The band-limited plan for the shape (under the current test hooks): 'lds' -- a unit stages the levels it hears when at most
+    `*_fit` of them are needed -- or 'global' for the forward and the backward."""
+    rc = _lib.lib().ddsp_wavetable_form_bl(B, T, N, L, hop)
+    _lib.check(rc if rc < 0 else 0, "ddsp_wavetable_form_bl")
+    return dict(forward=FORMS[rc & 3], backward=FORMS[(rc >> 2) & 3], forward_fit=(rc >> 8) & 0xff, backward_fit=(rc >> 16) & 0xff)
 
 
 def _check_inputs(f0, c, a):
@@ -105,6 +122,154 @@ def wavetable_backward(grad_y, f0, c, a, tables, hop: int, sample_rate: int, pha
     return grad_c, grad_a, grad_t
 
 
+_KERNELS = {}
+
+
+def mip_levels(L: int) -> int:
+    """Q + 1 = log2 L + 1, or ValueError for a table size that cannot be band-limited"""
+    L = int(L)
+    if L < 16 or L > 4096 or L & (L - 1):
+        raise ValueError(f"band-limited wavetables need a table size that is a power of two with 16 <= L <= 4096, got {L}")
+    return L.bit_length()
+
+
+def dirichlet_kernels(L: int, device="cpu") -> torch.Tensor:
+    """D [Q+1, L] fp32 on `device`: D[q, j] = fl32((1 + 2 sum_{h=1..L>>(q+1)} cos(2 pi h j / L)) / L), computed in fp64 on the host;
+    row 0 (level 0 is the table itself) is zero.  Cached per (L, device)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(L), str(device))
+    if key not in _KERNELS:
+        n = mip_levels(L)
+        j = torch.arange(L, dtype=torch.float64)
+        D = torch.zeros(n, L, dtype=torch.float64)
+        for q in range(1, n):
+            h = torch.arange(1, (L >> (q + 1)) + 1, dtype=torch.float64)
+            D[q] = (1.0 + 2.0 * torch.cos(2.0 * math.pi * h[:, None] * j[None, :] / L).sum(0)) / L
+        _KERNELS[key] = D.float().to(device)
+    return _KERNELS[key]
+
+
+def _check_levels(c, levels):
+    if levels.device != c.device:
+        raise _lib.DdspHipError(f"wavetable: the levels are on {levels.device}, the controls on {c.device}")
+    if levels.dim() != 3 or levels.shape[1] != c.shape[-1]:
+        raise ValueError(f"expected levels [Q+1, N, L] with N = c's last dimension, got levels {tuple(levels.shape)}, c {tuple(c.shape)}")
+    if levels.shape[0] != mip_levels(levels.shape[2]):
+        raise ValueError(f"expected {mip_levels(levels.shape[2])} levels of {levels.shape[2]} points, got {levels.shape[0]}")
+
+
+def _mip_build(tables):
+    """tables [N, L] fp32 contiguous on the device -> M [Q+1, N, L] (one launch)"""
+    N, L = tables.shape
+    n = mip_levels(L)
+    if not tables.is_cuda:
+        raise _lib.DdspHipError("wavetable_mipmaps runs on the GPU only (no CPU fallback): move the tables to cuda")
+    D = dirichlet_kernels(L, tables.device)
+    M = torch.empty((n, N, L), device=tables.device, dtype=torch.float32)
+    with torch.cuda.device(tables.device):
+        rc = _lib.lib().ddsp_wavetable_mip_build(tables.data_ptr(), D.data_ptr(), M.data_ptr(), N, L, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_wavetable_mip_build")
+    return M
+
+
+class _MipFunction(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, tables):
+        return _mip_build(tables.detach().contiguous().float())
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_levels):
+        g = grad_levels.detach().contiguous().float()
+        n, N, L = g.shape
+        out = torch.empty((N, L), device=g.device, dtype=torch.float32)
+        D = dirichlet_kernels(L, g.device)
+        with torch.cuda.device(g.device):
+            rc = _lib.lib().ddsp_wavetable_mip_adjoint(g.data_ptr(), D.data_ptr(), out.data_ptr(), N, L, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "ddsp_wavetable_mip_adjoint")
+        return out
+
+
+def wavetable_mipmaps(tables):
+    """tables [N, L] -> the mip levels M [Q+1, N, L] (M[0] is the tables bit for bit); differentiable with respect to the tables."""
+    if tables.dim() != 2:
+        raise ValueError(f"expected tables [N, L], got {tuple(tables.shape)}")
+    mip_levels(tables.shape[1])
+    return _MipFunction.apply(tables)
+
+
+def wavetable_forward_bl(f0, c, a, levels, hop: int, sample_rate: int, phase=None):
+    """Raw launcher of ddsp_wavetable_forward_bl -> y [B, T hop]; `phase` as in wavetable_forward."""
+    _check_inputs(f0, c, a)
+    _check_levels(c, levels)
+    f0 = f0.detach().contiguous().float()
+    c = c.detach().contiguous().float()
+    a = a.detach().contiguous().float()
+    levels = levels.detach().contiguous().float()
+    B, T, N = c.shape
+    y = torch.empty((B, T * hop), device=c.device, dtype=torch.float32)
+    if B == 0:
+        return y
+    if phase is not None and (phase.dtype != torch.float64 or phase.shape != (B,) or phase.device != c.device or not phase.is_contiguous()):
+        raise ValueError(f"phase must be a contiguous fp64 tensor [{B}] on {c.device}")
+    with torch.cuda.device(c.device):
+        rc = _lib.lib().ddsp_wavetable_forward_bl(f0.data_ptr(), c.data_ptr(), a.data_ptr(), levels.data_ptr(), y.data_ptr(), _dev_ptr(phase),
+                                                  B, T, N, levels.shape[2], hop, sample_rate, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_wavetable_forward_bl")
+    return y
+
+
+def wavetable_backward_bl(grad_y, f0, c, a, levels, hop: int, sample_rate: int, phase=None):
+    """Raw launcher of ddsp_wavetable_backward_bl -> (grad_c [B,T,N], grad_a [B,T,1], grad_levels [Q+1,N,L])."""
+    _check_inputs(f0, c, a)
+    _check_levels(c, levels)
+    f0 = f0.detach().contiguous().float()
+    c = c.detach().contiguous().float()
+    a = a.detach().contiguous().float()
+    levels = levels.detach().contiguous().float()
+    grad_y = grad_y.detach().contiguous().float()
+    B, T, N = c.shape
+    L = levels.shape[2]
+    grad_c, grad_a, grad_l = torch.empty_like(c), torch.empty_like(a), torch.empty_like(levels)
+    if B == 0:
+        return grad_c, grad_a, grad_l.zero_()
+    lib = _lib.lib()
+    scratch = torch.empty(lib.ddsp_wavetable_backward_bl_scratch_bytes(B, T, N, L, hop), device=c.device, dtype=torch.uint8)
+    with torch.cuda.device(c.device):
+        rc = lib.ddsp_wavetable_backward_bl(grad_y.data_ptr(), f0.data_ptr(), c.data_ptr(), a.data_ptr(), levels.data_ptr(), _dev_ptr(phase),
+                                            scratch.data_ptr(), grad_c.data_ptr(), grad_a.data_ptr(), grad_l.data_ptr(), B, T, N, L, hop,
+                                            sample_rate, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "ddsp_wavetable_backward_bl")
+    return grad_c, grad_a, grad_l
+
+
+class _WavetableBlFunction(torch.autograd.Function):
+    """The band-limited synthesis on given levels: differentiable w.r.t. c, a and the levels (wavetable_mipmaps carries that on to
+    the tables)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, f0, c, a, levels, hop, sample_rate):
+        f0 = f0.detach().contiguous().float()
+        c = c.detach().contiguous().float()
+        a = a.detach().contiguous().float()
+        levels = levels.detach().contiguous().float()
+        y = wavetable_forward_bl(f0, c, a, levels, hop, sample_rate)
+        ctx.save_for_backward(f0, c, a, levels)
+        ctx.hop, ctx.sample_rate = hop, sample_rate
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y):
+        f0, c, a, levels = ctx.saved_tensors
+        grad_c, grad_a, grad_l = wavetable_backward_bl(grad_y, f0, c, a, levels, ctx.hop, ctx.sample_rate)
+        return None, grad_c, grad_a, grad_l, None, None
+
+
 class _WavetableFunction(torch.autograd.Function):
     """Differentiable w.r.t. c, a and the tables; f0 carries no gradient, as in the oscillator bank."""
 
@@ -151,8 +316,11 @@ def resample_tables(tables: torch.Tensor, table_size: int) -> torch.Tensor:
 
 
 class WavetableBank(nn.Module):
-    def __init__(self, conf, n_wavetables=None, table_size=None, init='harmonic'):
+    def __init__(self, conf, n_wavetables=None, table_size=None, init='harmonic', band_limited=None):
         super().__init__()
+        if band_limited is None:
+            band_limited = bool(getattr(conf, 'wavetable_band_limited', False))
+        self.band_limited = bool(band_limited)
         if n_wavetables is None:
             n_wavetables = getattr(conf, 'n_wavetables', None) or conf.n_harmonics
         if table_size is None:
@@ -162,6 +330,8 @@ class WavetableBank(nn.Module):
         self.hop_size = conf.hop_length
         if self.n_wavetables < 1 or self.table_size < 2:
             raise ValueError(f"WavetableBank needs n_wavetables >= 1 and table_size >= 2, got {n_wavetables} and {table_size}")
+        if self.band_limited:
+            mip_levels(self.table_size)         # (ValueError for a size that cannot be band-limited)
         if torch.is_tensor(init):
             if tuple(init.shape) != (self.n_wavetables, self.table_size):
                 raise ValueError(f"init must be [{self.n_wavetables}, {self.table_size}], got {tuple(init.shape)}")
@@ -173,21 +343,60 @@ class WavetableBank(nn.Module):
         self.wavetables = nn.Parameter(tables)
         # the live stream's phase per batch row (cycles, fp64), updated in place by the kernel; not part of the state dict
         self.register_buffer("phase", torch.zeros(0, dtype=torch.float64), persistent=False)
+        # band-limited, live() only: the levels of the tables as they were at `_levels_key` (the parameter's version and
+        # storage), rebuilt when either changes or after invalidate_levels(); not a buffer, not part of the state dict
+        self._levels, self._levels_key = None, None
+
+    def levels(self) -> torch.Tensor:
+        """The mip levels [Q+1, N, L] of the tables for the live path, without gradient: cached, and rebuilt (one launch) after the
+        parameter was written to in a way autograd's version counter sees (an eager optimiser step, `load_tables`,
+        `load_state_dict`), after it moved, and after `invalidate_levels()`.  A write the counter does not see -- the replay of
+        a captured optimiser update -- needs `invalidate_levels()`; `GraphedTrainStep` calls it after every step.  `forward`
+        does not use this cache: it builds the levels from the tables on every call."""
+        w = self.wavetables
+        key = (w._version, w.data_ptr(), str(w.device))
+        if self._levels is None or self._levels_key != key:
+            with torch.no_grad():
+                self._levels = _mip_build(w.detach().contiguous().float())
+            self._levels_key = key
+        return self._levels
+
+    def invalidate_levels(self) -> None:
+        """Forget the cached mip levels: the next `live()` builds them from the tables as they are then."""
+        self._levels, self._levels_key = None, None
+
+    def _forward_bl(self, f0, c, a):
+        _check_tables(c, self.wavetables)
+        if torch.is_grad_enabled() and (c.requires_grad or a.requires_grad or self.wavetables.requires_grad):
+            return _WavetableBlFunction.apply(f0, c, a, wavetable_mipmaps(self.wavetables), self.hop_size, self.sample_rate)
+        # (no cache here: one 30 us launch, and nothing that rewrote the tables behind autograd's back can be missed)
+        with torch.no_grad():
+            levels = _mip_build(self.wavetables.detach().contiguous().float())
+        return wavetable_forward_bl(f0, c, a, levels, self.hop_size, self.sample_rate)
 
     def forward(self, x):
         f0, c, a = x['f0'], x['c'], x['a']
         _check_inputs(f0, c, a)
+        if self.band_limited:
+            return self._forward_bl(f0, c, a)
         if torch.is_grad_enabled() and (c.requires_grad or a.requires_grad or self.wavetables.requires_grad):
             _check_tables(c, self.wavetables)
             return _WavetableFunction.apply(f0, c, a, self.wavetables, self.hop_size, self.sample_rate)
         return wavetable_forward(f0, c, a, self.wavetables, self.hop_size, self.sample_rate)
 
     def live(self, x):
+        """One block of a stream: the phase per row is carried on the device.  Band-limited: the block is one launch on the
+        cached levels (`levels()`).  The first band-limited call on a device copies the Dirichlet kernels to it and builds the
+        levels, so call `live()` (or `levels()`) once before capturing it in a graph; a captured graph replays the levels it was
+        captured with."""
         f0, c, a = x['f0'], x['c'], x['a']
         _check_inputs(f0, c, a)
         B = c.shape[0]
         if self.phase.shape[0] != B or self.phase.device != c.device:
             self.phase = torch.zeros(B, dtype=torch.float64, device=c.device)
+        if self.band_limited:
+            _check_tables(c, self.wavetables)
+            return wavetable_forward_bl(f0, c, a, self.levels(), self.hop_size, self.sample_rate, phase=self.phase)
         return wavetable_forward(f0, c, a, self.wavetables, self.hop_size, self.sample_rate, phase=self.phase)
 
     def reset_phase(self):

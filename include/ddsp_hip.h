@@ -965,6 +965,48 @@ int ddsp_wavetable_set_form(int mode);
 int ddsp_wavetable_set_grid(int workgroups);
 
 /*
+ * Band-limited wavetables (csrc/ddsp_wavetable_mip.hip, csrc/ddsp_wavetable.hip): mip levels of the tables,
+ * two of which every sample reads, chosen from its increment so that no harmonic above sample_rate / 2 is played.  L must be a
+ * power of two with 16 <= L <= 4096 (DDSP_ERANGE otherwise); Q = log2 L and there are Q + 1 levels.
+ *   levels M [Q+1, N, L] fp32: M[0] = tables bit for bit; M[q] for q >= 1 keeps the mean and the harmonics h <= L >> (q + 1):
+ *   M[q,k,j] = sum_i tables[k,i] * kernels[q, (j - i) mod L], i ascending in fp32, with kernels [Q+1, L] fp32 the Dirichlet kernels
+ *   D[q,j] = (1 + 2 sum_{h=1..L>>(q+1)} cos(2 pi h j / L)) / L computed by the caller in fp64 (row 0 is never read).
+ *   A sample with increment u (as above) has r = L u.  not (r > 0.5): level 0 alone.  Otherwise r = m 2^e with m in [0.5, 1):
+ *   levels e and e + 1 with weights 1 - t and t, t = 2 m - 1; e >= Q: level Q alone.  Everything else is ddsp_wavetable_forward's.
+ *
+ * ddsp_wavetable_mip_levels   Q + 1, or DDSP_ERANGE for a table size that cannot be band-limited.
+ * ddsp_wavetable_mip_build    one launch, tables [N,L] -> levels; the same bits every run.
+ * ddsp_wavetable_mip_adjoint  one launch, grad_levels [Q+1,N,L] -> grad_tables [N,L] = grad_levels[0] + sum_q the same circular
+ *                             sum of grad_levels[q] with kernels[q] (they are symmetric); the same bits every run.
+ * ddsp_wavetable_form_bl      the band-limited plan under the current hooks: bits 0-1 the forward's form and bits 2-3 the
+ *                             backward's (1: a unit (row, chunk) stages the levels it hears in LDS when they fit, 2: every unit
+ *                             reads the levels from memory), bits 8-15 and 16-23 the most levels a unit of the forward and of the
+ *                             backward can stage; a negative DDSP_E* code for a shape the entry points would refuse.
+ * ddsp_wavetable_forward_bl   one launch; ddsp_wavetable_forward with `levels` in place of the tables (no scratch).
+ * ddsp_wavetable_backward_bl  two launches; as ddsp_wavetable_backward, with grad_levels [Q+1,N,L] out (give it to
+ *                             ddsp_wavetable_mip_adjoint for the tables' gradient).  t and the table position carry no gradient.
+ *                             scratch >= ddsp_wavetable_backward_bl_scratch_bytes, 256-byte aligned: the three partials per frame
+ *                             and one private [Q+1,N,L] table per workgroup; the workgroups are limited so that those stay within
+ *                             512 MiB.  grad_c and grad_a have the same bits every run; grad_levels is summed with atomics inside
+ *                             a workgroup.
+ * ddsp_wavetable_set_mip_lds  test hook: the LDS bytes a workgroup of the band-limited kernels may use (0: a CU's 160 KiB), so
+ *                             that "the levels do not fit" happens at small shapes.  ddsp_wavetable_set_form's form bits apply
+ *                             too: 1 returns DDSP_ERANGE unless all Q + 1 levels fit (then every unit stages), 2 stages nothing;
+ *                             its chunk and iteration bits and ddsp_wavetable_set_grid act as on the unlimited kernels.
+ */
+int ddsp_wavetable_mip_levels(int L);
+int ddsp_wavetable_mip_build(const float *tables, const float *kernels, float *levels, int N, int L, void *stream);
+int ddsp_wavetable_mip_adjoint(const float *grad_levels, const float *kernels, float *grad_tables, int N, int L, void *stream);
+int ddsp_wavetable_form_bl(int B, int T, int N, int L, int hop);
+int ddsp_wavetable_forward_bl(const float *f0, const float *c, const float *a, const float *levels, float *y, double *phase_io,
+                              int B, int T, int N, int L, int hop, int sample_rate, void *stream);
+size_t ddsp_wavetable_backward_bl_scratch_bytes(int B, int T, int N, int L, int hop);
+int ddsp_wavetable_backward_bl(const float *grad_y, const float *f0, const float *c, const float *a, const float *levels,
+                               const double *phase_in, void *scratch, float *grad_c, float *grad_a, float *grad_levels, int B,
+                               int T, int N, int L, int hop, int sample_rate, void *stream);
+int ddsp_wavetable_set_mip_lds(long bytes);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as

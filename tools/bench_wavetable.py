@@ -12,6 +12,12 @@ the fp64 reference of tests/wavetable_reference.py (error over its bound), and t
 against the definition's -- the difference that makes the torch-op form's phase drift.  There is no threshold: DESIGN.md section 5b
 records the figures.  The one claim it checks is printed as `hip_forward_faster_than_torch_ops`.
 
+Band-limited rows, beside the unlimited ones in the same run: `bl_*_forward` (the cached pyramid, one launch),
+`bl_*_forward_backward` (mip build, synthesis, its backward, the adjoint) and `mip_build` alone; `planned` lets a unit stage the
+levels it hears when they fit, `global` reads them from memory.  Two f0 tracks: the tool's random one (every row hears five levels:
+no row fits) and `notes` (a note per row with a vibrato of +-50 cents: a row hears two or three levels).  `bl_rows_that_stage` is
+the share of rows whose levels fit -- the share of units at batches of 256 rows and more, where a row is one unit.
+
     python tools/bench_wavetable.py [--batch 512] [--frames 500] [--hop 128] [--tables 16 32] [--size 512] [--window 0.25] [--repeats 5] [--runs 2] [--check-rows 2]
 """
 import argparse
@@ -85,6 +91,19 @@ def check_against_fp64(f0, c, a, W, gy, hop, rows, lib):
     return out
 
 
+def rows_that_stage(f0, L, fit):
+    """Share of rows whose frames hear at most `fit` levels, by the kernel's rule (g = f0 / sample_rate widened by 2^-20)."""
+    g = (f0[..., 0] / RATE).float()
+
+    def level(u):
+        r = (u * L).double()
+        q = torch.where(r > 0.5, torch.frexp(r.clamp(min=0.5))[1].double(), torch.zeros_like(r))
+        return torch.where(r >= L / 2, torch.full_like(r, L.bit_length() - 1), q)
+    lo = level(g * (1.0 - 2.0 ** -20)).amin(1)
+    hi = (level(g * (1.0 + 2.0 ** -20)) + 1).clamp(max=L.bit_length() - 1).amax(1)
+    return float(((hi - lo + 1) <= fit).double().mean())
+
+
 def torch_ops_forward(f0, c, a, W, hop):
     """The definition of section 5b as torch operations (fp32, the phase in fp64)."""
     up = lambda x: F.interpolate(x.transpose(1, 2), scale_factor=hop, mode="linear", align_corners=False).transpose(1, 2)   # noqa: E731
@@ -111,6 +130,7 @@ def main():
     ap.add_argument("--check-rows", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--no-band-limited", action="store_true", help="leave the band-limited rows out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_wavetable.py measures on the GPU; none is visible")
@@ -121,6 +141,9 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     f0 = 80.0 + 700.0 * torch.rand((B, T, 1), device=dev, generator=g)
     a = 0.1 + torch.rand((B, T, 1), device=dev, generator=g)
+    # `notes`: a note per row in the same range, with a 5 Hz vibrato of +-50 cents
+    note = 80.0 * (780.0 / 80.0) ** torch.rand((B, 1, 1), device=dev, generator=g)
+    f0_notes = note * 2.0 ** (torch.sin(2.0 * torch.pi * 5.0 * hop / RATE * torch.arange(T, device=dev).view(1, T, 1)) / 24.0)
     gy = torch.randn((B, T * hop), device=dev, generator=g)
     samples = B * T * hop
     results = {}
@@ -165,6 +188,15 @@ def main():
             c.grad = aw.grad = wt.wavetables.grad = None
             return y
 
+        bl, bl_info = None, {}
+        if not args.no_band_limited:
+            bl = ddsp.WavetableBank(Conf, table_size=L, init=wt.wavetables.detach().cpu(), band_limited=True).to(dev)
+            plan = ddsp.wavetable_form_bl(B, T, N, L, hop)
+            bl_info = dict(bl_planned=plan, bl_backward_scratch_bytes=int(lib.ddsp_wavetable_backward_bl_scratch_bytes(B, T, N, L, hop)),
+                           bl_rows_that_stage=dict(forward=rows_that_stage(f0, L, plan["forward_fit"]),
+                                                   backward=rows_that_stage(f0, L, plan["backward_fit"]),
+                                                   forward_notes=rows_that_stage(f0_notes, L, plan["forward_fit"]),
+                                                   backward_notes=rows_that_stage(f0_notes, L, plan["backward_fit"])))
         runs = []
         for _ in range(args.runs):
             t = {}
@@ -179,6 +211,25 @@ def main():
             t["hip_planned_forward_backward"] = timed(step, 3, args.repeats)
             t["torch_ops_forward"] = timed(torch_forward, 2, args.repeats)
             t["torch_ops_forward_backward"] = timed(torch_step, 2, args.repeats)
+            if bl is not None:
+                for track, f in (("", f0), ("_notes", f0_notes)):
+                    xb = {"f0": f, "c": c, "a": aw}
+
+                    def bl_forward():
+                        with torch.no_grad():
+                            return bl(xb)
+
+                    def bl_step():
+                        y = bl(xb)
+                        y.backward(gy)
+                        c.grad = aw.grad = bl.wavetables.grad = None
+                        return y
+                    for name, mode in (("planned", 0), ("global", 2)):
+                        assert lib.ddsp_wavetable_set_form(mode) == 0
+                        t[f"bl_{name}_forward{track}"] = timed(bl_forward, 3, args.repeats)
+                        t[f"bl_{name}_forward_backward{track}"] = timed(bl_step, 3, args.repeats)
+                    assert lib.ddsp_wavetable_set_form(0) == 0
+                t["mip_build"] = timed(lambda: ddsp.wavetable_mipmaps(bl.wavetables.detach()), 3, args.repeats)
             if N == args.tables[0]:
                 t["bank100_forward"] = timed(lambda: bank({"f0": f0, "c": cb.detach(), "a": ab.detach()}), 3, args.repeats)
                 t["bank100_forward_backward"] = timed(bank_step, 3, args.repeats)
@@ -188,7 +239,7 @@ def main():
         checks = check_against_fp64(f0, c, aw, wt.wavetables, gy, hop, rows, lib) if rows else {}
         form = ddsp.wavetable_form(B, T, N, L, hop)
         results[f"N{N}"] = dict(
-            planned=form, rows_checked_against_fp64=rows, **checks,
+            planned=form, rows_checked_against_fp64=rows, **checks, **bl_info,
             hip_forward_Msamples_per_s=round(samples / med("hip_planned_forward_ms") / 1e3, 1),
             hip_forward_faster_than_torch_ops=bool(med("hip_planned_forward_ms") < med("torch_ops_forward_ms")),
             torch_ops_over_hip_forward=round(med("torch_ops_forward_ms") / med("hip_planned_forward_ms"), 2),
