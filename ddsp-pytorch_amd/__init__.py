@@ -14,6 +14,8 @@ from . import wavetable  # noqa: F401
 from .wavetable import WavetableBank, wavetable_forward, wavetable_backward, wavetable_form  # noqa: F401
 from .wavetable import (dirichlet_kernels, wavetable_mipmaps, wavetable_forward_bl, wavetable_backward_bl,  # noqa: F401
                         wavetable_form_bl)
+from . import sinusoids  # noqa: F401
+from .sinusoids import InharmonicBank, sinusoids_forward, sinusoids_backward, stretched_ratios  # noqa: F401
 from .filtered_noise import FilteredNoise, noise_forward, noise_backward, noise_ola_stream, ola_stream_state, calibrate_noise_residency  # noqa: F401
 from .reverb import Reverb, causal_fft_convolve  # noqa: F401
 from .graphed import GraphedSynth, GraphedLiveDecoder, GraphedTrainStep  # noqa: F401
@@ -53,4 +55,5 @@ __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "
            "synthetic", "trainer", "DeviceBatches", "PlateauRate", "Trainer", "gather_batch", "load_checkpoint",
            "latest_checkpoint", "mfcc", "MFCC", "ZEncoder", "voices", "allocate_voices", "mix_voices",
            "wavetable", "WavetableBank", "wavetable_forward", "wavetable_backward", "wavetable_form",
-           "dirichlet_kernels", "wavetable_mipmaps", "wavetable_forward_bl", "wavetable_backward_bl", "wavetable_form_bl"]
+           "dirichlet_kernels", "wavetable_mipmaps", "wavetable_forward_bl", "wavetable_backward_bl", "wavetable_form_bl",
+           "sinusoids", "InharmonicBank", "sinusoids_forward", "sinusoids_backward", "stretched_ratios"]

@@ -152,6 +152,13 @@ SIGNATURES = {
     "ddsp_wavetable_backward_bl_scratch_bytes": (_size, [_i32] * 5),
     "ddsp_wavetable_backward_bl": (_i32, [_vp] * 10 + [_i32] * 6 + [_vp]),
     "ddsp_wavetable_set_mip_lds": (_i32, [_long]),
+    "ddsp_sinusoids_supported": (_i32, [_i32, _i32]),
+    "ddsp_sinusoids_scratch_bytes": (_size, [_i32] * 4),
+    "ddsp_sinusoids_forward": (_i32, [_vp] * 6 + [_i32] * 6 + [_vp]),
+    "ddsp_sinusoids_backward_scratch_bytes": (_size, [_i32] * 5),
+    "ddsp_sinusoids_backward": (_i32, [_vp] * 9 + [_i32] * 6 + [_vp]),
+    "ddsp_sinusoids_set_form": (_i32, [_i32]),
+    "ddsp_sinusoids_set_grid": (_i32, [_i32]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
     "ddsp_griffinlim_supported": (_i32, [_i32]),

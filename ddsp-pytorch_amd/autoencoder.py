@@ -55,6 +55,7 @@ from .voices import allocate_voices, mix_voices
 from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
 from .decoder import Decoder
 from .encoder import Encoder
+from .sinusoids import refuse_inharmonic
 from .wavetable import refuse_wavetable
 
 
@@ -206,6 +207,7 @@ class AutoEncoder(nn.Module):
         refine=N runs N steps of analysis.refine_f0 on the encoder's track before the analysis (a decoded track is a bin centre,
         up to 10 cents off); the dict's f0 is then the refined track.  refine=0 is the analysis along the encoder's own track."""
         refuse_wavetable(self.decoder, "analyse")
+        refuse_inharmonic(self.decoder, "analyse")
         if noise not in (False, True, 'truncated', 'overlap_add'):
             raise ValueError(f"analyse: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
         overlap_add = noise == 'overlap_add'
@@ -239,6 +241,7 @@ class AutoEncoder(nn.Module):
         `decoder.synthesize`, and `decoder.reverb` only when asked.  noise follows analyse's rules (True / 'truncated' /
         'overlap_add' must be the decoder's noise form); noise=False plays the harmonics alone (`decoder.harmonics`)."""
         refuse_wavetable(self.decoder, "transform")
+        refuse_inharmonic(self.decoder, "transform")
         ctrl = transform_controls(self.analyse(x, noise=noise, refine=refine), self.decoder.harmonics.sample_rate, stretch=stretch,
                                   transpose=transpose, formant=formant, positions=positions)
         with torch.no_grad():
@@ -256,6 +259,7 @@ class AutoEncoder(nn.Module):
         of the two analysed dicts; `timing`, 0 is x's clock and 1 is y's, `radius`, `penalty`; `frames` is then the timeline's T')
         instead of stretching both clips linearly; positions_a / positions_b must then be left out."""
         refuse_wavetable(self.decoder, "morph")
+        refuse_inharmonic(self.decoder, "morph")
         if align and (positions_a is not None or positions_b is not None):
             raise ValueError("morph: align=True finds positions_a and positions_b; give one or the other")
         ctrl_x, ctrl_y = self.analyse(x, noise=noise, refine=refine), self.analyse(y, noise=noise, refine=refine)

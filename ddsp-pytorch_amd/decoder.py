@@ -26,6 +26,7 @@ from .filtered_noise import FilteredNoise
 from .gru import GRU
 from .harmonic_oscillator import OscillatorBank
 from .reverb import Reverb
+from .sinusoids import InharmonicBank
 from .wavetable import WavetableBank
 
 
@@ -372,14 +373,18 @@ class Decoder(nn.Module):
     def __init__(self, conf, noise_rng: str = 'host', seed: int = 0, noise_overlap_add=None, synth=None, band_limited=None):
         super().__init__()
         synth = synth if synth is not None else (getattr(conf, 'synth', None) or 'harmonic')
-        if synth not in ('harmonic', 'wavetable'):
-            raise ValueError(f"Decoder: synth must be 'harmonic' or 'wavetable', got {synth!r}")
+        if synth not in ('harmonic', 'wavetable', 'inharmonic'):
+            raise ValueError(f"Decoder: synth must be 'harmonic', 'wavetable' or 'inharmonic', got {synth!r}")
         self.synth = synth
         if synth == 'wavetable':
             # the second tonal synthesiser (wavetable.py): `c` mixes its N learnable tables instead of weighting harmonics
             # (band_limited: None reads conf.wavetable_band_limited; it means nothing to the oscillator bank, which masks its harmonics)
             self.harmonics = WavetableBank(conf, band_limited=band_limited)
             self.controller = Controller(conf, n_controls=self.harmonics.n_wavetables)
+        elif synth == 'inharmonic':
+            # the third tonal synthesiser (sinusoids.py): `c` weights K partials whose frequencies need not be multiples of f0
+            self.controller = Controller(conf)
+            self.harmonics = InharmonicBank(conf, inharmonicity=float(getattr(conf, 'inharmonicity', 0.0) or 0.0))
         else:
             self.controller = Controller(conf)
             self.harmonics = OscillatorBank(conf)

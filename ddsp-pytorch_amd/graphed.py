@@ -18,6 +18,7 @@ from . import _lib
 from . import dense
 from .filtered_noise import FilteredNoise, noise_forward, noise_ola_stream, ola_stream_state
 from .harmonic_oscillator import osc_forward
+from .sinusoids import refuse_inharmonic
 from .wavetable import refuse_wavetable
 
 
@@ -33,6 +34,7 @@ class GraphedSynth:
             raise ValueError(_NO_LATENT.format(what="GraphedSynth(live=True)"))
         if live:
             refuse_wavetable((getattr(conf, 'synth', None) or 'harmonic') == 'wavetable', "GraphedSynth(live=True)")
+            refuse_inharmonic((getattr(conf, 'synth', None) or 'harmonic') == 'inharmonic', "GraphedSynth(live=True)")
         self.hop, self.sample_rate, self.live = conf.hop_length, conf.sample_rate, live
         dev = torch.device(device)
         H = conf.n_harmonics
@@ -124,6 +126,7 @@ class GraphedLiveDecoder:
         if getattr(decoder, 'z_dims', 0) > 0:
             raise ValueError(_NO_LATENT.format(what="GraphedLiveDecoder"))
         refuse_wavetable(decoder, "GraphedLiveDecoder")
+        refuse_inharmonic(decoder, "GraphedLiveDecoder")
         decoder.check_live(delayed, "GraphedLiveDecoder")
         self.dec = decoder.eval()
         dev = next(decoder.parameters()).device

@@ -1007,6 +1007,48 @@ int ddsp_wavetable_backward_bl(const float *grad_y, const float *f0, const float
 int ddsp_wavetable_set_mip_lds(long bytes);
 
 /*
+ * Inharmonic sinusoid bank (csrc/ddsp_sinusoids.hip): K sinusoids per batch row, each with its own
+ * frame-rate frequency track.
+ *   f [B,T,K] Hz, c [B,T,K], a [B,T,1] -> y [B, T*hop].  An entry of f is valid when it is finite and >= 0; an invalid one has
+ *   g = 0 and weight 0, a valid one g = (double)f / sample_rate and weight c, or 0 where f > sample_rate / 2 (integer division).
+ *   With `normalize` the weights of a frame are divided by their sum (fp64, rounded once; a zero sum gives zero weights).
+ *   y = up(a) * sum_k up(wn_k) * sin(2 pi P_k), up() the oscillator bank's upsampling, and P_k[n] = P0_k + the inclusive sum of the
+ *   same linear interpolation of g_k in real arithmetic, evaluated in fp64 through its closed form per segment
+ *   (n = hop/2 + s hop + j: P = P0 + Phi[s] + (j + 1) (g[s] + (g[s+1] - g[s]) (j + e) / (2 hop)), e = 1 for an even hop, else 0).
+ *
+ * ddsp_sinusoids_supported   1 when the kernels take K partials at this hop (1 <= K <= 1024, 1 <= hop <= 1024).
+ * ddsp_sinusoids_scratch_bytes  bytes of `scratch` the forward wants: 0 (one launch that keeps nothing); `scratch` may be NULL.
+ * ddsp_sinusoids_forward     one launch, the same bits every run and under every plan.  phase_io [B,K] fp64, nullable: the start
+ *                            phases P0 (turns), replaced in place by frac(P[b, T*hop-1, k]) -- the state of a live stream, with
+ *                            no host round trip, so the call can be captured in a graph.  NULL: P0 = 0, nothing is carried.
+ * ddsp_sinusoids_backward    two launches, three with grad_f.  grad_y [B, T*hop] -> grad_c [B,T,K] (with respect to the raw c:
+ *                            the normalisation's backward and the mask are inside), grad_a [B,T,1] and, unless grad_f is NULL,
+ *                            grad_f [B,T,K] (0 at invalid entries), the adjoint of the closed form: per segment the fp32 sums
+ *                            of q = grad_y up(a) up(wn) 2 pi cos(2 pi P), plain and weighted by the coefficients of g[s] and
+ *                            g[s+1], combined by an fp64 suffix sum over the segments.  `phase` [B,K]: the P0 the forward started
+ *                            from (nullable, read only).  scratch: >= ddsp_sinusoids_backward_scratch_bytes bytes, 256-byte
+ *                            aligned: four partials per frame and partial (4x grad_c) and with grad_f three more.  No atomics:
+ *                            every gradient has the same bits every run.
+ * All need T*hop <= 2^24 and return DDSP_ERANGE otherwise; with B == 0 they return 0 and write nothing.
+ *
+ * ddsp_sinusoids_set_form    test hook: bits 8-15 the segments of a chunk, bits 16-23 the segments of an iteration, bits 24-30 the
+ *                            backward's sample records per tile in units of 64 (0: the planner's, csrc/ddsp_sinusoids_plan.h), so
+ *                            that the chunk prefix, several iterations and several tiles run at small shapes; bits 0-7 must be 0.
+ * ddsp_sinusoids_set_grid    test hook: at most this many workgroups (1..2048; 0: the default), so that the stride over the units
+ *                            runs at small shapes.
+ */
+int ddsp_sinusoids_supported(int K, int hop);
+size_t ddsp_sinusoids_scratch_bytes(int B, int T, int K, int hop);
+int ddsp_sinusoids_forward(const float *f, const float *c, const float *a, float *y, void *scratch, double *phase_io, int B, int T,
+                           int K, int hop, int sample_rate, int normalize, void *stream);
+size_t ddsp_sinusoids_backward_scratch_bytes(int B, int T, int K, int hop, int want_grad_f);
+int ddsp_sinusoids_backward(const float *grad_y, const float *f, const float *c, const float *a, void *scratch, float *grad_f,
+                            float *grad_c, float *grad_a, const double *phase, int B, int T, int K, int hop, int sample_rate,
+                            int normalize, void *stream);
+int ddsp_sinusoids_set_form(int mode);
+int ddsp_sinusoids_set_grid(int workgroups);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
