@@ -38,6 +38,9 @@ from .analysis import NoiseAnalyzer, noise_analysis  # noqa: F401
 from .analysis import ControlTransform, transform_controls  # noqa: F401
 from .analysis import ControlMorph, morph_controls  # noqa: F401
 from .analysis import ControlAlign, align_controls, control_features, dtw_align  # noqa: F401
+from . import partials  # noqa: F401
+from .partials import (PartialAnalyzer, partial_analysis, partial_resynthesis, partial_residual, refine_partials,  # noqa: F401
+                       fit_inharmonicity, inharmonic_analysis)
 from .autoencoder import AutoEncoder  # noqa: F401
 from .dataset import AudioData, PLHDataset, load_audio, example_geometry  # noqa: F401
 from .spectral import griffinlim  # noqa: F401
@@ -56,4 +59,6 @@ __all__ = ["OscillatorBank", "FilteredNoise", "Reverb", "causal_fft_convolve", "
            "latest_checkpoint", "mfcc", "MFCC", "ZEncoder", "voices", "allocate_voices", "mix_voices",
            "wavetable", "WavetableBank", "wavetable_forward", "wavetable_backward", "wavetable_form",
            "dirichlet_kernels", "wavetable_mipmaps", "wavetable_forward_bl", "wavetable_backward_bl", "wavetable_form_bl",
-           "sinusoids", "InharmonicBank", "sinusoids_forward", "sinusoids_backward", "stretched_ratios"]
+           "sinusoids", "InharmonicBank", "sinusoids_forward", "sinusoids_backward", "stretched_ratios",
+           "partials", "PartialAnalyzer", "partial_analysis", "partial_resynthesis", "partial_residual", "refine_partials",
+           "fit_inharmonicity", "inharmonic_analysis"]

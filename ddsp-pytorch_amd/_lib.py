@@ -159,6 +159,10 @@ SIGNATURES = {
     "ddsp_sinusoids_backward": (_i32, [_vp] * 9 + [_i32] * 6 + [_vp]),
     "ddsp_sinusoids_set_form": (_i32, [_i32]),
     "ddsp_sinusoids_set_grid": (_i32, [_i32]),
+    "ddsp_partials_supported": (_i32, [_i32, _i32, _i32]),
+    "ddsp_partials_workspace_bytes": (_size, [_long, _long, _i32, _i32, _i32]),
+    "ddsp_partials_analysis": (_i32, [_vp] * 8 + [_long, _long, _i32, _i32, _i32, _i32, _vp]),
+    "ddsp_partials_resynth": (_i32, [_vp] * 6 + [_long, _long, _i32, _i32, _i32, _u32, _vp]),
     "ddsp_pcm_to_mono": (_i32, [_vp, _vp, _long, _i32, _i32, _vp]),
     "ddsp_make_examples": (_i32, [_vp, _long, _vp, _i32, _long, _long, _long, _long, _i32, _vp, _vp, _vp]),
     "ddsp_griffinlim_supported": (_i32, [_i32]),

@@ -52,10 +52,12 @@ from .conditioning import fit_conditioning
 from .tuning import tune_pitch
 from .notes import Expression, extract_notes, note_expression, render_notes
 from .voices import allocate_voices, mix_voices
-from .analysis import align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, transform_controls
+from .analysis import (align_controls, harmonic_analysis, harmonic_residual, morph_controls, noise_analysis, refine_f0,
+                       transform_controls)
 from .decoder import Decoder
 from .encoder import Encoder
-from .sinusoids import refuse_inharmonic
+from .partials import inharmonic_analysis, partial_residual
+from .sinusoids import is_inharmonic, refuse_inharmonic
 from .wavetable import refuse_wavetable
 
 
@@ -208,16 +210,7 @@ class AutoEncoder(nn.Module):
         up to 10 cents off); the dict's f0 is then the refined track.  refine=0 is the analysis along the encoder's own track."""
         refuse_wavetable(self.decoder, "analyse")
         refuse_inharmonic(self.decoder, "analyse")
-        if noise not in (False, True, 'truncated', 'overlap_add'):
-            raise ValueError(f"analyse: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
-        overlap_add = noise == 'overlap_add'
-        if noise and not overlap_add and self.decoder.noise.overlap_add:
-            # the truncated model's H played through the overlap-add would come out too strong
-            raise ValueError("analyse(noise=True) inverts the truncated noise model; it does not apply to a decoder with noise_overlap_add: "
-                             "ask for noise='overlap_add'")
-        if overlap_add and not self.decoder.noise.overlap_add:
-            raise ValueError("analyse(noise='overlap_add') inverts the overlap-add noise model; on a decoder without noise_overlap_add its H "
-                             "would come out too weak: ask for noise=True")
+        overlap_add = self._noise_form(noise, "analyse")
         bank = self.decoder.harmonics
         with torch.no_grad():
             z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
@@ -231,6 +224,55 @@ class AutoEncoder(nn.Module):
         _, resid, ctrl = harmonic_residual(*args, voiced=z.get('voiced'), return_complex=return_complex, refine=refine)
         ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average,
                                    iterations=iterations, overlap_add=overlap_add)
+        return ctrl
+
+    def _noise_form(self, noise, what: str) -> bool:
+        """The `noise` argument of the analysis entry points against the decoder's noise form -> whether it is the overlap-add one."""
+        if noise not in (False, True, 'truncated', 'overlap_add'):
+            raise ValueError(f"{what}: noise must be False, True, 'truncated' or 'overlap_add', got {noise!r}")
+        overlap_add = noise == 'overlap_add'
+        if noise and not overlap_add and self.decoder.noise.overlap_add:
+            # the truncated model's H played through the overlap-add would come out too strong
+            raise ValueError(f"{what}(noise=True) inverts the truncated noise model; it does not apply to a decoder with noise_overlap_add: "
+                             "ask for noise='overlap_add'")
+        if overlap_add and not self.decoder.noise.overlap_add:
+            raise ValueError(f"{what}(noise='overlap_add') inverts the overlap-add noise model; on a decoder without noise_overlap_add its H "
+                             "would come out too weak: ask for noise=True")
+        return overlap_add
+
+    def analyse_partials(self, x: torch.Tensor, iterations: int = 4, model: str = 'stiff', noise=False, refine: int = 0,
+                         return_complex: bool = False, average: int = 1, noise_iterations=None, max_cents: float = 50.0) -> dict:
+        """audio [B, L] -> the inharmonic bank's control dict without the decoder's network (a `synth='inharmonic'` decoder only):
+        the encoder's pitch track (and its voicing, where that is on) as `analyse` takes it, after `refine` steps of
+        analysis.refine_f0, then partials.inharmonic_analysis with the bank's partial count, base ratios and current
+        inharmonicity as the start: dict(f0, ratios, a, c, inharmonicity[, C]).  `self.decoder.harmonics(d)` is the resynthesis
+        of x's partials, and `self.decoder.harmonics.init_from(d)` starts the bank's trainable parameters there.
+
+        noise follows `analyse`'s rules and adds 'H' [B, T, n_noise_filters]: analysis.noise_analysis (with `average` and
+        `noise_iterations`) of the residual partials.partial_residual leaves along the dict's tracks, so that
+        `self.decoder.synthesize(self.analyse_partials(x, noise=True))` is the partials-plus-noise resynthesis of x."""
+        if not is_inharmonic(self.decoder):
+            raise ValueError("analyse_partials: needs the inharmonic synthesiser (build the model with synth='inharmonic'); a harmonic "
+                             "decoder is analysed by analyse()")
+        overlap_add = self._noise_form(noise, "analyse_partials")
+        bank = self.decoder.harmonics
+        with torch.no_grad():
+            z = self.encoder(F.pad(x, (self.padding // 2, self.padding - self.padding // 2)))
+        f0, voiced = z['f0'], z.get('voiced')
+        frames = f0.shape[1]
+        if frames * self.hop_length > x.shape[-1]:
+            raise ValueError(f"the encoder returned {frames} frames of hop {self.hop_length} for {x.shape[-1]} samples")
+        clip, window, K = x[:, :frames * self.hop_length], self.padding + self.hop_length, bank.n_partials
+        if refine:
+            f0 = refine_f0(clip, f0, self.hop_length, bank.sample_rate, K, window, voiced=voiced, iterations=refine, max_cents=max_cents)
+        ctrl = inharmonic_analysis(clip, f0, self.hop_length, bank.sample_rate, K, window, voiced=voiced,
+                                   inharmonicity=bank.inharmonicity.detach().clamp(min=0), base_ratios=bank.base_ratios,
+                                   iterations=iterations, max_cents=max_cents, model=model, return_complex=return_complex)
+        if noise:
+            f = ctrl['f0'].float() * ctrl['ratios'].float()
+            _, resid, _ = partial_residual(clip, f, self.hop_length, bank.sample_rate, window, voiced=voiced)
+            ctrl['H'] = noise_analysis(resid, self.hop_length, self.n_noise_filters, average=average, iterations=noise_iterations,
+                                       overlap_add=overlap_add)
         return ctrl
 
     def transform(self, x: torch.Tensor, stretch=1.0, transpose=0.0, formant=0.0, positions=None, noise=True, refine: int = 0,

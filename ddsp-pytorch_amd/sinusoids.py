@@ -186,6 +186,27 @@ class InharmonicBank(nn.Module):
     def reset_phase(self):
         self.phase.zero_()
 
+    def init_from(self, ctrl) -> None:
+        """Starting values of the two trainable parameters from an analysed dict (partials.inharmonic_analysis): `inharmonicity`
+        becomes the mean of ctrl['inharmonicity'] [B], `detune_cents` [K] the a c weighted mean over the frames of
+        1200 log2(ratios / rho(B)), rho(B) = base_ratios sqrt(1 + B base_ratios^2); a partial without weight keeps detune 0.  The
+        state-dict keys are unchanged."""
+        with torch.no_grad():
+            B_coef = ctrl['inharmonicity'].detach().double().reshape(-1).mean().clamp(min=0)
+            self.inharmonicity.copy_(B_coef.to(self.inharmonicity))
+            r = self.base_ratios.double().to(B_coef.device)
+            rho = r * torch.sqrt(1.0 + B_coef * r * r)
+            ratios = ctrl['ratios'].detach().double()
+            if ratios.dim() != 3 or ratios.shape[-1] != self.n_partials:
+                raise ValueError(f"init_from: expected ratios [B, T, {self.n_partials}], got {tuple(ratios.shape)}")
+            weight = (ctrl['a'].detach().double() * ctrl['c'].detach().double()).expand_as(ratios)
+            ok = torch.isfinite(ratios) & (ratios > 0) & torch.isfinite(weight) & (weight > 0)
+            weight = torch.where(ok, weight, torch.zeros_like(weight))
+            cents = 1200.0 * torch.log2(torch.where(ok, ratios, rho.expand_as(ratios)) / rho)
+            total = weight.sum((0, 1))
+            detune = (weight * cents).sum((0, 1)) / torch.where(total > 0, total, torch.ones_like(total))
+            self.detune_cents.copy_(detune.to(self.detune_cents))
+
     def export_ratios(self) -> torch.Tensor:
         """The learned frequency ratios [K] on the CPU: the inharmonicity as a tensor to inspect, store or give to another model."""
         with torch.no_grad():

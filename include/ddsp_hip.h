@@ -1049,6 +1049,49 @@ int ddsp_sinusoids_set_form(int mode);
 int ddsp_sinusoids_set_grid(int workgroups);
 
 /*
+ * Inharmonic analysis, the inverse of the sinusoid bank (csrc/ddsp_partials.hip).  All fp32 but the
+ * workspace, dense row-major; rows are independent.
+ *   audio [B, N], N = T hop; f [B, T, K] in Hz; voiced [B, T] bytes (nullable: every frame is voiced); sample rate sr; an even
+ *   window W >= 2.
+ *   1. g = (double)f / sr where f is finite and > 0, else 0.
+ *   2. P_k[n] is the bank's phase with P0 = 0: the inclusive sum of the linearly interpolated g_k in real arithmetic through its
+ *      closed form per segment (above: n = hop/2 + s hop + j: P = Phi[s] + (j + 1) (g[s] + (g[s+1] - g[s]) (j + e) / (2 hop)); the
+ *      samples n < hop/2 in front: P = (n + 1) g[0]), in fp64, Phi kept modulo 1.
+ *   3. Frame t covers the samples s_t + j, j < W, s_t = t hop - floor((W - hop) / 2); w is the periodic Hann window; samples
+ *      outside [0, N) are left out and norm_t is the sum of w over the samples inside (ddsp_harm_analysis' items 3 and 4).
+ *   4. C[t,k] = (2 / norm_t) sum_j w[j] audio[s_t + j] exp(-2 pi i P_k[s_t + j]).
+ *   5. C[t,k] = 0 where f[t,k] is not finite or <= 0, where f[t,k] > sr / 2 (integer division; the bank's mask on the frame's own
+ *      entry), and on an unvoiced frame.
+ *   6. amp = |C|, a = sum_k amp, c = amp / a, and c = 1 / K where a = 0.
+ *   7. On the frames whose window lies inside the clip and where C != 0, with D the sum of item 4 under w'[j] = (pi / W)
+ *      sin(2 pi j / W), both unscaled:  f_re[t,k] = mean_w(up(f_k)) - sr / (2 pi) (Im D Re C - Re D Im C) / |C|^2, mean_w the
+ *      window-weighted mean of the upsampled (cleaned) track in fp64.  Elsewhere f_re has the bits of f.
+ *   8. harm[n] = sum_k Re(up(C[:,k])[n] exp(+2 pi i P_k[n])), resid = audio - harm.
+ *
+ * ddsp_partials_supported        1 when the kernels take this shape: 1 <= K <= 256, 1 <= hop <= 1024, W even in 2 .. 4096.  No device.
+ * ddsp_partials_workspace_bytes  bytes of `workspace` (16-byte aligned) for both calls; 0: sizes that are not positive, out of range
+ *                                or overflowing.  It holds the two windows and Phi, g and d / (2 hop) [B, T, K] in fp64.
+ * ddsp_partials_analysis   -> C [B, T, K] interleaved (re, im), a [B, T], c [B, T, K] and, unless f_re is NULL, f_re [B, T, K]; it
+ *                          fills `workspace`.  Three launches (prefix, windows, analysis).  With f_re == NULL the second window
+ *                          and its two FMAs per (sample, partial) do not exist.
+ * ddsp_partials_resynth    C [B, T, K] interleaved (8-byte aligned) -> harm [B, N] and, where resid is not NULL, resid = audio - harm
+ *                          (audio may be NULL otherwise).  With DDSP_PARTIALS_PHASE_READY in flags the workspace still holds the
+ *                          prefix of a ddsp_partials_analysis or ddsp_partials_resynth call with the same f, B, T, K, hop and
+ *                          sample_rate, and the prefix launch is left out.  Two launches, one with the flag.
+ * Beyond the range above, or with T hop > 2^24 or B T K or B T hop > 2^40: DDSP_ERANGE.  A null pointer, an odd W, an unknown flag
+ * or a size that is not positive: DDSP_EINVAL before anything touches the device; B == 0 returns 0.  No atomics on global memory,
+ * nothing allocated or synchronised: the calls can be captured in a graph.  The same bits every run, and for a row whatever its
+ * batch.
+ */
+#define DDSP_PARTIALS_PHASE_READY 1u
+int ddsp_partials_supported(int K, int hop, int W);
+size_t ddsp_partials_workspace_bytes(long B, long T, int K, int hop, int W);
+int ddsp_partials_analysis(const float *audio, const float *f, const uint8_t *voiced, float *C, float *a, float *c, float *f_re,
+                           void *workspace, long B, long T, int K, int hop, int W, int sample_rate, void *stream);
+int ddsp_partials_resynth(const float *C, const float *f, const float *audio, float *harm, float *resid, void *workspace, long B,
+                          long T, int K, int hop, int sample_rate, unsigned flags, void *stream);
+
+/*
  * Training-set audio (dataset/audio_dataset.py): the stages between the file read and the encoder.  All fp32 out.
  *
  * ddsp_pcm_to_mono   interleaved PCM pcm [L, C] (as the WAV file stores it) -> y [L]: each sample scaled as
